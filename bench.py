@@ -13,6 +13,13 @@ product's own HIP runtime; no torch in a GPU process).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]       (N > 1: this process starts N ranks)
     torchrun --nproc-per-node N bench.py --gpus N ...          (each rank started by torchrun)
+
+A plain run does what the headline needs and no more: it renders the frames, warms up, times the K
+steps (HIP events around the ICP kernel on every 16th frame, as always), and prints the line.
+--full adds every measurement that takes a run of its own, each in a fresh context after the timed
+one: the per-stage breakdown, the canonical-algebra pass, the per-call rates, C1, the HBM copy rate
+and the CPU baseline.  --dump-outputs DIR writes what the timed context holds after its last step
+(DIR/<name>.npy, float32 / float64) so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -80,6 +87,14 @@ def parse():
     ap.add_argument("--colour", action="store_true",
                     help="C2 with the colour TSDF: Voxel_s_rgb voxels integrated from a synthetic colour stream "
                          "(depth+colour, TopFu::operator()(depth, image), topfu.hpp:80); GPU-rendered RGB frames")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline, each a run of its own: the per-stage "
+                         "breakdown pass, the canonical-algebra pass, the per-call rates, C1, the HBM copy rate and "
+                         "the CPU baseline (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed context computed in its last step (the step's "
+                         "per-frame verdicts, pose, counters, rendered image, ICP-map raycast, hash table, voxels) as "
+                         "DIR/<name>.npy, float32 / float64; arrays over 2^19 rows as a fixed seeded sample of rows")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bounded CPU-baseline sample length")
     ap.add_argument("--no-profile", action="store_true", help="disable the per-stage HIP-event timing")
@@ -143,6 +158,52 @@ def pmc_tracked_bytes(pmc, stage):
     (profiles/pmc_traffic.json, tools/pmc_frames_summary.py), else the older per-launch figure."""
     e = pmc.get(stage) or {}
     return (e.get("tracked") or {}).get("bytes", e.get("bytes_per_launch"))
+
+
+DUMP_MAX_ROWS = 1 << 19      # rows of one dumped array (the arrays of a run have 16 columns in all: 34 MB)
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 0x7F0517
+
+
+def sample_rows(a):
+    """All rows of a (first axis), or -- over DUMP_MAX_ROWS -- the rows at a fixed seeded draw of
+    indices, in index order."""
+    if len(a) <= DUMP_MAX_ROWS:
+        return a
+    return a[np.sort(np.random.default_rng(DUMP_SEED).integers(0, len(a), DUMP_MAX_ROWS))]
+
+
+def dump_rows(a):
+    """sample_rows(a) as float32 (float64 where float32 would round an integer)."""
+    a = sample_rows(np.asarray(a))
+    wide = a.dtype.kind in "iu" and a.size and int(np.abs(a).max()) > (1 << 24)
+    return np.ascontiguousarray(a, np.float64 if wide or a.dtype == np.float64 else np.float32)
+
+
+def dump_fields(rec, names):
+    """The named fields of a structured array's sample_rows as columns."""
+    rec = sample_rows(rec)
+    return np.stack([rec[n].astype(np.int64) for n in names], 1)
+
+
+def scene_outputs(tf, colour=False):
+    """The scene a context holds: hash table (x, y, z, offset, ptr per entry) and voxels (sdf, w)."""
+    out = {"hash": dump_fields(tf.hash(), ("x", "y", "z", "offset", "ptr")),
+           "voxels": dump_fields(tf.vba(), ("sdf", "w"))}
+    if colour:
+        out["voxels_rgb"] = tf.vba_rgb()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy (dump_rows), DUMP_MAX_BYTES at the most."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = dump_rows(a)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, (name, total)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def omp_threads():
@@ -338,6 +399,8 @@ def c3_integrate(args):
                         "voxel_lanes_total": int(nb) * 128,
                         "reference_equivalent_bytes": int(b_ref),
                         "reference_equivalent_GBs": round(b_ref / (ms * 1e-3) / 1e9, 2)}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, scene_outputs(tf))
     print(json.dumps(out))
     tf.close()
 
@@ -379,6 +442,10 @@ def c3_raycast(args):
                         "frac": round(ach / PEAK_HBM_GBS, 5), "traffic": pmc.get("bytes_per_launch"),
                         "kernel": "k_raycast_pair", "algorithmic_bytes_per_launch": b, "avg_launch_ms": round(ms, 5),
                         "timing": "HIP events around back-to-back launches on the context stream"}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"raycast": ray.reshape(-1, 4),
+                                         "grey": tf.frame_grey().reshape(-1, 4),
+                                         "visible_type": tf.visible_type()})
     print(json.dumps(out))
     tf.close()
 
@@ -487,6 +554,8 @@ def c5e_bench(args):
     rep.barrier()
     elapsed = time.perf_counter() - t0
     tot = tf.totals()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(scene_outputs(tf), records=dump_fields(recs[-1], recs[-1].dtype.names)))
     rec = np.concatenate(recs)
     timed = rec[warm * F:]
     nb = tf.params().n_blocks
@@ -594,6 +663,8 @@ def standin(args):
     elapsed = time.perf_counter() - t0
     emax, total, multi = rep.summary(elapsed, n, identity=rank_identity(args, local_rank, rank),
                                      extra={"frames_ok": ok})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pose": o.pose()})
     if rank == 0:
         print(json.dumps({"metric": "stand-in: oracle frames/sec @80x60 (launcher test, not a GPU number)",
                           "value": round(total / emax, 4), "unit": "frames/s", "n_gpus": world, "steps": n,
@@ -649,7 +720,7 @@ def main():
         pkw.update(use_swapping=1, swap_transfer_blocks=args.swap_transfer_blocks)
     if args.colour:
         pkw.update(voxel_rgb=1)            # rgb_intr 0 / depth_to_rgb 0: the colour camera registered with the depth one
-    n_breakdown = 0 if args.no_profile else min(args.breakdown_frames, args.steps * F)
+    n_breakdown = min(args.breakdown_frames, args.steps * F) if args.full and not args.no_profile else 0
     n_frames = (args.warmup + args.steps) * F
     seed = (13 if cfg["walk"] else 7) + rank
     dev = (walk_frames if cfg["walk"] else orbit_frames)(n_frames, W, H, seed)
@@ -664,16 +735,15 @@ def main():
             return tfx.process_frames(base + k0 * frame_bytes, n)
         return tfx.process_frames(base + k0 * frame_bytes, n, rgb_frames=rgb.ptr + k0 * rgb_bytes, rgb_stride=rgb_bytes)
 
-    # per-stage breakdown first (outside the timed region, a context of its own): a fresh context
-    # replays the warm-up and the first frames of the timed region with every stage timed; the
-    # dominant single-kernel stage -- by measured time per full launch -- is the one the timed
-    # region times and the roofline names
+    # --full: per-stage breakdown first (outside the timed region, a context of its own): a fresh
+    # context replays the warm-up and the first frames of the timed region with every stage timed;
+    # the dominant single-kernel stage -- by measured time per full launch -- is the one the timed
+    # region times and the roofline names (a plain run: the ICP kernel, the one that pass finds)
     prof = {}
-    lanes_bd = nvis_bd = None
-    tb = TopFu(default_params(**pkw), device=local_rank)
-    single = [k for k in SINGLE_KERNEL_STAGES if k != "icp" or tb.icp_persistent()]
-    dominant = "icp" if tb.icp_persistent() else "raycast_icp"
+    lanes_bd = nvis_bd = dominant = None
     if n_breakdown:
+        tb = TopFu(default_params(**pkw), device=local_rank)
+        single = [k for k in SINGLE_KERNEL_STAGES if k != "icp" or tb.icp_persistent()]
         run(tb, 0, args.warmup * F)
         tb.profile(True)
         tb.reset_totals()
@@ -686,10 +756,13 @@ def main():
         avg = {k: prof[k][0] / prof[k][1] for k in single if prof[k][1]}
         if avg:
             dominant = max(avg, key=avg.get)
-    tb.close()
-    device_sync()
+        tb.close()
+        device_sync()
 
     tf = TopFu(default_params(**pkw), device=local_rank)
+    single = [k for k in SINGLE_KERNEL_STAGES if k != "icp" or tf.icp_persistent()]
+    if dominant is None:
+        dominant = "icp" if tf.icp_persistent() else "raycast_icp"
     device_sync()
     for w in range(args.warmup):                      # warm-up: whole steps (full enqueue groups)
         run(tf, w * F, F)
@@ -710,6 +783,13 @@ def main():
     prof_timed = tf.profile_read() if not args.no_profile else {}
     tot = tf.totals()
     st = tf.stats()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after the last step: the step's verdicts, the pose,
+        # the counters, the image renderImage made in the last frame, the ICP maps' points, the scene
+        dump_outputs(args.dump_outputs, dict(
+            scene_outputs(tf, args.colour), ok=oks[-1], pose=tf.getCameraPose(),
+            counters=np.array([st[k] for k in ("lastFreeBlockId", "lastFreeExcessListId", "noVisibleEntries")]),
+            grey=tf.frame_grey().reshape(-1, 4), raycast=tf.raycast_result().reshape(-1, 4)))
     # the timed context closes here: the measurements below each run a context of their own, and
     # with two contexts on a device every persistent ICP launch is ordered after the other
     # context's by a stream event (tf_capi.hip icp_order_*), a dispatch gap no single user sees
@@ -720,7 +800,7 @@ def main():
     # a fresh context under the canonical algebra (when the headline ran the reference's) -- wall
     # clock, and the ICP's full launches timed as in the timed region
     other = None
-    if rgb is None and tf_alg != 0 and not args.no_other_algebra:
+    if args.full and rgb is None and tf_alg != 0 and not args.no_other_algebra:
         tc = TopFu(default_params(**pkw), device=local_rank)
         tc.set_pose_algebra("canonical")
         device_sync()
@@ -748,7 +828,7 @@ def main():
     # frames of the timed region, from a fresh context, and the batched rate of a fresh context on
     # the same frames beside it (the orbit's cost per frame varies along it: compare like with like)
     per_call = per_call_batched = None
-    nc = min(args.per_call_frames, args.steps * F) if rgb is None else 0   # (colour: RGB frames wait for the whole frame)
+    nc = min(args.per_call_frames, args.steps * F) if args.full and rgb is None else 0   # (colour: RGB frames wait for the whole frame)
     if nc > 0:
         pc_base = base + args.warmup * F * frame_bytes
         tc = TopFu(default_params(**pkw), device=local_rank)
@@ -763,7 +843,7 @@ def main():
     # on a fresh context each time: wall time of the call (host sync included), median of 5 after a
     # warm-up, beside the CPU baseline's c1_ms_per_frame on the same frame
     c1_gpu = None
-    if rgb is None:
+    if args.full and rgb is None:
         c1 = []
         for _ in range(6):
             t1 = TopFu(default_params(**pkw), device=local_rank)
@@ -830,9 +910,9 @@ def main():
                                             "hand-offs -> the 6x6 solve on one wave (the reference's algebra: the "
                                             "lane-parallel Jacobi SVD, ~20 k cycles; DESIGN.md 5); the previous-frame "
                                             "gathers hit L2, so PMC traffic is a fraction of the algorithmic bytes")
-        stream_gbs = round(hbm_stream_copy(), 1)
+        stream_gbs = round(hbm_stream_copy(), 1) if args.full else None
         cpu = None
-        if not args.no_cpu_baseline and world == 1:        # (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and world == 1:        # (rank 0 at N = 1 only)
             # all cores: the OpenMP build of the oracle; 1 thread: the serial build (reported
             # beside); BASELINE.md protocol: one warm-up frame, then the median of 5 repeats of a
             # bounded sample of the same stream

@@ -15,7 +15,7 @@ for v in "$@"; do
 done
 for round in 1 2; do
   for v in "$@"; do
-    TFUSION_HIP_LIB=$(lib $v) timeout -k 10 300 python bench.py --colour --no-cpu-baseline --per-call-frames 0 > $O/bench_$v.log 2>&1 \
+    TFUSION_HIP_LIB=$(lib $v) timeout -k 10 300 python bench.py --full --colour --no-cpu-baseline --per-call-frames 0 > $O/bench_$v.log 2>&1 \
       || { tail -20 $O/bench_$v.log; exit 1; }
     python -c "
 import json

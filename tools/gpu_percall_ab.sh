@@ -11,7 +11,7 @@ timeout -k 10 700 python -u -m pytest $SEL -m gpu -x -q --timeout 400 --timeout-
 tail -1 $O/tests.log
 for v in "1 1" "1 0" "0 0"; do
   set -- $v
-  TFUSION_PERCALL_EARLY=$1 TFUSION_PERCALL_DEFER=$2 timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_$1$2.log 2>&1 || { tail -20 $O/bench_$1$2.log; exit 1; }
+  TFUSION_PERCALL_EARLY=$1 TFUSION_PERCALL_DEFER=$2 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_$1$2.log 2>&1 || { tail -20 $O/bench_$1$2.log; exit 1; }
   python -c "
 import json
 e=json.loads(open('$O/bench_$1$2.log').read().strip().splitlines()[-1])

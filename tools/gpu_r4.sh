@@ -15,5 +15,5 @@ timeout -k 10 300 python bench.py --config C5E > $O/bench_C5E.log 2>&1 || { tail
 tail -1 $O/bench_C5E.log | cut -c1-400
 timeout -k 10 300 python bench.py --config C5E --swapping > $O/bench_C5E_swapping.log 2>&1 || { tail -20 $O/bench_C5E_swapping.log; exit 1; }
 tail -1 $O/bench_C5E_swapping.log | cut -c1-400
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
 tail -1 $O/bench_c2.log | cut -c1-200

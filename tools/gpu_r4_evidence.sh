@@ -13,7 +13,7 @@ TFUSION_HIP_LIB=tools/_build/libtfusion_hip_timing.so timeout -k 10 120 python t
 tail -4 $O/icp_timeline.txt | cut -c1-250
 for cfg in "--colour" "--config C3" "--config C3I" "--config C3R" "--config C5" "--config C5E" "--config C5E --swapping"; do
   name=$(echo "$cfg" | tr -d ' -')
-  timeout -k 10 400 python bench.py $cfg --no-cpu-baseline > $O/bench_$name.log 2>&1 || { tail -20 $O/bench_$name.log; exit 1; }
+  timeout -k 10 400 python bench.py --full $cfg --no-cpu-baseline > $O/bench_$name.log 2>&1 || { tail -20 $O/bench_$name.log; exit 1; }
   tail -1 $O/bench_$name.log | cut -c1-200
 done
 cd /tmp && export TMPDIR=/tmp

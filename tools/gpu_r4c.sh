@@ -11,5 +11,5 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_failures.py -m gpu -x -v --
 tail -3 $O/tests_fail.log
 timeout -k 10 800 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread --deselect tests/test_gpu_failures.py > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-timeout -k 10 300 python bench.py > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
 tail -1 $O/bench_c2.log | cut -c1-300

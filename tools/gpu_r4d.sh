@@ -15,7 +15,7 @@ tail -3 $O/icp_timeline.txt | cut -c1-250
 for round in 1 2; do
   for v in tree "$@"; do
     if [ $v = tree ]; then L=$PWD/topfusion_amd/libtfusion_hip.so; else L=$PWD/tools/_build/$v/libtfusion_hip.so; fi
-    TFUSION_HIP_LIB=$L timeout -k 10 200 python bench.py --no-cpu-baseline --per-call-frames 0 > $O/ab_${v}_$round.log 2>&1 \
+    TFUSION_HIP_LIB=$L timeout -k 10 200 python bench.py --full --no-cpu-baseline --per-call-frames 0 > $O/ab_${v}_$round.log 2>&1 \
       || { tail -20 $O/ab_${v}_$round.log; exit 1; }
     python -c "
 import json

@@ -13,7 +13,7 @@ st=0
 timeout -k 10 1000 python -u -m pytest tests -m gpu -q -rs --timeout 600 --timeout-method thread > $O/tests.log 2>&1 || st=$?
 tail -12 $O/tests.log
 [ $st -eq 0 ] || [ $st -eq 1 ] || exit $st
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python -c "
 import json
 e=json.loads(open('$O/bench.json').read().strip().splitlines()[-1])

@@ -20,6 +20,6 @@ python3 tools/pmc_traffic.py gpurun_out/pmc_${TAG}_c2 C2 $O/pmc_traffic.json > /
 python3 tools/pmc_traffic.py gpurun_out/pmc_${TAG}_c3i C3I $O/pmc_traffic.json > /dev/null
 for cfg in "--config C3I" "--config C5E" "--colour"; do
   name=$(echo "$cfg" | tr -d ' -')
-  timeout -k 10 400 python bench.py $cfg --no-cpu-baseline > $O/bench_$name.log 2>&1 || { tail -20 $O/bench_$name.log; exit 1; }
+  timeout -k 10 400 python bench.py --full $cfg --no-cpu-baseline > $O/bench_$name.log 2>&1 || { tail -20 $O/bench_$name.log; exit 1; }
   tail -1 $O/bench_$name.log | cut -c1-200
 done

@@ -13,8 +13,8 @@ timeout -k 10 200 ./tools/micro/svd_lanes_stats tests/golden/icp_systems_C2_open
 cat $O/svd_lanes.txt
 timeout -k 10 700 python -u -m pytest $SEL -m gpu -x -v -rs --timeout 600 --timeout-method thread > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_canonical.json 2> $O/bench_canonical.err || { tail -20 $O/bench_canonical.err; exit 1; }
-timeout -k 10 300 python bench.py --no-cpu-baseline --pose-algebra opencv4 > $O/bench_opencv4.json 2> $O/bench_opencv4.err || { tail -20 $O/bench_opencv4.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_canonical.json 2> $O/bench_canonical.err || { tail -20 $O/bench_canonical.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --pose-algebra opencv4 > $O/bench_opencv4.json 2> $O/bench_opencv4.err || { tail -20 $O/bench_opencv4.err; exit 1; }
 python - <<PY
 import json
 for n in ("canonical", "opencv4"):

@@ -15,7 +15,7 @@ for b in 0 1; do
 done
 timeout -k 10 900 python -u -m pytest $SEL -m gpu -x -v -rs --timeout 400 --timeout-method thread > $O/tests.log 2>&1 || { tail -40 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-ARGS="--no-cpu-baseline --no-other-algebra"
+ARGS="--full --no-cpu-baseline --no-other-algebra"
 for k in 1 2; do
   for b in 0 1; do
     TFUSION_INTEG_BANDS=$b timeout -k 10 300 python bench.py $ARGS > $O/bench_b${b}_$k.json 2> $O/bench_b${b}_$k.err || { tail -20 $O/bench_b${b}_$k.err; exit 1; }

@@ -8,7 +8,7 @@ O=gpurun_out/${1:-r6b}
 mkdir -p $O
 timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -30 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 420 python bench.py > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 420 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python - <<PY
 import json
 e = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

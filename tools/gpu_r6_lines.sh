@@ -7,7 +7,7 @@ O=gpurun_out/${1:-r6l}
 mkdir -p $O
 for cfg in "--colour" "--config C3" "--config C3I" "--config C3R" "--config C5" "--config C5E" "--config C5E --swapping"; do
   name=$(echo "$cfg" | tr -d ' -')
-  timeout -k 10 300 python bench.py $cfg --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err || { tail -20 $O/bench_$name.err; exit 1; }
+  timeout -k 10 300 python bench.py --full $cfg --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.err || { tail -20 $O/bench_$name.err; exit 1; }
   python3 -c "
 import json,sys
 e=json.loads(open('$O/bench_$name.json').read().strip().splitlines()[-1])

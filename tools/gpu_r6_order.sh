@@ -10,7 +10,7 @@ tail -1 $O/tests.log
 TFUSION_HIP_LIB=tools/_build/ptl/libtfusion_hip.so timeout -k 10 200 python tools/pair_timeline.py > $O/pair_timeline.txt 2>&1 || { tail -20 $O/pair_timeline.txt; exit 1; }
 PTL_BATCH=1 TFUSION_HIP_LIB=tools/_build/ptl_la/libtfusion_hip.so timeout -k 10 200 python tools/pair_timeline.py > $O/pair_timeline_batch.txt 2>&1 || { tail -20 $O/pair_timeline_batch.txt; exit 1; }
 head -12 $O/pair_timeline.txt | cut -c1-200; echo ==; head -12 $O/pair_timeline_batch.txt | cut -c1-200
-ARGS="--no-cpu-baseline --no-other-algebra"
+ARGS="--full --no-cpu-baseline --no-other-algebra"
 for k in 1 2; do
   timeout -k 10 300 python bench.py $ARGS > $O/bench_new_$k.json 2> $O/bench_new_$k.err || { tail -20 $O/bench_new_$k.err; exit 1; }
   TFUSION_HIP_LIB=tools/_build/oldorder/libtfusion_hip.so timeout -k 10 300 python bench.py $ARGS > $O/bench_old_$k.json 2> $O/bench_old_$k.err || { tail -20 $O/bench_old_$k.err; exit 1; }

@@ -5,7 +5,7 @@ cd $R
 O=$R/gpurun_out/${1:-r6rep}
 mkdir -p $O
 for k in 1 2 3; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_$k.json 2> $O/bench_$k.err || { tail -20 $O/bench_$k.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_$k.json 2> $O/bench_$k.err || { tail -20 $O/bench_$k.err; exit 1; }
 done
 python3 - <<PY
 import json

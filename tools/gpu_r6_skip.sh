@@ -7,7 +7,7 @@ O=$R/gpurun_out/${1:-r6skip}
 mkdir -p $O
 timeout -k 10 700 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_colour.py tests/test_gpu_engines.py -m gpu -x -q -rs --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-ARGS="--no-cpu-baseline --no-other-algebra"
+ARGS="--full --no-cpu-baseline --no-other-algebra"
 for k in 1 2; do
   timeout -k 10 300 python bench.py $ARGS > $O/bench_new_$k.json 2> $O/bench_new_$k.err || { tail -20 $O/bench_new_$k.err; exit 1; }
   TFUSION_HIP_LIB=tools/_build/noskip/libtfusion_hip.so timeout -k 10 300 python bench.py $ARGS > $O/bench_old_$k.json 2> $O/bench_old_$k.err || { tail -20 $O/bench_old_$k.err; exit 1; }

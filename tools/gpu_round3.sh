@@ -6,10 +6,10 @@ TAG=${1:-final}
 O=$R/gpurun_out/r3_$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
 tail -1 $O/bench_c2.log | cut -c1-200
 for cfg in C3 C3I C3R; do
-  timeout -k 10 400 python bench.py --config $cfg --no-cpu-baseline > $O/bench_$cfg.log 2>&1 || { tail -20 $O/bench_$cfg.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --config $cfg --no-cpu-baseline > $O/bench_$cfg.log 2>&1 || { tail -20 $O/bench_$cfg.log; exit 1; }
   tail -1 $O/bench_$cfg.log | cut -c1-160
 done
 cd /tmp && export TMPDIR=/tmp

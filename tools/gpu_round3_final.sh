@@ -8,13 +8,13 @@ TAG=${1:-final}
 O=$R/gpurun_out/r3f_$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 1; }
 tail -1 $O/bench_c2.log | cut -c1-160
 for cfg in C3 C3I C3R C5; do
-  timeout -k 10 400 python bench.py --config $cfg --no-cpu-baseline > $O/bench_$cfg.log 2>&1 || { tail -20 $O/bench_$cfg.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --config $cfg --no-cpu-baseline > $O/bench_$cfg.log 2>&1 || { tail -20 $O/bench_$cfg.log; exit 1; }
   tail -1 $O/bench_$cfg.log | cut -c1-160
 done
-timeout -k 10 400 python bench.py --config C5 --swapping --no-cpu-baseline > $O/bench_C5_swapping.log 2>&1 || { tail -20 $O/bench_C5_swapping.log; exit 1; }
+timeout -k 10 400 python bench.py --full --config C5 --swapping --no-cpu-baseline > $O/bench_C5_swapping.log 2>&1 || { tail -20 $O/bench_C5_swapping.log; exit 1; }
 tail -1 $O/bench_C5_swapping.log | cut -c1-160
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
