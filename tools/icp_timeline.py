@@ -42,7 +42,8 @@ for i in range(its):
                      f" maps in {(tl[i + 1, 2 * NW + 9] - t0) / 100.0:5.2f}]")
     print(line)
 # the tail's halves on the shader clock, each run twice back to back (the second run's code is
-# in the instruction cache): workgroup 0, per iteration
+# in the instruction cache): workgroup 0, per iteration.  The OpenCV algebras run each half once:
+# their "again" columns read 0.
 try:
     tb = (ctypes.c_longlong * 256)()
     _lib.load().tf_debug_icp_tail_cycles(tb)

@@ -2,7 +2,9 @@
 // serial one (icp_cv_solve_svd6) and the oracle (tfo_cv_solve_svd6), bit for bit, on captured ICP
 // systems (tools/svd_systems.py), random ICP-like systems and degenerate ones (A = 0, rank
 // deficient, huge / tiny scales); then the latency of both forms on one wave, each solve
-// depending on the last.
+// depending on the last.  Built three times (plain, -DTF_SV_STATS, -DTF_SV_TIMING) and once more
+// with -DSV_ONESHOT=0 (svd_lanes_oneshot0: every sweep through the levels) for the A/B of the
+// batched final-sweep test.
 //   make -C tools/micro svd_lanes;  ./tools/micro/svd_lanes tests/golden/icp_systems_C2_opencv4.f32
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -10,10 +12,11 @@
 #include <cstring>
 #include <vector>
 #ifdef TF_SV_STATS                               // (the svd_lanes_stats build: counts, not timing)
-__device__ unsigned long long g_sv_stats[4];     // rotations, fast-path fallback levels, zero-SV finishes
+__device__ unsigned long long g_sv_stats[8];     // rotations, fast-path fallback levels, zero-SV finishes,
+                                                 // batched final-sweep tests (tries), those that ended the sweeps (hits)
 #endif
 #ifdef TF_SV_TIMING                              // (the svd_lanes_timing build: cycles per level phase)
-__device__ long long g_sv_t[8];
+__device__ long long g_sv_t[9];
 #endif
 #include "../../topfusion_amd/csrc/tf_icp_tail.h"
 
@@ -142,7 +145,7 @@ int main(int argc, char** argv)
     float *dS, *dX, *dO; int* dB; long long* dC;
     hipMalloc(&dS, sys.size() * 4); hipMalloc(&dX, (size_t)n * 6 * 4); hipMalloc(&dB, 4); hipMalloc(&dC, 16 * 8); hipMalloc(&dO, 64);
     hipMemcpy(dS, sys.data(), sys.size() * 4, hipMemcpyHostToDevice);
-    unsigned long long z4[4] = {};
+    unsigned long long z4[8] = {};
     for (int alg = 4; alg >= 2; alg -= 2) {
         hipMemset(dB, 0, 4);
 #ifdef TF_SV_STATS
@@ -153,7 +156,7 @@ int main(int argc, char** argv)
         else hipLaunchKernelGGL(k_check<2>, dim3(2048), dim3(64), 0, 0, dS, n, dX, dB);
         int bad = -1;
         hipMemcpy(&bad, dB, 4, hipMemcpyDeviceToHost);
-        unsigned long long st[4] = {};
+        unsigned long long st[8] = {};
 #ifdef TF_SV_STATS
         hipMemcpyFromSymbol(st, HIP_SYMBOL(g_sv_stats), sizeof(st));
 #endif
@@ -161,6 +164,10 @@ int main(int argc, char** argv)
                alg, bad, n, ncap, nrand, ndeg);
         printf("  rotations %llu, fast-path fallbacks %llu (%.2e), zero-singular-value finishes %llu\n", st[0], st[1],
                st[0] ? (double)st[1] / (double)st[0] : 0.0, st[2]);
+#ifdef TF_SV_STATS
+        printf("  batched final-sweep tests: tries %llu (%.3f per solve), hits %llu (%.3f per solve)\n", st[3],
+               (double)st[3] / n, st[4], (double)st[4] / n);
+#endif
         if (alg == 4) {                      // the oracle (CPU) on every system
             std::vector<float> xl((size_t)n * 6);
             hipMemcpy(xl.data(), dX, xl.size() * 4, hipMemcpyDeviceToHost);
@@ -185,7 +192,7 @@ int main(int argc, char** argv)
     hipLaunchKernelGGL(k_time<0>, dim3(1), dim3(64), 0, 0, dS, ns, N, dC, dO);
 #ifdef TF_SV_TIMING
     {
-        long long z8[8] = {};
+        long long z8[9] = {};
         hipMemcpyToSymbol(HIP_SYMBOL(g_sv_t), z8, sizeof(z8));       // (the check kernels' stamps dropped)
     }
 #endif
@@ -195,16 +202,18 @@ int main(int argc, char** argv)
     hipMemcpy(c, dC, sizeof(c), hipMemcpyDeviceToHost);
 #ifdef TF_SV_TIMING
     {
-        long long t[8];
+        long long t[9];
         hipMemcpyFromSymbol(t, HIP_SYMBOL(g_sv_t), sizeof(t));
-        const char* nm[8] = { "previous level end -> level start", "partner bpermute", "sums (DPP gather + fma)",
+        const char* nm[9] = { "previous level end -> level start", "partner bpermute", "sums (DPP gather + fma)",
                               "test + ballot", "(c, s) chain + checks", "broadcast + update",
-                              "after the sweeps: |row|, sort, gather", "normalise + back substitution" };
+                              "after the sweeps: |row|, sort, gather", "normalise + back substitution",
+                              "batched final-sweep test" };
         printf("per-phase cycles per solve (timing build, stamps included):\n");
-        for (int k = 0; k < 8; ++k) printf("  %-36s %9.1f\n", nm[k], (double)t[k] / (N + 20));
+        for (int k = 0; k < 9; ++k) printf("  %-36s %9.1f\n", nm[k], (double)t[k] / (N + 20));
     }
 #endif
-    printf("latency over the first %d systems, one wave, dependent solves (s_memtime cycles per solve):\n", ns);
+    printf("latency over the first %d systems, one wave, dependent solves (s_memtime cycles per solve), SV_ONESHOT %d:\n", ns,
+           (int)SV_ONESHOT);
     printf("  serial  icp_cv_solve_svd6        %9.1f\n", (double)c[0] / N);
     printf("  lanes   icp_cv_solve_svd6_lanes  %9.1f   (%.2fx)\n", (double)c[1] / N, (double)c[0] / (double)c[1]);
     return 0;

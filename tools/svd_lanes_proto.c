@@ -8,7 +8,12 @@
  * systems and on random ones.
  *
  *   gcc -O2 -ffp-contract=off tools/svd_lanes_proto.c -Loracle -loracle -lm -o tools/_build/svd_proto
- *   LD_LIBRARY_PATH=oracle tools/_build/svd_proto tools/_build/svd_systems_C2.f32
+ *   LD_LIBRARY_PATH=oracle tools/_build/svd_proto [-oneshot] tools/_build/svd_systems_C2.f32
+ *
+ * -oneshot: the batched final-sweep test (SV_ONESHOT, icp_sv_oneshot) -- after level 2 of a
+ * period whose head pairs rotated nothing, the other 11 pairs of that sweep tested on the current
+ * state; all skip: the sweeps end there.  Prints levels, tries and hits per solve.  (The kernel
+ * tests all 15 pairs there, the four head pairs again on the same state: the same outcome.)
  *
  * Test infrastructure (tools/): models the kernel's schedule; the product never runs it. */
 #include <float.h>
@@ -70,6 +75,8 @@ static int safe_f(double v)
 
 static uint64_t g_rng_c;
 static long long g_fast, g_fallback, g_levels, g_solves;
+static int g_oneshot;                      /* -oneshot */
+static long long g_tries, g_hits;
 
 /* (c, s) of one rotation from p (already doubled), a, b: the serial form (beta < 0 branch and
    all), exactly as the oracle */
@@ -172,6 +179,21 @@ static void solve_levels(const float A[36], const float bv[6], float x[6], int f
             if (L == 2 && s >= 0) {            /* sweep s complete */
                 if (!changed_tail || s == 29) goto done;
             }
+            if (L == 2 && g_oneshot && head_on && !changed_head) {
+                /* sweep s + 1's head pairs rotated nothing: its other 11 pairs (the tail pairs
+                   of levels 0-2, every pair of levels 3-5) tested on this state */
+                int rot = 0;
+                ++g_tries;
+                for (int M = 0; M < 6; ++M)
+                    for (int i = 0; i < 6; ++i) {
+                        const int j = PARTNER[M][i];
+                        if (j < i || (M < 3 && !is_tail(M, i, j))) continue;
+                        double p = 0;
+                        for (int k = 0; k < 6; k++) p += (double)At[i][k] * At[j][k];
+                        rot |= fast ? test_fast(p, W[i] * W[j]) : !(fabs(p) <= eps * sqrt(W[i] * W[j]));
+                    }
+                if (!rot) { ++g_hits; goto done; }
+            }
         }
         changed_tail = changed_head;           /* sweep s + 1 becomes the tail */
         changed_head = 0;
@@ -253,6 +275,7 @@ int main(int argc, char** argv)
     tfo_set_pose_algebra(4, 0);
     long long n = 0, bad[2] = { 0, 0 };
     float* sys = NULL;
+    if (argc > 1 && !strcmp(argv[1], "-oneshot")) { g_oneshot = 1; --argc; ++argv; }
     if (argc > 1) {
         FILE* f = fopen(argv[1], "rb");
         if (!f) { perror(argv[1]); return 2; }
@@ -263,12 +286,38 @@ int main(int argc, char** argv)
         if (fread(sys, 4, n * 27, f) != (size_t)(n * 27)) return 2;
         fclose(f);
     }
-    const long long nrand = 200000;
+    const long long nrand = 200000, ncon = 640;
     uint64_t st = 12345;
-    for (long long q = 0; q < n + nrand; ++q) {
+    for (long long q = 0; q < n + nrand + ncon; ++q) {
         float sm[27], A[36], b[6], x0[6], x1[6], x2[6];
         if (q < n) memcpy(sm, sys + 27 * q, sizeof(sm));
-        else {            /* random ICP-like systems: sums of outer products of 7-vectors */
+        else if (q >= n + nrand) {
+            /* constructed: diagonal A at four scales (the first 40), then exactly one coupled
+               pair A[i][j] = e sqrt(A[i][i] A[j][j]), e from 2^0 down to 2^-36 in steps of 2^-4
+               with a random mantissa, each of the 15 pairs at each scale */
+            static const float SC[4] = { 1.f, 1e-6f, 1e6f, 37.f };
+            const long long c = q - n - nrand;
+            const float scale = SC[c & 3];
+            float d[6];
+            memset(sm, 0, sizeof(sm));
+            for (int k = 0; k < 6; ++k) {
+                st = st * 6364136223846793005ull + 1442695040888963407ull;
+                d[k] = (0.5f + (float)(st >> 40) / 16777216.0f) * scale;
+            }
+            int s2 = 0, pr = 0;
+            for (int a = 0; a < 6; ++a)
+                for (int cc = a; cc < 7; ++cc, ++s2) {
+                    st = st * 6364136223846793005ull + 1442695040888963407ull;
+                    const float u = (float)(st >> 40) / 16777216.0f;
+                    if (cc == 6) sm[s2] = (u - 0.5f) * scale;
+                    else if (cc == a) sm[s2] = d[a];
+                    else {
+                        if (c >= 40 && pr == (int)((c - 40) / 4 % 15))
+                            sm[s2] = ldexpf(0.5f + 0.5f * u, -4 * (int)((c - 40) / 60)) * sqrtf(d[a] * d[cc]);
+                        ++pr;
+                    }
+                }
+        } else {            /* random ICP-like systems: sums of outer products of 7-vectors */
             memset(sm, 0, sizeof(sm));
             const int rows = 7 + (int)(q % 60);
             for (int r = 0; r < rows; ++r) {
@@ -288,7 +337,10 @@ int main(int argc, char** argv)
         if (memcmp(x0, x1, sizeof(x0))) { if (bad[0]++ < 5) printf("levels/exact differs on system %lld\n", q); }
         if (memcmp(x0, x2, sizeof(x0))) { if (bad[1]++ < 5) printf("levels/fast differs on system %lld\n", q); }
     }
-    printf("systems: %lld captured + %lld random; differing: levels-exact %lld, levels-fast %lld\n", n, nrand, bad[0], bad[1]);
+    printf("systems: %lld captured + %lld random + %lld constructed; differing: levels-exact %lld, levels-fast %lld\n", n, nrand,
+           ncon, bad[0], bad[1]);
+    printf("batched final-sweep test %s: tries per solve %.3f, hits per solve %.3f\n", g_oneshot ? "on" : "off",
+           (double)g_tries / (double)g_solves, (double)g_hits / (double)g_solves);
     printf("fast-path rotations %lld, fallbacks %lld (%.2e); exact rotation tests %lld; levels per solve %.2f\n", g_fast,
            g_fallback, (double)g_fallback / (double)(g_fast + g_fallback), g_test_exact, (double)g_levels / (double)g_solves);
     return bad[0] || bad[1];

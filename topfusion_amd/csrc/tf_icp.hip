@@ -936,8 +936,24 @@ k_icp_frame(IcpFrameArgs a)
                         } else
 #endif
                         if constexpr (ALG != 0 && IP_SVD_LANES) {       // projective_icp.cpp:206-209
+#ifdef TF_ICP_TIMING
+                            // solve end and the halves' cycles as on the ALG == 0 path, each half
+                            // run once (g_icp_tail_cyc's "again" columns stay 0)
+                            const long long c0 = IPT_CYC(0.f);
+                            icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, rv);
+                            const long long c1 = IPT_CYC(rv[0] + rv[5]);
+                            IPT_REC_DEP(done, 2 * ICP_NWG + 3, rv[0] + rv[5]);
+                            const long long c3 = IPT_CYC(0.f);
+                            icp_cv_rodrigues<ALG>(rv, R);
+                            const long long c4 = IPT_CYC(R[0] + R[8]);
+                            if (blockIdx.x == 0 && lane == 0 && done < 64) {
+                                g_icp_tail_cyc[4 * done + 0] = c1 - c0; g_icp_tail_cyc[4 * done + 1] = 0;
+                                g_icp_tail_cyc[4 * done + 2] = c4 - c3; g_icp_tail_cyc[4 * done + 3] = 0;
+                            }
+#else
                             icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, rv);
                             icp_cv_rodrigues<ALG>(rv, R);
+#endif
                         } else {
                             icp_solve_rodrigues<ALG>(Am, bv, rv, R);
                         }

@@ -548,6 +548,8 @@ __device__ __forceinline__ void icp_cv_svd_finish(float (&At)[6][6], float (&Vt)
 //    sweep that changed nothing is detected after its last rotation, (4, 5), exactly where the
 //    serial loop breaks -- the next sweep's rotations already issued then find the data they
 //    would have found and rotate nothing);
+//  * the last sweep, which only verifies convergence, does not go through its six levels: once
+//    its first pairs have rotated nothing, one batched test settles the rest (icp_sv_oneshot);
 //  * a rotation's sums (the dot product, the new |row|^2) keep the serial order: the six exact
 //    double products reach the row's lane 0 by DPP row_shl and are added there in order;
 //  * (c, s) come from a short sequence (v_rsq_f64 / v_rcp_f64 plus one refinement each,
@@ -782,7 +784,7 @@ __device__ __forceinline__ float icp_row_bcast(float v, int lane)
 #ifdef TF_SV_TIMING                               // (tools/micro/svd_lanes.hip timing build only)
 // a stamp after a value: its phase's cycles since the previous stamp accumulate in registers
 // (SvTimes), written to g_sv_t at the end of the solve
-struct SvTimes { long long t0, acc[8]; };
+struct SvTimes { long long t0, acc[9]; };
 #define SV_TPARAM , SvTimes& svt
 #define SV_TARG , svt
 #define SV_T(k, val_) do { const float d_ = (float)(val_); asm volatile("; sv dep %0" :: "v"(d_)); \
@@ -923,6 +925,63 @@ __device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int s
     ch_head = ch_head || (m & ~TL) != 0;
 }
 
+// The final sweep settled by one batched test (SV_ONESHOT).  The serial loop ends after the first
+// sweep that rotates nothing; in the level schedule that sweep costs six levels (3-5 of its head
+// period, 0-2 of the next), each a whole fetch -> gather -> sum -> test chain.  A sweep that
+// rotates nothing never changes At, so all 15 of its tests see one state.  After level 2 of a
+// period, when sweep s + 1's four head pairs (0,1) (0,2) (0,3) (1,2) have just tested clean (rows
+// 0 and 1 are not touched by sweep s's tail, row 2 last at level 0, row 3 last at level 1: they
+// were tested on the state below), the sweep's other pairs are tested here on that same state,
+// all at once, one pair per lane: lane 8 r + c, c < 5, takes row r against the c-th other row
+// (every pair from both sides, the four head pairs again: the test is pure).  Each lane holds its
+// whole row (DPP row_newbcast of the row's six lanes), fetches the partner row's six elements
+// (ds_bpermute, one address), and forms p and both |row|^2 as a level does: the same exact double
+// products added in the serial order (p by commuted products, the same doubles).  The decision is
+// icp_sv_test itself.  All skip: sweep s + 1 would run without a rotation and the serial loop
+// would break with this very At and Vt -- true.  Otherwise nothing has been modified and the
+// levels go on.  wo: |own row|^2 of that state (every lane of the row).
+#ifndef SV_ONESHOT
+#define SV_ONESHOT 1           // 0: every sweep through the levels (A/B)
+#endif
+// element K of the lane's row, on every lane of the row
+template <int K>
+__device__ __forceinline__ float icp_row_elem(float v, int lane)
+{
+    const float b0 = icp_dpp_f<0x150 + K>(v), b8 = icp_dpp_f<0x158 + K>(v);
+    return (lane & 8) ? b8 : b0;
+}
+__device__ __forceinline__ bool icp_sv_oneshot(float a, int lane, double& wo SV_TPARAM)
+{
+    SV_T(0, a);
+    // a lane of the partner row of this lane's pair: row r against the k-th other row, k < 5 (the
+    // other lanes fetch some row; nothing of theirs is used).  Formed here from an opaque copy of
+    // the lane index: as a loop invariant it would hold a VGPR across the whole kernel (k_icp_frame
+    // is at its 256)
+    int l = lane;
+    asm volatile("; sv oneshot %0" : "+v"(l));
+    const int psrc = 8 * ((l & 7) < (l >> 3) ? (l & 7) : (l & 7) + 1);
+    const float o0 = icp_row_elem<0>(a, lane), o1 = icp_row_elem<1>(a, lane), o2 = icp_row_elem<2>(a, lane);
+    const float o3 = icp_row_elem<3>(a, lane), o4 = icp_row_elem<4>(a, lane), o5 = icp_row_elem<5>(a, lane);
+    const float x0 = icp_bperm_f(psrc, o0), x1 = icp_bperm_f(psrc, o1), x2 = icp_bperm_f(psrc, o2);
+    const float x3 = icp_bperm_f(psrc, o3), x4 = icp_bperm_f(psrc, o4), x5 = icp_bperm_f(psrc, o5);
+    const double d0 = o0, d1 = o1, d2 = o2, d3 = o3, d4 = o4, d5 = o5;
+    wo = fma(d0, d0, 0.0);
+    wo = fma(d1, d1, wo); wo = fma(d2, d2, wo); wo = fma(d3, d3, wo); wo = fma(d4, d4, wo); wo = fma(d5, d5, wo);
+    const double e0 = x0, e1 = x1, e2 = x2, e3 = x3, e4 = x4, e5 = x5;
+    double wq = fma(e0, e0, 0.0), p = fma(d0, e0, 0.0);
+    wq = fma(e1, e1, wq); p = fma(d1, e1, p);
+    wq = fma(e2, e2, wq); p = fma(d2, e2, p);
+    wq = fma(e3, e3, wq); p = fma(d3, e3, p);
+    wq = fma(e4, e4, wq); p = fma(d4, e4, p);
+    wq = fma(e5, e5, wq); p = fma(d5, e5, p);
+    const unsigned long long m = icp_sv_test(0x00001f1f1f1f1f1full, p, wo * wq);   // rows 0..5, c = 0..4
+    SV_T(8, (float)m);
+#ifdef TF_SV_STATS                                // (tools/micro/svd_lanes.hip: batched tests, and those that ended the sweeps)
+    if (lane == 0) { atomicAdd(&g_sv_stats[3], 1ull); if (m == 0) atomicAdd(&g_sv_stats[4], 1ull); }
+#endif
+    return m == 0;
+}
+
 // tot: lane stride * q holds sum q of the system (StreamHelper layout, projective_icp.cpp:51-61);
 // x: the solution, uniform
 template <int ALG>
@@ -955,18 +1014,28 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
     icp_sv_level<0, false, true>(a, v, lane, src[0], ch_tail, ch_head SV_TARG);
     icp_sv_level<1, false, true>(a, v, lane, src[1], ch_tail, ch_head SV_TARG);
     icp_sv_level<2, false, true>(a, v, lane, src[2], ch_tail, ch_head SV_TARG);
-    icp_sv_level<3, false, true>(a, v, lane, src[3], ch_tail, ch_head SV_TARG);
-    icp_sv_level<4, false, true>(a, v, lane, src[4], ch_tail, ch_head SV_TARG);
-    icp_sv_level<5, false, true>(a, v, lane, src[5], ch_tail, ch_head SV_TARG);
+    bool done = false, shot = false;            // shot: the sweeps ended through the batched test
+    double wsq = 0;                             // then |row|^2 of the final state
+#if SV_ONESHOT
+    if (!ch_head && icp_sv_oneshot(a, lane, wsq SV_TARG)) done = shot = true;   // sweep 0 rotates nothing
+#endif
+    if (!done) {
+        icp_sv_level<3, false, true>(a, v, lane, src[3], ch_tail, ch_head SV_TARG);
+        icp_sv_level<4, false, true>(a, v, lane, src[4], ch_tail, ch_head SV_TARG);
+        icp_sv_level<5, false, true>(a, v, lane, src[5], ch_tail, ch_head SV_TARG);
+    }
     ch_tail = ch_head;
     ch_head = false;
-    bool done = false;
 #pragma unroll 1
-    for (int sw = 0; sw < 29; ++sw) {           // period sw: tail sweep sw, head sweep sw + 1
+    for (int sw = 0; sw < 29 && !done; ++sw) {  // period sw: tail sweep sw, head sweep sw + 1
         icp_sv_level<0, true, true>(a, v, lane, src[0], ch_tail, ch_head SV_TARG);
         icp_sv_level<1, true, true>(a, v, lane, src[1], ch_tail, ch_head SV_TARG);
         icp_sv_level<2, true, true>(a, v, lane, src[2], ch_tail, ch_head SV_TARG);
         if (!ch_tail) { done = true; break; }   // sweep sw changed nothing: the serial loop's exit
+#if SV_ONESHOT
+        // sweep sw + 1's head rotated nothing: its other pairs in one batched test (sw + 1 < 30)
+        if (!ch_head && icp_sv_oneshot(a, lane, wsq SV_TARG)) { done = shot = true; break; }
+#endif
         icp_sv_level<3, true, true>(a, v, lane, src[3], ch_tail, ch_head SV_TARG);
         icp_sv_level<4, true, true>(a, v, lane, src[4], ch_tail, ch_head SV_TARG);
         icp_sv_level<5, true, true>(a, v, lane, src[5], ch_tail, ch_head SV_TARG);
@@ -979,7 +1048,10 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
         icp_sv_level<2, true, false>(a, v, lane, src[2], ch_tail, ch_head SV_TARG);
     }
     // ---- singular values, sorted descending (selection sort, strict <: the first maximum)
-    const double Wf = sqrt(icp_sv_rowsum((double)a * (double)a, lane));
+    // |row|^2: the batched test that ended the sweeps formed it (the same products added in the
+    // same order, on every lane of the row)
+    const double w2 = shot ? wsq : icp_sv_rowsum((double)a * (double)a, lane);
+    const double Wf = sqrt(w2);
     if (__builtin_amdgcn_ballot_w64((r < 6) & (k == 0) & (Wf <= TF_FLT_MIN)) != 0) {
         // a zero singular value: the serial finish (random completion) on the gathered matrices
 #ifdef TF_SV_STATS
@@ -1032,7 +1104,11 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
                     }
             }
         }
-        const int sl = r < 6 ? 8 * (int)((perm >> (4 * r)) & 15u) + k : lane;
+        // (the shift from an opaque copy of the lane index: 4 r as a kernel-wide invariant for this
+        // rare path is a VGPR k_icp_frame does not have)
+        int lr = lane;
+        asm volatile("; sv tie %0" : "+v"(lr));
+        const int sl = r < 6 ? 8 * (int)((perm >> (4 * (lr >> 3))) & 15u) + k : lane;
         as = icp_bperm_f(sl, a);
         vs = icp_bperm_f(sl, v);
         sd = icp_bperm_d(sl, Wf);
@@ -1077,7 +1153,7 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
 #ifdef TF_SV_TIMING
     SV_T(7, x[0] + x[5]);
     if (lane == 0)
-        for (int q = 0; q < 8; ++q) g_sv_t[q] += svt.acc[q];
+        for (int q = 0; q < 9; ++q) g_sv_t[q] += svt.acc[q];
 #endif
 }
 
