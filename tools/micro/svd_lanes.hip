@@ -4,7 +4,8 @@
 // deficient, huge / tiny scales); then the latency of both forms on one wave, each solve
 // depending on the last.  Built three times (plain, -DTF_SV_STATS, -DTF_SV_TIMING) and once more
 // with -DSV_ONESHOT=0 (svd_lanes_oneshot0: every sweep through the levels) for the A/B of the
-// batched final-sweep test.
+// batched final-sweep test; `make svd_lanes_cs` builds an off-twin per switch of the (c, s) chain
+// and the level (SV_CS_W0, SV_CS_LATE, SV_CH_MASK, SV_BCAST2) and svd_lanes_cs0 with all four off.
 //   make -C tools/micro svd_lanes;  ./tools/micro/svd_lanes tests/golden/icp_systems_C2_opencv4.f32
 #include <hip/hip_runtime.h>
 #include <cstdio>

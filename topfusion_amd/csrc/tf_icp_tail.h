@@ -714,11 +714,28 @@ __device__ __forceinline__ void icp_sv_cs_exact(double p, double beta, float& c,
 // (v, u) by the sign of beta, gamma = hypot(p, beta).  Here h ~ 1 / (2 gamma) from v_rsq_f64 and
 // one Newton step, q = 1/2 + |beta| h ~ (gamma + |beta|) / (2 gamma), U ~ sqrt(q) from v_rsq_f64
 // and one Goldschmidt step (which also refines 1 / (2 U)), 1 / u from that by one Newton step
-// on the rounded u, V = p h / u.  v_rsq_f64 is within 2^-24.2 (relative; all inputs checked,
-// profiles/r06/f64_approx.txt), so U and V are within ~2^-47 of the exact sequence's doubles,
-// 2^10 below the margin icp_sv_round_safe demands: where both pass it, (c, s)
-// are the exact sequence's.  Rotating lanes that fail take icp_sv_cs_exact (uniform branch).
-__device__ __forceinline__ void icp_sv_cs(double p, double beta, unsigned long long m, float& c, float& s)
+// on the rounded u, V = p h / u.
+// V is formed as W0 + W0 t with W0 = (p h) z0 beside the rounding of u and t = 1 - u z0 -- the
+// Newton step z0 (1 + t) for 1 / u multiplied out, one dependent operation fewer (SV_CS_W0).
+// v_rsq_f64 is within 2^-24.2 (relative; sampled, 2^30 inputs over the exponents 2^-300..2^520,
+// tools/micro/f64_approx.hip, profiles/r08/f64_approx.txt), one Goldschmidt step leaves
+// 1.5 (2^-24.2)^2 = 2^-47.8 in U and in z0 and the Newton step as much in h, so U and V are within
+// 2^-47 of the exact sequence's doubles (sampled on 2^30 (X, beta) with a second rsq that starts
+// from a worse value than this one: U 2^-47.5, V 2^-47.2), 2^10 below the margin
+// icp_sv_round_safe demands: where both pass it, (c, s) are the exact sequence's.
+// The result is the mask of the rotating lanes that fail it; the level gives those
+// icp_sv_cs_exact's (icp_sv_cs_fix, a wave-uniform branch) -- beside the update, not ahead of it
+// (SV_CS_LATE).
+#ifndef SV_CS_W0
+#define SV_CS_W0 1             // 0: V = (p h) z with the Newton step's z formed first
+#endif
+#ifndef SV_CS_LATE
+#define SV_CS_LATE 1           // 0: the margin's ballot and branch before the broadcast and the update
+#endif
+#ifndef SV_CH_MASK
+#define SV_CH_MASK 1           // 0: "a tail / head pair rotated" as booleans formed in every level
+#endif
+__device__ __forceinline__ unsigned long long icp_sv_cs(double p, double beta, unsigned long long m, float& c, float& s)
 {
     const double X = fma(p, p, beta * beta);
     const double y = __builtin_amdgcn_rsq(X);
@@ -729,26 +746,45 @@ __device__ __forceinline__ void icp_sv_cs(double p, double beta, unsigned long l
     double U = q * y2;
     const double h2 = 0.5 * y2, r2 = fma(-U, h2, 0.5);
     U = fma(U, r2, U);
+#if SV_CS_W0
+    const double z0 = fma(y2, r2, y2);                         // 1 / U
+    const double W0 = (p * h) * z0;
+    const float u = (float)U;
+    const double ud = u;
+    const double V = fma(W0, fma(-ud, z0, 1.0), W0);           // p h / u
+#else
     const double z0 = 2.0 * fma(h2, r2, h2);                   // 1 / U
     const float u = (float)U;
     const double ud = u;
     const double z = fma(fma(-ud, z0, 1.0), z0, z0);           // 1 / u
     const double V = (p * h) * z;
+#endif
     const float v = (float)V;
     const bool neg = beta < 0;
     c = neg ? v : u;
     s = neg ? u : v;
-    const unsigned long long bad =
-        m & ~__builtin_amdgcn_ballot_w64((int)icp_sv_round_safe<false>(U) & (int)icp_sv_round_safe<true>(V));
-    if (__builtin_expect(bad != 0, 0)) {
-#ifdef TF_SV_STATS                                // (tools/micro/svd_lanes.hip: levels that fell back)
-        if ((threadIdx.x & 63) == 0) atomicAdd(&g_sv_stats[1], 1ull);
+#if SV_CS_LATE
+    // (icp_sv_round_safe<false>(U) and <true>(V), one ballot per compare: each v_cmp writes its
+    // wave mask and the masks meet in scalar code)
+    const unsigned ve = (unsigned)(__builtin_bit_cast(unsigned long long, V) >> 52) & 0x7ffu;
+    const unsigned long long bu = __builtin_amdgcn_ballot_w64(icp_sv_round_safe<false>(U));
+    const unsigned long long bv = __builtin_amdgcn_ballot_w64(icp_sv_round_safe<false>(V));
+    const unsigned long long be = __builtin_amdgcn_ballot_w64(ve - (1023u - 125u) <= 251u);
+    return m & ~(bu & bv & be);
+#else
+    return m & ~__builtin_amdgcn_ballot_w64((int)icp_sv_round_safe<false>(U) & (int)icp_sv_round_safe<true>(V));
 #endif
-        float ce, se;
-        icp_sv_cs_exact(p, beta, ce, se);
-        c = icp_lsel(bad, ce, c);
-        s = icp_lsel(bad, se, s);
-    }
+}
+// the lanes of bad: (c, s) by the exact sequence
+__device__ __forceinline__ void icp_sv_cs_fix(double p, double beta, unsigned long long bad, float& c, float& s)
+{
+#ifdef TF_SV_STATS                                // (tools/micro/svd_lanes.hip: levels that fell back)
+    if ((threadIdx.x & 63) == 0) atomicAdd(&g_sv_stats[1], 1ull);
+#endif
+    float ce, se;
+    icp_sv_cs_exact(p, beta, ce, se);
+    c = icp_lsel(bad, ce, c);
+    s = icp_lsel(bad, se, s);
 }
 
 // the serial form's rotation test, !(|p| <= eps sqrt(a b)) with eps = 2 FLT_EPSILON = 2^-22, without
@@ -775,10 +811,23 @@ __device__ __forceinline__ float icp_dpp_f(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 // lane 0 of the lane's 8-lane row group (DPP row_newbcast:0 / :8)
+#ifndef SV_BCAST2
+#define SV_BCAST2 1            // 0: both broadcasts everywhere and a select by the lane's half of the DPP row
+#endif
 __device__ __forceinline__ float icp_row_bcast(float v, int lane)
 {
+#if SV_BCAST2
+    // two moves, no select: bank_mask 0x3 writes lanes 0-7 of each DPP row, 0xc lanes 8-15, and a
+    // lane outside the mask keeps the first move's value (the two masks cover every lane, so the
+    // register the first move starts from needs no value)
+    int un;
+    asm("; sv bcast %0" : "=v"(un));
+    const int lo = __builtin_amdgcn_update_dpp(un, __builtin_bit_cast(int, v), 0x150, 0xf, 0x3, false);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(lo, __builtin_bit_cast(int, v), 0x158, 0xf, 0xc, false));
+#else
     const float b0 = icp_dpp_f<0x150>(v), b8 = icp_dpp_f<0x158>(v);
     return (lane & 8) ? b8 : b0;
+#endif
 }
 
 #ifdef TF_SV_TIMING                               // (tools/micro/svd_lanes.hip timing build only)
@@ -855,6 +904,13 @@ constexpr bool sv_xor_ok()
 }
 static_assert(sv_xor_ok(), "icp_sv_partner: masks must match SV_P");
 
+// "a pair of the period's tail / head sweep has rotated": the rotating lanes' bits OR-ed over
+// the levels and tested once where the sweeps' control needs it (SV_CH_MASK), or a boolean
+#if SV_CH_MASK
+typedef unsigned long long sv_ch_t;
+#else
+typedef bool sv_ch_t;
+#endif
 // one level of a period: every row with a partner in an enabled sweep rotates with it.  Lane 0
 // of each row group gathers its row and the partner row (DPP row_shl) and forms the three sums the
 // rotation needs in the serial order -- p = sum_k At[I][k] At[J][k] and both |row|^2, exact double
@@ -862,7 +918,7 @@ static_assert(sv_xor_ok(), "icp_sv_partner: masks must match SV_P");
 // lanes apply (c, s) to their element.  src: the lane holding this lane's element of the partner
 // row (own lane when the row is idle); which pairs are enabled is a template argument.
 template <int L, bool TAIL_ON, bool HEAD_ON>
-__device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int src, bool& ch_tail, bool& ch_head SV_TPARAM)
+__device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int src, sv_ch_t& ch_tail, sv_ch_t& ch_head SV_TPARAM)
 {
     constexpr unsigned long long ACT = sv_act_base(L, TAIL_ON, HEAD_ON);
     constexpr unsigned long long LOW = sv_lower_lanes(L);
@@ -905,24 +961,46 @@ __device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int s
     SV_T(3, (float)m);
     if (m != 0) {                                               // (uniform: otherwise nothing changes)
         float c, s;
-        icp_sv_cs(p * 2, beta, m, c, s);
+        const double p2 = p * 2;
+        const unsigned long long bad = icp_sv_cs(p2, beta, m, c, s);
+#if !SV_CS_LATE
+        if (__builtin_expect(bad != 0, 0)) icp_sv_cs_fix(p2, beta, bad, c, s);
+#endif
         SV_T(4, c + s);
-        const float cb = icp_row_bcast(c, lane), sb = icp_row_bcast(s, lane);
+        float cb = icp_row_bcast(c, lane), sb = icp_row_bcast(s, lane);
         // row I: c Ai + s Aj, Vi c + Vj s;  row J: -s Ai + c Aj, Vj c - Vi s (the same products and
         // one addition each: a + b == b + a and x - y == x + (-y) bit for bit)
-        const float sc = icp_lsel(LOW, sb, -sb);
-        const float na = cb * a + sc * xa;
-        const float nv = v * cb + xv * sc;
+        float sc = icp_lsel(LOW, sb, -sb);
+        float na = cb * a + sc * xa;
+        float nv = v * cb + xv * sc;
+#if SV_CS_LATE
+        // the margin's verdict arrives beside the update: only where a lane failed it (about 1
+        // rotation in 2000) are (c, s) formed again, exactly, and the update repeated -- the
+        // values committed below are the ones the check ahead of the update would have chosen
+        if (__builtin_expect(bad != 0, 0)) {
+            icp_sv_cs_fix(p2, beta, bad, c, s);
+            cb = icp_row_bcast(c, lane); sb = icp_row_bcast(s, lane);
+            sc = icp_lsel(LOW, sb, -sb);
+            na = cb * a + sc * xa;
+            nv = v * cb + xv * sc;
+        }
+#endif
         const unsigned long long mr = icp_sv_spread(m);
         a = icp_lsel(mr, na, a);
         v = icp_lsel(mr, nv, v);
         SV_T(5, a + v);
+#if SV_CH_MASK
+        if constexpr (TL != 0) ch_tail |= m & TL;
+        ch_head |= m & ~TL;
+#endif
     }
 #ifdef TF_SV_STATS                                // (tools/micro/svd_lanes.hip: rotations)
     if (lane == 0) atomicAdd(&g_sv_stats[0], (unsigned long long)__builtin_popcountll(m) / 2);
 #endif
+#if !SV_CH_MASK
     ch_tail = ch_tail || (m & TL) != 0;
     ch_head = ch_head || (m & ~TL) != 0;
+#endif
 }
 
 // The final sweep settled by one batched test (SV_ONESHOT).  The serial loop ends after the first
@@ -1005,7 +1083,7 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
         const int P = (int)((sv_pack(L) >> (4 * r)) & 15u);
         src[L] = P != 15 ? 8 * P + k : lane;
     }
-    bool ch_tail = false, ch_head = false;
+    sv_ch_t ch_tail = 0, ch_head = 0;
 #ifdef TF_SV_TIMING
     SvTimes svt = {};
     svt.t0 = (long long)__builtin_amdgcn_s_memtime();
@@ -1025,7 +1103,7 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
         icp_sv_level<5, false, true>(a, v, lane, src[5], ch_tail, ch_head SV_TARG);
     }
     ch_tail = ch_head;
-    ch_head = false;
+    ch_head = 0;
 #pragma unroll 1
     for (int sw = 0; sw < 29 && !done; ++sw) {  // period sw: tail sweep sw, head sweep sw + 1
         icp_sv_level<0, true, true>(a, v, lane, src[0], ch_tail, ch_head SV_TARG);
@@ -1040,7 +1118,7 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
         icp_sv_level<4, true, true>(a, v, lane, src[4], ch_tail, ch_head SV_TARG);
         icp_sv_level<5, true, true>(a, v, lane, src[5], ch_tail, ch_head SV_TARG);
         ch_tail = ch_head;
-        ch_head = false;
+        ch_head = 0;
     }
     if (!done) {                                // sweep 29, the last (max_iter = 30): its tail only
         icp_sv_level<0, true, false>(a, v, lane, src[0], ch_tail, ch_head SV_TARG);
