@@ -7,6 +7,7 @@
 //
 //   ./demo_headless [frames=100] [cols=640] [rows=480]
 //   ./demo_headless --pgm 'dir/%04d.pgm' [--ppm 'dir/%04d.ppm'] [max_frames]
+//   ... --mesh out.ply : the reconstructed surface after the last frame (TopFu::saveMesh)
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -25,11 +26,12 @@ using namespace tfusion;
 
 int main(int argc, char** argv)
 {
-    std::string pgm, ppm;
+    std::string pgm, ppm, mesh;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--pgm") && i + 1 < argc) pgm = argv[++i];
         else if (!std::strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
+        else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh = argv[++i];
         else pos.push_back(argv[i]);
     }
     int frames = pos.size() > 0 ? std::atoi(pos[0]) : (pgm.empty() ? 100 : 1 << 30);
@@ -89,6 +91,10 @@ int main(int argc, char** argv)
     const tf_stats st = topfu->stats();
     std::printf("frames %d ok %d resets %d visible %d  pose t = (%.4f %.4f %.4f)\n", n, n_ok, st.n_resets,
                 st.noVisibleEntries, pose.translation()[0], pose.translation()[1], pose.translation()[2]);
+    if (!mesh.empty()) {
+        topfu->saveMesh(mesh);
+        std::printf("mesh written to %s\n", mesh.c_str());
+    }
     long lit = 0;
     for (size_t k = 0; k < view_host.size(); k += 4) lit += view_host[k] > 0;
     std::printf("rendered pixels lit: %ld of %d\n", lit, cols * rows);

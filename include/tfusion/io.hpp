@@ -8,8 +8,11 @@
 //     widened to uint16;
 //   * P6 (PPM), maxval <= 255: RGB triplets -> B, G, R order (imread's 3-channel BGR Mat).
 // Header comments (#...) and any whitespace between header fields are accepted, as netpbm
-// allows.  Header-only, no dependencies beyond the C++ standard library.
+// allows.  Header-only; the readers need nothing beyond the C++ standard library, writePLY
+// (mesh output, an addition) goes through the C-ABI's tf_mesh_write_ply.
 #pragma once
+
+#include "../tfusion_hip.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -104,6 +107,15 @@ inline void writePGM16(const std::string& path, const uint16_t* px, int cols, in
     const bool ok = std::fwrite(raw.data(), 1, raw.size(), f) == raw.size();
     std::fclose(f);
     if (!ok) throw std::runtime_error("short write " + path);
+}
+
+// n triangles (float[n][9], three xyz vertices each -- TopFu::extractMesh's layout, downloaded) as a
+// binary little-endian PLY with vertices welded by exact bit equality (tf_mesh_write_ply; an
+// addition, the reference writes no mesh)
+inline void writePLY(const std::string& path, const float* triangles, long long n)
+{
+    const tf_status s = tf_mesh_write_ply(path.c_str(), triangles, n);
+    if (s != TF_OK) throw std::runtime_error("cannot write " + path + ": " + tf_status_string(s));
 }
 
 // A numbered frame sequence in place of the reference's capture source (OpenNISource::grab,

@@ -245,6 +245,23 @@ namespace tfusion
             check(tf_get_stats(ctx_, &s), "tf_get_stats");
             return s;
         }
+        // Mesh extraction (additions: the reference has no mesher; tf_mesh_extract / tf_mesh_save_ply).
+        // extractMesh: the scene's triangles as 9 floats each (three xyz vertices, right-hand normal
+        // towards free space) in `triangles`, resized to fit; returns their number.
+        long long extractMesh(cuda::DeviceArray<float>& triangles)
+        {
+            long long n = 0;
+            check(tf_mesh_extract(ctx_, nullptr, 0, &n), "tf_mesh_extract");
+            triangles.create((size_t)n * 9);
+            if (n > 0) {
+                long long m = 0;
+                check(tf_mesh_extract(ctx_, triangles.ptr(), n, &m), "tf_mesh_extract");
+            }
+            return n;
+        }
+        // the mesh as a binary PLY with welded vertices
+        void saveMesh(const std::string& path) { check(tf_mesh_save_ply(ctx_, path.c_str()), "tf_mesh_save_ply"); }
+
         tf_ctx* handle() { return ctx_; }
         hipStream_t stream() const { return (hipStream_t)tf_get_stream(ctx_); }
 

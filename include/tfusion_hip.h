@@ -431,6 +431,28 @@ tf_status tf_reset_totals(tf_ctx* ctx);
  * updated by every launch exactly as by tf_stage_integrate / tf_stage_raycast. */
 tf_status tf_time_stage(tf_ctx* ctx, int stage, const float pose_rt[12], int iters, float* ms_per_iter);
 
+/* ---- mesh extraction (additions: the reference has no mesher, nothing here replaces a reference
+ * interface) ------------------------------------------------------------------------------------
+ * Marching tetrahedra on the Kuhn split of every voxel cube of every allocated block (hash entries
+ * with ptr >= 0), specified to the bit in DESIGN.md (Mesh extraction): a cube is meshed when all
+ * eight corner voxels exist with w > 0, a corner is inside when its sdf short is < 0, vertices are
+ * world positions (voxel coordinate * voxelSize, as integration and raycast place them).  Blocks
+ * swapped out to the GlobalCache (ptr == -1) are not meshed and count as missing for their
+ * neighbours' cubes.  The scene is only read. */
+/* addition (no reference counterpart): triangles in a fixed order (ascending hash entry, voxel
+ * x + 8y + 64z, tetrahedron, triangle of the case) as float[n][9] -- three xyz vertices, right-hand
+ * normal towards sdf >= 0 -- into the device buffer: the first min(n, capacity) of them;
+ * *n_triangles = the full count n.  capacity 0 (dev_triangles may be NULL) only counts.  Two
+ * extractions of one scene are byte-identical.  Synchronous. */
+tf_status tf_mesh_extract(tf_ctx* ctx, float* dev_triangles, long long capacity, long long* n_triangles);
+/* addition (no reference counterpart): host only, no context -- n triangles (float[n][9]) as a binary
+ * little-endian PLY: vertices welded by exact bit equality of their three floats (in unspecified
+ * order), faces of three int indices in the input order */
+tf_status tf_mesh_write_ply(const char* path, const float* host_triangles, long long n);
+/* addition (no reference counterpart): count, extract into a temporary device buffer, download,
+ * tf_mesh_write_ply; TF_OOM when the buffers cannot be had */
+tf_status tf_mesh_save_ply(tf_ctx* ctx, const char* path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ def load():
         "tf_profile_sample": ([P, I], I),
         "tf_profile_reset": ([P], I),
         "tf_profile_read": ([P, P, P, I], I),
+        "tf_mesh_extract": ([P, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)], I),
+        "tf_mesh_write_ply": ([ctypes.c_char_p, P, ctypes.c_longlong], I),
+        "tf_mesh_save_ply": ([P, ctypes.c_char_p], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():
@@ -180,6 +183,29 @@ def load():
         fn.restype = res
     _lib = L
     return L
+
+
+_hip = None
+
+
+def hip_runtime():
+    """ctypes handle of the HIP runtime libtfusion_hip.so itself links (device buffers for calls that
+    take caller device memory; no second runtime in the process)."""
+    global _hip
+    if _hip is None:
+        load()
+        need = ""
+        with open("/proc/self/maps") as f:                 # the copy the library brought in
+            for line in f:
+                if "libamdhip64.so" in line:
+                    need = line.split()[-1]
+                    break
+        h = ctypes.CDLL(need or "libamdhip64.so")
+        h.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        h.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        h.hipFree.argtypes = [ctypes.c_void_p]
+        _hip = h
+    return _hip
 
 
 def status_string(s):

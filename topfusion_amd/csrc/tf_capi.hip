@@ -154,7 +154,8 @@ static void ctx_free(tf_ctx* c)
                      c->visCounts, c->visAgg, c->visibleIds, c->visType, c->range, c->range_render, c->raycast, c->grey,
                      c->blockRec, c->blockTiles, c->blockOff, c->edChunk, c->edSpill, c->edBins, c->edBinCnt, c->edDone, c->depth_in, c->dists, c->icp_partial, c->icp_ticket, c->icp_tagged, c->st,
                      c->swapState, c->swapFlags, c->swapStore, c->swapCounts,
-                     c->vba_rgb_guard, c->rgb_in, c->integ_cnt, c->fuse_pose, c->fuse_rec, c->fuse_dists, c->tile_cost, c->tile_order };
+                     c->vba_rgb_guard, c->rgb_in, c->integ_cnt, c->fuse_pose, c->fuse_rec, c->fuse_dists, c->tile_cost, c->tile_order,
+                     c->meshCount, c->meshBase };
     for (void* b : bufs) if (b) (void)hipFree(b);
     // pyramid maps: one allocation per map (level 0 is the base; swaps keep levels together)
     float4* maps[4] = { c->curr_pts[0], c->curr_nrm[0], c->prev_pts[0], c->prev_nrm[0] };
@@ -1616,4 +1617,96 @@ extern "C" tf_status tf_reset_totals(tf_ctx* c)
     TF_CHECK(hipStreamSynchronize(c->stream));
     c->icp_fallbacks = 0;
     return TF_OK;
+}
+
+// ---- mesh extraction (additions: the reference has no mesher; DESIGN.md §Mesh extraction) ------------
+// count + prefix on the stream, then the total
+static tf_status mesh_count(tf_ctx* c, long long* n)
+{
+    TF_CHECK(tfk_mesh_count(c));
+    TF_CHECK(hipMemcpyAsync(n, c->meshBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    return sync_checked(c);
+}
+
+extern "C" tf_status tf_mesh_extract(tf_ctx* c, float* dev_triangles, long long capacity, long long* n_triangles)
+{
+    TF_FLUSH(c);
+    if (!c || !n_triangles || capacity < 0 || (capacity > 0 && !dev_triangles)) return TF_INVALID_ARG;
+    long long n = 0;
+    tf_status s = mesh_count(c, &n);
+    if (s != TF_OK) return s;
+    *n_triangles = n;
+    if (capacity == 0 || !dev_triangles || n == 0) return TF_OK;
+    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffer on stream 0
+    TF_CHECK(tfk_mesh_emit(c, dev_triangles, capacity));
+    return sync_checked(c);
+}
+
+// binary little-endian PLY: vertices welded by the exact bits of their three floats (-0.0f and 0.0f
+// stay apart), faces of int indices in the input order
+extern "C" tf_status tf_mesh_write_ply(const char* path, const float* host_triangles, long long n)
+{
+    if (!path || n < 0 || (n > 0 && !host_triangles) || n > (long long)(0x7fffffff / 3)) return TF_INVALID_ARG;
+    struct Key { uint32_t v[3]; };
+    const size_t nv = (size_t)n * 3;
+    // open addressing over the vertex bits; slots hold vertex index + 1
+    size_t cap = 16;
+    while (cap < nv * 2) cap <<= 1;
+    std::vector<int> slot, face;
+    std::vector<Key> verts;
+    try { slot.assign(cap, 0); face.resize(nv); verts.reserve(nv / 4 + 16); } catch (const std::bad_alloc&) { return TF_OOM; }
+    try {
+        for (size_t i = 0; i < nv; ++i) {
+            Key k;
+            memcpy(k.v, host_triangles + 3 * i, sizeof(k.v));
+            size_t h = (k.v[0] * 73856093u) ^ (k.v[1] * 19349669u) ^ (k.v[2] * 83492791u);
+            h ^= h >> 15;
+            for (h &= cap - 1;; h = (h + 1) & (cap - 1)) {
+                if (!slot[h]) { verts.push_back(k); slot[h] = (int)verts.size(); break; }
+                if (!memcmp(verts[(size_t)slot[h] - 1].v, k.v, sizeof(k.v))) break;
+            }
+            face[i] = slot[h] - 1;
+        }
+    } catch (const std::bad_alloc&) { return TF_OOM; }
+    FILE* f = fopen(path, "wb");
+    if (!f) return TF_INVALID_ARG;
+    bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\nelement vertex %zu\n"
+                         "property float x\nproperty float y\nproperty float z\nelement face %lld\n"
+                         "property list uchar int vertex_indices\nend_header\n", verts.size(), n) > 0;
+    ok = ok && (verts.empty() || fwrite(verts.data(), sizeof(Key), verts.size(), f) == verts.size());
+    std::vector<unsigned char> rec;
+    try { rec.resize((size_t)n * 13); } catch (const std::bad_alloc&) { fclose(f); return TF_OOM; }
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        rec[13 * i] = 3;
+        memcpy(&rec[13 * i + 1], &face[3 * i], 12);
+    }
+    ok = ok && (rec.empty() || fwrite(rec.data(), 1, rec.size(), f) == rec.size());
+    ok = (fclose(f) == 0) && ok;
+    return ok ? TF_OK : TF_INVALID_ARG;
+}
+
+extern "C" tf_status tf_mesh_save_ply(tf_ctx* c, const char* path)
+{
+    TF_FLUSH(c);
+    if (!c || !path) return TF_INVALID_ARG;
+    long long n = 0;
+    tf_status s = mesh_count(c, &n);
+    if (s != TF_OK) return s;
+    float* dev = nullptr;
+    float* host = nullptr;
+    if (n > 0) {
+        const size_t bytes = sizeof(float) * 9 * (size_t)n;
+        host = (float*)malloc(bytes);
+        if (!host) return TF_OOM;
+        if (hipMalloc((void**)&dev, bytes) != hipSuccess) { (void)hipGetLastError(); free(host); return TF_OOM; }
+        hipError_t e = tfk_mesh_emit(c, dev, n);
+        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+        s = tf_from_hip(e);
+        const tf_status s2 = sync_checked(c);          // (the stream is idle before the buffer goes)
+        if (s == TF_OK) s = s2;
+        (void)hipFree(dev);
+    }
+    if (s == TF_OK) s = tf_mesh_write_ply(path, host, n);
+    free(host);
+    return s;
 }

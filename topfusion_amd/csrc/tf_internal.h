@@ -256,6 +256,28 @@ __host__ __device__ __forceinline__ size_t tf_grid_cell(int bx, int by, int bz)
            (size_t)(bx + TF_GRID_HALF);
 }
 
+// What a reader of the scene's voxels needs (the raycasting side, tf_render.hip; mesh extraction,
+// tf_mesh.hip).
+struct SceneView {
+    const TfHashEntry* hash;
+    const TfVoxel* vba;      // the guard block before the VBA (tf_ctx::vba_guard): voxel offsets are voff + TF_BLK3 + lin
+    const int2* grid;        // block grid (TF_GRID_*)
+    unsigned mask;
+    int n_buckets;
+};
+
+// the hash walk for a block outside the block grid (rare: the grid spans +-128 blocks)
+__device__ __forceinline__ int2 blk_walk(const SceneView& s, int bx, int by, int bz)
+{
+    int hi = tf_hash_index(bx, by, bz, s.mask);
+    while (true) {
+        const TfHashEntry e = s.hash[hi];
+        if (e.x == (short)bx && e.y == (short)by && e.z == (short)bz && e.ptr >= 0) return make_int2(hi, e.ptr * TF_BLK3);
+        if (e.offset < 1) return make_int2(-1, TF_VOFF_NONE);
+        hi = s.n_buckets + e.offset - 1;
+    }
+}
+
 // the cell of a block the hash now holds (allocation, reallocation after a swap-out)
 __device__ __forceinline__ void grid_set(int2* grid, const TfHashEntry& e, int idx)
 {
@@ -441,6 +463,10 @@ struct tf_ctx {
     float* fuse_pose;                    // [fuse_cap][12] world -> camera, row-major [R|t]
     int* fuse_rec;                       // [fuse_cap] tf_fuse_record
     int fuse_cap;
+    // mesh extraction (tf_mesh.hip): per hash entry its triangle count and exclusive base (+ the total);
+    // allocated by the first extraction
+    long long* meshCount;                // [n_total] counts, then one total per 512-entry group
+    long long* meshBase;                 // [n_total + 1]
 };
 #define TF_VERDICT_WORDS 16
 
@@ -540,5 +566,10 @@ hipError_t tfk_frame0_matrices(tf_ctx* c);
 // and IntegrateGlobalIntoLocal + SaveToGlobalMemory (after integration)
 hipError_t tfk_swap_realloc(tf_ctx* c);
 hipError_t tfk_swap(tf_ctx* c, int which = 3);   // 1 in, 2 out, 3 both
+
+// mesh extraction (tf_mesh.hip): count + prefix (the total lands in meshBase[n_total]), then the emit pass
+// of the first `capacity` triangles (9 floats each) in entry / voxel / tetrahedron order
+hipError_t tfk_mesh_count(tf_ctx* c);
+hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity);
 
 enum { TF_POSE_ALLOC = 1, TF_POSE_RAY = 2, TF_POSE_ALLOC_NOINV = 4 };

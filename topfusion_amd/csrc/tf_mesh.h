@@ -1,0 +1,166 @@
+// tf_mesh.h -- the per-cube part of mesh extraction (DESIGN.md §Mesh extraction): marching tetrahedra on
+// the Kuhn split of a voxel cube.  No reference counterpart (the reference has no mesher).  Plain
+// functions of eight corner voxels, shared by the count and the emit kernels of tf_mesh.hip; also
+// compilable as host C++ (the case rules can then be checked without a GPU).
+#pragma once
+
+#if defined(__HIPCC__)
+#define TFM_HD __host__ __device__ __forceinline__
+#define TFM_TABLE static __constant__ const
+#else
+#define TFM_HD inline
+#define TFM_TABLE static constexpr
+#endif
+
+// Tetrahedron k of the cube, axis permutation (a, b, c) in the order xyz xzy yxz yzx zxy zyx: corners
+// c0 = 0, c1 = e_a, c2 = e_a + e_b, c3 = (1,1,1), as cube corner ids (bit 0 x, bit 1 y, bit 2 z), 3 bits
+// each.  det[c1 - c0, c2 - c0, c3 - c0] = det[e_a, e_b, e_c]: the permutation's sign is the
+// tetrahedron's handedness.
+constexpr unsigned tfm_perm_a(int k) { return (unsigned)(k >> 1); }
+constexpr unsigned tfm_perm_b(int k) { return k == 0 ? 1u : k == 1 ? 2u : k == 2 ? 0u : k == 3 ? 2u : k == 4 ? 0u : 1u; }
+constexpr unsigned tfm_tet_corners(int k)
+{
+    return (0u) | ((1u << tfm_perm_a(k)) << 3) | (((1u << tfm_perm_a(k)) | (1u << tfm_perm_b(k))) << 6) | (7u << 9);
+}
+// odd permutations: xzy, yxz, zyx
+constexpr bool tfm_tet_negative(int k) { return k == 1 || k == 2 || k == 5; }
+
+// A case of a tetrahedron, from the inside set m (bit i: corner i has sdf < 0), by rule:
+//   bits 0-1  triangles (0, 1, 2)
+//   bit  2    swap each triangle's last two vertices in a POSITIVE tetrahedron (a negative one: the opposite)
+//   bits 4-19 the vertices v0..v3, 4 bits each: the edge's lower corner | upper corner << 2
+// One inside corner i: the edges (i, j), j ascending; the listed order's normal points away from i
+// iff (-1)^i det > 0 [(p1 - ci) . ((p2 - p1) x (p3 - p1)) = t1 t2 t3 det[cj1 - ci, cj2 - ci, cj3 - ci], and
+// moving ci to the front of (c0..c3) takes i transpositions].  One outside corner i: the same
+// vertices, the normal must point towards i.  Two and two (i < j inside, k < l outside): the quad
+// v_ik v_il v_jl v_jk; at the edge midpoints its normal is (cl - ck) x (cj - ci) / 4 and n . (outside
+// centroid - inside centroid) = det[cj - ci, ck - ci, cl - ci] / 4, so the listed order is right iff
+// the permutation (i, j, k, l) is even (times the handedness).
+constexpr unsigned tfm_edge(int u, int v) { return u < v ? (unsigned)(u | v << 2) : (unsigned)(v | u << 2); }
+constexpr int tfm_popc4(unsigned m) { return (int)((m & 1) + (m >> 1 & 1) + (m >> 2 & 1) + (m >> 3 & 1)); }
+constexpr int tfm_nth_set(unsigned m, int n)    // index of the n-th set bit of m (n from 0)
+{
+    return (m & 1) ? (n == 0 ? 0 : 1 + tfm_nth_set(m >> 1, n - 1)) : 1 + tfm_nth_set(m >> 1, n);
+}
+constexpr int tfm_inversions(int a, int b, int c, int d)
+{
+    return (a > b) + (a > c) + (a > d) + (b > c) + (b > d) + (c > d);
+}
+constexpr unsigned tfm_case(unsigned m)
+{
+    const int n = tfm_popc4(m);
+    if (n == 0 || n == 4) return 0u;
+    if (n == 1 || n == 3) {
+        const unsigned one = n == 1 ? m : (~m & 15u), rest = ~one & 15u;
+        const int i = tfm_nth_set(one, 0);
+        const unsigned v = tfm_edge(i, tfm_nth_set(rest, 0)) | tfm_edge(i, tfm_nth_set(rest, 1)) << 4 |
+                           tfm_edge(i, tfm_nth_set(rest, 2)) << 8;
+        const bool ok_pos = n == 1 ? (i % 2 == 0) : (i % 2 == 1);
+        return 1u | (ok_pos ? 0u : 4u) | v << 4;
+    }
+    const unsigned out = ~m & 15u;
+    const int i = tfm_nth_set(m, 0), j = tfm_nth_set(m, 1), k = tfm_nth_set(out, 0), l = tfm_nth_set(out, 1);
+    const unsigned v = tfm_edge(i, k) | tfm_edge(i, l) << 4 | tfm_edge(j, l) << 8 | tfm_edge(j, k) << 12;
+    return 2u | (tfm_inversions(i, j, k, l) % 2 == 0 ? 0u : 4u) | v << 4;
+}
+TFM_TABLE unsigned tfm_cases[16] = { tfm_case(0), tfm_case(1), tfm_case(2), tfm_case(3), tfm_case(4), tfm_case(5),
+                                     tfm_case(6), tfm_case(7), tfm_case(8), tfm_case(9), tfm_case(10), tfm_case(11),
+                                     tfm_case(12), tfm_case(13), tfm_case(14), tfm_case(15) };
+
+// triangles of a 4-bit case: 0 for none / all inside, 2 for two and two, else 1
+TFM_HD int tfm_case_tris(unsigned m)
+{
+    // 2 bits per case, from the rule: |S| = 1, 3 -> 1; |S| = 2 -> 2
+    constexpr unsigned long long packed =
+        (unsigned long long)(tfm_case(0) & 3) | (unsigned long long)(tfm_case(1) & 3) << 2 | (unsigned long long)(tfm_case(2) & 3) << 4 |
+        (unsigned long long)(tfm_case(3) & 3) << 6 | (unsigned long long)(tfm_case(4) & 3) << 8 | (unsigned long long)(tfm_case(5) & 3) << 10 |
+        (unsigned long long)(tfm_case(6) & 3) << 12 | (unsigned long long)(tfm_case(7) & 3) << 14 | (unsigned long long)(tfm_case(8) & 3) << 16 |
+        (unsigned long long)(tfm_case(9) & 3) << 18 | (unsigned long long)(tfm_case(10) & 3) << 20 | (unsigned long long)(tfm_case(11) & 3) << 22 |
+        (unsigned long long)(tfm_case(12) & 3) << 24 | (unsigned long long)(tfm_case(13) & 3) << 26 | (unsigned long long)(tfm_case(14) & 3) << 28 |
+        (unsigned long long)(tfm_case(15) & 3) << 30;
+    return (int)(packed >> (2 * m) & 3);
+}
+
+// The cube's eight corner voxels, corner id = dx | dy << 1 | dz << 2: sdf shorts and "all eight exist
+// with w > 0".
+struct TfmCube {
+    int sdf[8];
+    bool valid;
+};
+
+// the case of tetrahedron K from the cube's 8-bit inside mask (bit = corner id)
+template <int K>
+TFM_HD unsigned tfm_tet_case(unsigned inside8)
+{
+    constexpr unsigned c = tfm_tet_corners(K);
+    return (inside8 >> (c & 7) & 1) | (inside8 >> (c >> 3 & 7) & 1) << 1 | (inside8 >> (c >> 6 & 7) & 1) << 2 |
+           (inside8 >> (c >> 9 & 7) & 1) << 3;
+}
+TFM_HD unsigned tfm_inside_mask(const TfmCube& q)
+{
+    unsigned m = 0;
+    for (int i = 0; i < 8; ++i) m |= (q.sdf[i] < 0 ? 1u : 0u) << i;
+    return m;
+}
+// triangles of the cube
+TFM_HD int tfm_cube_count(const TfmCube& q)
+{
+    if (!q.valid) return 0;
+    const unsigned m = tfm_inside_mask(q);
+    return tfm_case_tris(tfm_tet_case<0>(m)) + tfm_case_tris(tfm_tet_case<1>(m)) + tfm_case_tris(tfm_tet_case<2>(m)) +
+           tfm_case_tris(tfm_tet_case<3>(m)) + tfm_case_tris(tfm_tet_case<4>(m)) + tfm_case_tris(tfm_tet_case<5>(m));
+}
+
+// The vertex on the edge from the cube corner `lo` (sdf sp, global voxel gx, gy, gz of the cube's
+// corner 0) to `hi` (sdf sq): t = RN(sp / (sp - sq)) (the difference in int, exact in float), then per
+// axis RN(RN(g + t) * voxelSize) where the edge moves, RN(g * voxelSize) where it does not.  Both
+// cubes (and all tetrahedra) that share the edge compute the same three floats.
+TFM_HD void tfm_vertex(unsigned lo, unsigned hi, int sp, int sq, int gx, int gy, int gz, float vs, float* out)
+{
+    const float t = (float)sp / (float)(sp - sq);
+    const unsigned d = hi & ~lo;
+    const float px = (float)(gx + (int)(lo & 1)), py = (float)(gy + (int)(lo >> 1 & 1)), pz = (float)(gz + (int)(lo >> 2 & 1));
+    const float ax = px + t, ay = py + t, az = pz + t;
+    out[0] = ((d & 1) ? ax : px) * vs;
+    out[1] = ((d & 2) ? ay : py) * vs;
+    out[2] = ((d & 4) ? az : pz) * vs;
+}
+
+// Tetrahedron K's triangles of the cube through emit(const float tri[9]), in case order; returns
+// their number.  The cube must be valid.
+template <int K, class Emit>
+TFM_HD int tfm_tet_emit(const TfmCube& q, unsigned inside8, int gx, int gy, int gz, float vs, Emit& emit)
+{
+    constexpr unsigned corners = tfm_tet_corners(K);
+    const unsigned info = tfm_cases[tfm_tet_case<K>(inside8)];
+    const int n = (int)(info & 3);
+    const bool flip = ((info >> 2 & 1) != 0) != tfm_tet_negative(K);
+    for (int tr = 0; tr < n; ++tr) {
+        float tri[9];
+        for (int v = 0; v < 3; ++v) {
+            // triangle 0: v0 v1 v2, triangle 1: v0 v2 v3; flipped: the last two swapped
+            const int w = v == 0 ? 0 : (flip ? 3 - v : v) + tr;
+            const unsigned e = info >> (4 + 4 * w) & 15u;
+            const unsigned lo = corners >> (3 * (e & 3)) & 7u, hi = corners >> (3 * (e >> 2)) & 7u;
+            int sp = q.sdf[0], sq = q.sdf[0];
+            for (int i = 1; i < 8; ++i) { sp = lo == (unsigned)i ? q.sdf[i] : sp; sq = hi == (unsigned)i ? q.sdf[i] : sq; }
+            tfm_vertex(lo, hi, sp, sq, gx, gy, gz, vs, tri + 3 * v);
+        }
+        emit(tri);
+    }
+    return n;
+}
+
+template <class Emit>
+TFM_HD int tfm_cube_emit(const TfmCube& q, int gx, int gy, int gz, float vs, Emit& emit)
+{
+    if (!q.valid) return 0;
+    const unsigned m = tfm_inside_mask(q);
+    int n = tfm_tet_emit<0>(q, m, gx, gy, gz, vs, emit);
+    n += tfm_tet_emit<1>(q, m, gx, gy, gz, vs, emit);
+    n += tfm_tet_emit<2>(q, m, gx, gy, gz, vs, emit);
+    n += tfm_tet_emit<3>(q, m, gx, gy, gz, vs, emit);
+    n += tfm_tet_emit<4>(q, m, gx, gy, gz, vs, emit);
+    n += tfm_tet_emit<5>(q, m, gx, gy, gz, vs, emit);
+    return n;
+}

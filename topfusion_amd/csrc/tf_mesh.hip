@@ -1,0 +1,265 @@
+// tf_mesh.hip -- mesh extraction from the voxel block hash for gfx950 (an addition: the reference has no
+// mesher).  Marching tetrahedra on the Kuhn split of every voxel cube (tf_mesh.h, DESIGN.md §Mesh
+// extraction), as three plain launches on the context stream:
+//
+//   k_mesh_count  : per live hash entry (ptr >= 0) the 9 x 9 x 9 corner voxels of its 512 cubes staged in
+//                   LDS (own block + up to seven neighbours, found through the block grid, outside it by
+//                   the hash walk), every cube classified, the entry's triangle count (64-bit) written;
+//                   dead entries get 0; each 512-entry group's total written beside
+//   k_mesh_prefix : exclusive scan of the counts in entry order -> every entry's base, and the total
+//   k_mesh_emit   : the classification again, an exclusive scan over the 512 voxels inside the
+//                   workgroup, triangles written at base + offset while below the caller's capacity
+//
+// No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) is only read.
+#include "tf_internal.h"
+#include "tf_mesh.h"
+
+#define TFM_WG 512               // threads per workgroup = voxels per block = entries per group
+#define TFM_TILE 9
+#define TFM_TILE3 (TFM_TILE * TFM_TILE * TFM_TILE)
+#define TFM_GRID 2048            // workgroups of the count / emit passes (groups are taken round robin)
+#define TFM_SCAN_GROUPS 4        // groups (of TFM_WG entries) per k_mesh_prefix workgroup
+
+struct MeshScene {
+    SceneView v;                 // v.vba: the guard block of Voxel_s() (sdf 32767, w 0), then the VBA -- a missing block reads it
+    int n_total;
+};
+
+// (hash entry, VBA voxel offset) of a neighbour block; a block coordinate outside the short range,
+// a block the hash does not hold, and a swapped-out entry (ptr -1) are all missing
+__device__ __forceinline__ int mesh_block_voff(const MeshScene& s, int bx, int by, int bz)
+{
+    if (tf_grid_in(bx, by, bz)) return s.v.grid[tf_grid_cell(bx, by, bz)].y;
+    if (bx > 32767 || by > 32767 || bz > 32767) return TF_VOFF_NONE;
+    return blk_walk(s.v, bx, by, bz).y;
+}
+
+// The entry's 729 corner voxels into LDS (sdf | w << 16 per voxel, index x + 9 y + 81 z).  All
+// threads of the workgroup call it; e is uniform.
+__device__ __forceinline__ void mesh_stage(const MeshScene& s, const TfHashEntry& e, unsigned* tile, int* nvoff)
+{
+    const int t = threadIdx.x;
+    __syncthreads();             // the previous entry's reads of tile / nvoff are done
+    if (t < 8) {
+        const int dx = t & 1, dy = t >> 1 & 1, dz = t >> 2;
+        nvoff[t] = t == 0 ? e.ptr * TF_BLK3 : mesh_block_voff(s, e.x + dx, e.y + dy, e.z + dz);
+    }
+    __syncthreads();
+    for (int i = t; i < TFM_TILE3; i += TFM_WG) {
+        const int z = i / (TFM_TILE * TFM_TILE), r = i - z * (TFM_TILE * TFM_TILE), y = r / TFM_TILE, x = r - y * TFM_TILE;
+        const int voff = nvoff[(x >> 3) | (y >> 3) << 1 | (z >> 3) << 2];
+        const TfVoxel v = s.v.vba[TF_BLK3 + voff + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6)];
+        tile[i] = (unsigned)(unsigned short)v.sdf | (unsigned)v.w << 16;
+    }
+    __syncthreads();
+}
+
+// this thread's cube: voxel threadIdx.x = x + 8 y + 64 z
+__device__ __forceinline__ TfmCube mesh_cube(const unsigned* tile)
+{
+    const int t = threadIdx.x, x = t & 7, y = t >> 3 & 7, z = t >> 6;
+    const int b = x + TFM_TILE * y + TFM_TILE * TFM_TILE * z;
+    TfmCube q;
+    unsigned wmin = 255u;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const unsigned v = tile[b + (c & 1) + TFM_TILE * (c >> 1 & 1) + TFM_TILE * TFM_TILE * (c >> 2)];
+        q.sdf[c] = (int)(short)(v & 0xffffu);
+        wmin = min(wmin, v >> 16);
+    }
+    q.valid = wmin > 0;
+    return q;
+}
+
+__device__ __forceinline__ int wave_sum(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(TFM_WG) void k_mesh_count(MeshScene s, long long* __restrict__ count, long long* __restrict__ groupTot)
+{
+    __shared__ unsigned tile[TFM_TILE3];
+    __shared__ int nvoff[8];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ int wsum[TFM_WG / 64];
+    const int t = threadIdx.x;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        __syncthreads();
+        if (t == 0) nlive = 0;
+        __syncthreads();
+        const int idx = g * TFM_WG + t;
+        if (idx < s.n_total) {
+            if (s.v.hash[idx].ptr >= 0) live[atomicAdd(&nlive, 1)] = idx;      // (any order: each entry's count stands alone)
+            else count[idx] = 0;
+        }
+        __syncthreads();
+        const int n = nlive;
+        long long tot = 0;
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            const TfHashEntry e = s.v.hash[ei];
+            mesh_stage(s, e, tile, nvoff);
+            const int c = wave_sum(tfm_cube_count(mesh_cube(tile)));
+            if ((t & 63) == 0) wsum[t >> 6] = c;
+            __syncthreads();
+            if (t == 0) {
+                int sum = 0;
+                for (int w = 0; w < TFM_WG / 64; ++w) sum += wsum[w];
+                count[ei] = sum;
+                tot += sum;
+            }
+        }
+        if (t == 0) groupTot[g] = tot;
+    }
+}
+
+// Exclusive scan of count[0 .. n_total) into base, base[n_total] = the total.  Workgroup w owns
+// TFM_SCAN_GROUPS groups: its start is the sum of the lower groups' totals (read, not waited for: they
+// were written by the launch before), then a scan of its own TFM_SCAN_GROUPS * TFM_WG counts.
+__global__ __launch_bounds__(256) void k_mesh_prefix(const long long* __restrict__ count, const long long* __restrict__ groupTot,
+                                                     long long* __restrict__ base, int n_total)
+{
+    __shared__ long long red[256];
+    __shared__ long long carry;
+    const int t = threadIdx.x;
+    const int ngroups = (n_total + TFM_WG - 1) / TFM_WG;
+    const int g0 = blockIdx.x * TFM_SCAN_GROUPS;
+    long long s = 0;
+    for (int g = t; g < g0 && g < ngroups; g += 256) s += groupTot[g];
+    red[t] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) carry = red[0];
+    __syncthreads();
+    const int first = g0 * TFM_WG, last = min(first + TFM_SCAN_GROUPS * TFM_WG, n_total);
+    for (int i0 = first; i0 < last; i0 += 256) {
+        const int i = i0 + t;
+        const long long v = i < last ? count[i] : 0;
+        __syncthreads();
+        red[t] = v;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {                 // Hillis-Steele inclusive scan
+            const long long a = t >= o ? red[t - o] : 0;
+            __syncthreads();
+            red[t] += a;
+            __syncthreads();
+        }
+        const long long c = carry;
+        if (i < last) base[i] = c + red[t] - v;
+        __syncthreads();
+        if (t == 255) carry = c + red[255];
+        __syncthreads();
+    }
+    if (last == n_total && t == 0) base[n_total] = carry;
+}
+
+// 4-byte aligned 16-byte store: a triangle is 36 bytes, so its address is only dword aligned
+typedef float tfm_f4 __attribute__((ext_vector_type(4), aligned(4)));
+
+struct MeshWriter {
+    float* out;
+    long long idx;           // the next triangle's index
+    long long capacity;
+    __device__ __forceinline__ void operator()(const float* tri)
+    {
+        if (idx < capacity) {
+            float* p = out + idx * 9;
+            tfm_f4 a, b;
+            a.x = tri[0]; a.y = tri[1]; a.z = tri[2]; a.w = tri[3];
+            b.x = tri[4]; b.y = tri[5]; b.z = tri[6]; b.w = tri[7];
+            *reinterpret_cast<tfm_f4*>(p) = a;
+            *reinterpret_cast<tfm_f4*>(p + 4) = b;
+            p[8] = tri[8];
+        }
+        ++idx;
+    }
+};
+
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit(MeshScene s, const long long* __restrict__ count, const long long* __restrict__ base,
+                                                      float* __restrict__ out, long long capacity, float voxelSize)
+{
+    __shared__ unsigned tile[TFM_TILE3];
+    __shared__ int nvoff[8];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ int wsum[TFM_WG / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        __syncthreads();
+        if (t == 0) nlive = 0;
+        __syncthreads();
+        const int idx = g * TFM_WG + t;
+        // entries with triangles below the capacity (count and base are uniform per entry)
+        if (idx < s.n_total && count[idx] > 0 && base[idx] < capacity) live[atomicAdd(&nlive, 1)] = idx;
+        __syncthreads();
+        const int n = nlive;
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            const TfHashEntry e = s.v.hash[ei];
+            mesh_stage(s, e, tile, nvoff);
+            const TfmCube q = mesh_cube(tile);
+            const int mine = tfm_cube_count(q);
+            // exclusive scan over the 512 voxels: inclusive within the wave, then the lower waves' sums
+            int inc = mine;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            if (lane == 63) wsum[wave] = inc;
+            __syncthreads();
+            int off = inc - mine;
+            for (int w = 0; w < wave; ++w) off += wsum[w];
+            if (mine) {
+                MeshWriter wr = { out, base[ei] + off, capacity };
+                tfm_cube_emit(q, e.x * TF_BLK + (t & 7), e.y * TF_BLK + (t >> 3 & 7), e.z * TF_BLK + (t >> 6), voxelSize, wr);
+            }
+        }
+    }
+}
+
+static MeshScene mesh_scene(const tf_ctx* c)
+{
+    MeshScene s;
+    s.v.hash = c->hash; s.v.vba = c->vba_guard; s.v.grid = c->bgrid;
+    s.v.mask = (unsigned)c->p.n_buckets - 1u; s.v.n_buckets = c->p.n_buckets; s.n_total = c->n_total;
+    return s;
+}
+
+static int mesh_groups(const tf_ctx* c) { return (c->n_total + TFM_WG - 1) / TFM_WG; }
+
+// count + prefix; the scratch (counts, bases + total, group totals behind the counts) is the
+// context's from the first call on
+hipError_t tfk_mesh_count(tf_ctx* c)
+{
+    const int ng = mesh_groups(c);
+    if (!c->meshCount) {
+        hipError_t e = hipMalloc((void**)&c->meshCount, sizeof(long long) * ((size_t)c->n_total + (size_t)ng));
+        if (e != hipSuccess) { c->meshCount = nullptr; return e; }
+        e = hipMalloc((void**)&c->meshBase, sizeof(long long) * ((size_t)c->n_total + 1));
+        if (e != hipSuccess) { (void)hipFree(c->meshCount); c->meshCount = nullptr; c->meshBase = nullptr; return e; }
+    }
+    long long* groupTot = c->meshCount + c->n_total;
+    hipLaunchKernelGGL(k_mesh_count, dim3(ng < TFM_GRID ? ng : TFM_GRID), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount,
+                       groupTot);
+    hipLaunchKernelGGL(k_mesh_prefix, dim3((ng + TFM_SCAN_GROUPS - 1) / TFM_SCAN_GROUPS), dim3(256), 0, c->stream, c->meshCount,
+                       groupTot, c->meshBase, c->n_total);
+    return hipGetLastError();
+}
+
+// after tfk_mesh_count on the same stream
+hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
+{
+    const int ng = mesh_groups(c);
+    hipLaunchKernelGGL(k_mesh_emit, dim3(ng < TFM_GRID ? ng : TFM_GRID), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount,
+                       c->meshBase, triangles, capacity, c->p.voxelSize);
+    return hipGetLastError();
+}

@@ -13,13 +13,7 @@
 #include "tf_preproc.h"
 #include "tf_reset.h"
 
-struct SceneView {
-    const TfHashEntry* hash;
-    const TfVoxel* vba;      // the guard block before the VBA (tf_ctx::vba_guard): voxel offsets are voff + TF_BLK3 + lin
-    const int2* grid;        // block grid (tf_internal.h, TF_GRID_*)
-    unsigned mask;
-    int n_buckets;
-};
+// SceneView, blk_walk (the hash walk for a block outside the block grid): tf_internal.h, shared with tf_mesh.hip
 
 // VoxelBlockHash::IndexCache (VoxelBlockHash.hpp:58-62): the cached block position decides castRay's
 // visibility marks; the cached pointer is never needed (voxels are read through the grid)
@@ -45,18 +39,6 @@ template <typename T>
 __device__ __forceinline__ T ld_off(const void* base, unsigned byte_off)
 {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-
-// the hash walk for a block outside the block grid (rare: the grid spans +-128 blocks)
-__device__ __forceinline__ int2 blk_walk(const SceneView& s, int bx, int by, int bz)
-{
-    int hi = tf_hash_index(bx, by, bz, s.mask);
-    while (true) {
-        const TfHashEntry e = s.hash[hi];
-        if (e.x == (short)bx && e.y == (short)by && e.z == (short)bz && e.ptr >= 0) return make_int2(hi, e.ptr * TF_BLK3);
-        if (e.offset < 1) return make_int2(-1, TF_VOFF_NONE);
-        hi = s.n_buckets + e.offset - 1;
-    }
 }
 
 // Cell byte offsets of the 2x2x2 block set {X[i]} x {Y[j]} x {Z[k]} (corner c = i + 2j + 4k;

@@ -2,7 +2,9 @@
 
 Same pixels as OpenCV's imread(path, CV_16U) / imread(path) for binary netpbm files: P5 with
 maxval > 255 holds big-endian 16-bit samples; P6 holds RGB, returned as BGR like imread.
-The C++ side is include/tfusion/io.hpp (readPGM16 / readPPM / FrameSequenceSource)."""
+The C++ side is include/tfusion/io.hpp (readPGM16 / readPPM / FrameSequenceSource).
+
+Mesh output (an addition): write_ply / read_ply, the binary PLY of tf_mesh_write_ply."""
 import numpy as np
 
 
@@ -67,3 +69,37 @@ def read_sequence(depth_pattern, first=0, count=None):
         out.append(read_pgm16(depth_pattern % i))
         i += 1
     return np.stack(out) if out else np.zeros((0, 0, 0), np.uint16)
+
+
+def write_ply(path, tris):
+    """Triangles (n, 3, 3) float32 as a binary little-endian PLY, vertices welded by exact bit
+    equality (tf_mesh_write_ply, the writer TopFu.save_mesh uses)."""
+    import ctypes
+    from . import _lib as L
+    t = np.ascontiguousarray(tris, np.float32).reshape(-1, 3, 3)
+    L.check(L.load().tf_mesh_write_ply(str(path).encode(), t.ctypes.data_as(ctypes.c_void_p), len(t)), "tf_mesh_write_ply")
+
+
+def read_ply(path):
+    """(vertices (m, 3) float32, faces (n, 3) int32) of a PLY exactly as write_ply writes it."""
+    buf = open(path, "rb").read()
+    end = buf.find(b"end_header\n")
+    if not buf.startswith(b"ply\nformat binary_little_endian 1.0\n") or end < 0:
+        raise ValueError("not a binary little-endian PLY")
+    nv = nf = None
+    for line in buf[:end].split(b"\n"):
+        f = line.split()
+        if f[:2] == [b"element", b"vertex"]:
+            nv = int(f[2])
+        elif f[:2] == [b"element", b"face"]:
+            nf = int(f[2])
+    if nv is None or nf is None:
+        raise ValueError("PLY header without vertex / face elements")
+    off = end + len(b"end_header\n")
+    if len(buf) != off + 12 * nv + 13 * nf:
+        raise ValueError("PLY body size does not match its header")
+    verts = np.frombuffer(buf, "<f4", 3 * nv, off).reshape(nv, 3).copy()
+    rec = np.frombuffer(buf, np.dtype([("n", "u1"), ("v", "<i4", 3)]), nf, off + 12 * nv)
+    if nf and not (rec["n"] == 3).all():
+        raise ValueError("PLY face that is not a triangle")
+    return verts, rec["v"].astype(np.int32)

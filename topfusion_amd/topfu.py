@@ -323,6 +323,39 @@ class TopFu:
     def swap_load(self, path):
         L.check(L.load().tf_swap_load(self._h, str(path).encode()), "tf_swap_load")
 
+    # -- mesh extraction (additions: tf_mesh_*; the reference has no mesher) ------------------------
+    def mesh_count(self):
+        """Triangles the scene's mesh has (the count pass alone)."""
+        n = ctypes.c_longlong()
+        L.check(L.load().tf_mesh_extract(self._h, None, 0, ctypes.byref(n)), "tf_mesh_extract")
+        return n.value
+
+    def mesh(self):
+        """The scene's surface as (n, 3, 3) float32 triangles -- marching tetrahedra over the voxel
+        block hash, in the fixed order of tf_mesh_extract, right-hand normals towards free space.
+        Counts, allocates a device buffer through the library's HIP runtime, extracts, downloads."""
+        n = self.mesh_count()
+        out = np.empty((n, 3, 3), np.float32)
+        if n == 0:
+            return out
+        hip = L.hip_runtime()
+        dev = ctypes.c_void_p()
+        if hip.hipMalloc(ctypes.byref(dev), ctypes.c_size_t(out.nbytes)) != 0:
+            raise L.TfError(L.TF_OOM, "hipMalloc (mesh)")
+        try:
+            m = ctypes.c_longlong()
+            L.check(L.load().tf_mesh_extract(self._h, dev, n, ctypes.byref(m)), "tf_mesh_extract")
+            assert m.value == n, (m.value, n)
+            if hip.hipMemcpy(_ptr(out), dev, ctypes.c_size_t(out.nbytes), 2) != 0:      # hipMemcpyDeviceToHost
+                raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (mesh)")
+        finally:
+            hip.hipFree(dev)
+        return out
+
+    def save_mesh(self, path):
+        """The mesh as a binary PLY with welded vertices (tf_mesh_save_ply)."""
+        L.check(L.load().tf_mesh_save_ply(self._h, str(path).encode()), "tf_mesh_save_ply")
+
     # typed views
     def hash(self):
         return self.download(L.TF_BUF_HASH).view(HASH_DTYPE)
