@@ -119,6 +119,13 @@ def lib(omp=False):
         L.tfo_swap_out.argtypes = [P]
         L.tfo_swap_counts.argtypes = [P, P]
         L.tfo_alloc_failures.argtypes = [P, P]
+        L.tfo_test_sdf_read.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P, P]
+        L.tfo_test_normal_from_sdf.argtypes = [P, P, ctypes.c_int, P]
+        L.tfo_test_colour_at.argtypes = [P, P, ctypes.c_int, P]
+        L.tfo_test_block_visibility.argtypes = [P, P, P, ctypes.c_int, P, P]
+        L.tfo_test_project_blocks.argtypes = [P, P, P, ctypes.c_int, P, P, P]
+        L.tfo_test_alloc_type.argtypes = [P]; L.tfo_test_alloc_type.restype = P
+        L.tfo_test_block_coords.argtypes = [P]; L.tfo_test_block_coords.restype = P
         for name in ("tfo_alloc_list", "tfo_excess_list", "tfo_hash", "tfo_vba", "tfo_visible_ids", "tfo_visible_type", "tfo_range_image",
                      "tfo_raycast_result", "tfo_dists", "tfo_frame_grey", "tfo_swap_state", "tfo_swap_stored_flags",
                      "tfo_swap_stored", "tfo_vba_rgb"):
@@ -368,6 +375,77 @@ class Oracle:
             self._view(self.L.tfo_swap_state(self.ctx), np.uint8, n_tot)[:] = swap_state
             self._view(self.L.tfo_swap_stored_flags(self.ctx), np.uint8, n_tot)[:] = swap_stored_flags
             self._view(self.L.tfo_swap_stored(self.ctx), VOXEL_DTYPE, n_tot * 512)[:] = np.asarray(swap_stored, VOXEL_DTYPE)
+
+    def upload_vba(self, vba, vba_rgb=None):
+        """Write all voxels (VOXEL_DTYPE) and, in a voxel_rgb context, the colour plane (uint32)."""
+        nv = self.params.n_blocks * 512
+        self._view(self.L.tfo_vba(self.ctx), VOXEL_DTYPE, nv)[:] = np.asarray(vba, VOXEL_DTYPE)
+        if vba_rgb is not None:
+            self._view(self.L.tfo_vba_rgb(self.ctx), np.uint32, nv)[:] = vba_rgb
+
+    def upload_range_image(self, r):
+        self._view(self.L.tfo_range_image(self.ctx), np.float32, self.W * self.H * 2)[:] = np.asarray(r, np.float32).reshape(-1)
+
+    def upload_raycast_result(self, r):
+        self._view(self.L.tfo_raycast_result(self.ctx), np.float32, self.W * self.H * 4)[:] = np.asarray(r, np.float32).reshape(-1)
+
+    def upload_visible_type(self, t):
+        self._view(self.L.tfo_visible_type(self.ctx), np.uint8, self.n_total)[:] = t
+
+    def render_type(self, invM_rt, type, into=None):
+        """RenderImage_common's pixel stage of `type` on the current raycast result, into a zeroed
+        image or into `into` (types that keep alpha)."""
+        img = np.zeros((self.H, self.W, 4), np.uint8) if into is None else np.ascontiguousarray(into, np.uint8).copy()
+        self.L.tfo_render_type(self.ctx, ptr(np.ascontiguousarray(invM_rt, np.float32).reshape(12)), int(type), ptr(img))
+        return img
+
+    # test hooks of the reference stage pin: the static per-element functions
+    def sdf_read(self, pts, carried):
+        """(uninterpolated, vmIndex, interpolated, interpolated with confidence, confidence) at each of
+        the points (n, 3), each read with a fresh IndexCache or one carried along the sequence."""
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        n = len(p)
+        u, i, cs, cf = (np.empty(n, np.float32) for _ in range(4))
+        vm = np.empty(n, np.int32)
+        self.L.tfo_test_sdf_read(self.ctx, ptr(p), n, int(carried), ptr(u), ptr(vm), ptr(i), ptr(cs), ptr(cf))
+        return u, vm, i, cs, cf
+
+    def normal_from_sdf(self, pts):
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        out = np.empty_like(p)
+        self.L.tfo_test_normal_from_sdf(self.ctx, ptr(p), len(p), ptr(out))
+        return out
+
+    def colour_at(self, pts):
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        out = np.empty((len(p), 4), np.uint8)
+        self.L.tfo_test_colour_at(self.ctx, ptr(p), len(p), ptr(out))
+        return out
+
+    def block_visibility(self, pose_rt, blocks):
+        """(check_block_visibility, check_block_enlarged) of block positions (n, 3) int16."""
+        b = np.ascontiguousarray(blocks, np.int16).reshape(-1, 3)
+        vis, enl = np.empty(len(b), np.uint8), np.empty(len(b), np.uint8)
+        self.L.tfo_test_block_visibility(self.ctx, ptr(np.ascontiguousarray(pose_rt, np.float32).reshape(12)), ptr(b), len(b),
+                                         ptr(vis), ptr(enl))
+        return vis, enl
+
+    def alloc_requests(self, pose_rt, dists):
+        """buildHashAllocAndVisibleTypePP over a dists image on zeroed arrays, without the allocation pass:
+        (entriesAllocType, entriesVisibleType, blockCoords (n_total, 4)).  The visible list is rebuilt."""
+        self.upload_visible_type(np.zeros(self.n_total, np.uint8))
+        self.alloc(pose_rt, dists, only_update_visible=True, reset_visible=True)
+        return (self._view(self.L.tfo_test_alloc_type(self.ctx), np.uint8, self.n_total).copy(), self.visible_type(),
+                self._view(self.L.tfo_test_block_coords(self.ctx), np.int16, self.n_total * 4, (self.n_total, 4)).copy())
+
+    def project_blocks(self, pose_rt, entries):
+        """The block projection of hash entries (indices): (accepted, box (n, 4) int16: upperLeft x, y,
+        lowerRight x, y, depth range (n, 2)); zeros where rejected or ptr < 0."""
+        e = np.ascontiguousarray(entries, np.int32)
+        valid, box, z = np.empty(len(e), np.uint8), np.empty((len(e), 4), np.int16), np.empty((len(e), 2), np.float32)
+        self.L.tfo_test_project_blocks(self.ctx, ptr(np.ascontiguousarray(pose_rt, np.float32).reshape(12)), ptr(e), len(e),
+                                       ptr(valid), ptr(box), ptr(z))
+        return valid, box, z
 
     def upload_visible_ids(self, ids):
         ids = np.ascontiguousarray(ids, np.int32)

@@ -1965,6 +1965,42 @@ void tfo_render_image(tfo_ctx* c, uint8_t* rgba)
     tfo_render_grey(c, c->pose, rgba);
 }
 
+/* ProjectSingleBlock, VisualisationEngine_Shared.hpp:33-75: the block's bounding box in the range image and its
+   depth range; 0 where the projection is rejected */
+static int project_block(const tfo_ctx* c, const tfo_hash_entry* e, const float M[16], int* pulx, int* puly, int* plrx, int* plry,
+                         float* pzmin, float* pzmax)
+{
+    const int W = c->p.cols, H = c->p.rows;
+    const float vs = c->p.voxelSize;
+    int ulx = W / SUBSAMPLE, uly = H / SUBSAMPLE, lrx = -1, lry = -1;
+    float zmin = FAR_AWAY, zmax = VERY_CLOSE;
+    for (int corner = 0; corner < 8; ++corner) {
+        int16_t tx = (int16_t)(e->x + ((corner & 1) ? 1 : 0));
+        int16_t ty = (int16_t)(e->y + ((corner & 2) ? 1 : 0));
+        int16_t tz = (int16_t)(e->z + ((corner & 4) ? 1 : 0));
+        float p3[4] = { (float)tx * (float)BLK * vs, (float)ty * (float)BLK * vs, (float)tz * (float)BLK * vs, 1.0f }, q[4];
+        m4v(M, p3, q);
+        if ((double)q[2] < 1e-6) continue;
+        float p2x = (c->p.fx * q[0] / q[2] + c->p.cx) / (float)SUBSAMPLE;
+        float p2y = (c->p.fy * q[1] / q[2] + c->p.cy) / (float)SUBSAMPLE;
+        if ((float)ulx > floorf(p2x)) ulx = (int)floorf(p2x);
+        if ((float)lrx < ceilf(p2x)) lrx = (int)ceilf(p2x);
+        if ((float)uly > floorf(p2y)) uly = (int)floorf(p2y);
+        if ((float)lry < ceilf(p2y)) lry = (int)ceilf(p2y);
+        if (zmin > q[2]) zmin = q[2];
+        if (zmax < q[2]) zmax = q[2];
+    }
+    if (ulx < 0) ulx = 0;
+    if (uly < 0) uly = 0;
+    if (lrx >= W) lrx = W - 1;
+    if (lry >= H) lry = H - 1;
+    if (ulx > lrx || uly > lry) return 0;
+    if (zmin < VERY_CLOSE) zmin = VERY_CLOSE;
+    if (zmax < VERY_CLOSE) return 0;
+    *pulx = ulx; *puly = uly; *plrx = lrx; *plry = lry; *pzmin = zmin; *pzmax = zmax;
+    return 1;
+}
+
 /* CreateExpectedDepths, VisualisationEngine_CUDA.cu:119-173; ProjectSingleBlock / CreateRenderingBlocks
    VisualisationEngine_Shared.hpp:33-95; projectAndSplitBlocks_device / fillBlocks_device VisualisationHelper.cu:52-121 */
 void tfo_expected_depths(tfo_ctx* c, const float pose_rt[12])
@@ -1975,36 +2011,13 @@ void tfo_expected_depths(tfo_ctx* c, const float pose_rt[12])
     if (c->noVisibleEntries == 0) return;
     float M[16];
     rt_to_m4(pose_rt, M);
-    float vs = c->p.voxelSize;
     unsigned total = 0;
     for (int i = 0; i < c->noVisibleEntries; ++i) {
         const tfo_hash_entry* e = &c->hash[c->visibleIds[i]];
         if (e->ptr < 0) continue;
-        int ulx = W / SUBSAMPLE, uly = H / SUBSAMPLE, lrx = -1, lry = -1;
-        float zmin = FAR_AWAY, zmax = VERY_CLOSE;
-        for (int corner = 0; corner < 8; ++corner) {
-            int16_t tx = (int16_t)(e->x + ((corner & 1) ? 1 : 0));
-            int16_t ty = (int16_t)(e->y + ((corner & 2) ? 1 : 0));
-            int16_t tz = (int16_t)(e->z + ((corner & 4) ? 1 : 0));
-            float p3[4] = { (float)tx * (float)BLK * vs, (float)ty * (float)BLK * vs, (float)tz * (float)BLK * vs, 1.0f }, q[4];
-            m4v(M, p3, q);
-            if ((double)q[2] < 1e-6) continue;
-            float p2x = (c->p.fx * q[0] / q[2] + c->p.cx) / (float)SUBSAMPLE;
-            float p2y = (c->p.fy * q[1] / q[2] + c->p.cy) / (float)SUBSAMPLE;
-            if ((float)ulx > floorf(p2x)) ulx = (int)floorf(p2x);
-            if ((float)lrx < ceilf(p2x)) lrx = (int)ceilf(p2x);
-            if ((float)uly > floorf(p2y)) uly = (int)floorf(p2y);
-            if ((float)lry < ceilf(p2y)) lry = (int)ceilf(p2y);
-            if (zmin > q[2]) zmin = q[2];
-            if (zmax < q[2]) zmax = q[2];
-        }
-        if (ulx < 0) ulx = 0;
-        if (uly < 0) uly = 0;
-        if (lrx >= W) lrx = W - 1;
-        if (lry >= H) lry = H - 1;
-        if (ulx > lrx || uly > lry) continue;
-        if (zmin < VERY_CLOSE) zmin = VERY_CLOSE;
-        if (zmax < VERY_CLOSE) continue;
+        int ulx, uly, lrx, lry;
+        float zmin, zmax;
+        if (!project_block(c, e, M, &ulx, &uly, &lrx, &lry, &zmin, &zmax)) continue;
         int nbx = (int)ceilf((float)(lrx - ulx + 1) / RB_SIZE);
         int nby = (int)ceilf((float)(lry - uly + 1) / RB_SIZE);
         unsigned need = (unsigned)(nbx * nby);
@@ -2168,4 +2181,71 @@ int tfo_hash_index(int x, int y, int z, int n_buckets)
 {
     return (int)((((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349669u) ^ ((uint32_t)z * 83492791u)) &
                  (uint32_t)(n_buckets - 1));
+}
+
+/* ------------------------------------------------------------------------- */
+/* test hooks: the static per-element functions above, exposed as they are, for the reference
+   stage pin (tests/test_oracle_stage_pin.py against tests/golden/stage_pin_*.bin)             */
+/* ------------------------------------------------------------------------- */
+
+/* the SDF reads at n points (3 floats each, voxel units); carried: one IndexCache per read kind
+   carried along the point sequence, else a fresh one per point */
+void tfo_test_sdf_read(const tfo_ctx* c, const float* pts, int n, int carried, float* uninterp, int* vm,
+                       float* interp, float* conf_sdf, float* conf)
+{
+    icache ku, ki, kc;
+    cache_init(&ku); cache_init(&ki); cache_init(&kc);
+    for (int i = 0; i < n; ++i) {
+        int v;
+        if (!carried) { cache_init(&ku); cache_init(&ki); cache_init(&kc); }
+        uninterp[i] = sdf_uninterp(c, pts + 3 * i, &vm[i], &ku);
+        interp[i] = sdf_interp(c, pts + 3 * i, &v, &ki);
+        conf_sdf[i] = sdf_interp_conf(c, &conf[i], pts + 3 * i, &v, &kc);
+    }
+}
+
+void tfo_test_normal_from_sdf(const tfo_ctx* c, const float* pts, int n, float* normals)
+{
+    for (int i = 0; i < n; ++i) normal_from_sdf(c, pts + 3 * i, normals + 3 * i);
+}
+
+void tfo_test_colour_at(const tfo_ctx* c, const float* pts, int n, uint8_t* rgba)
+{
+    for (int i = 0; i < n; ++i) colour_at(c, pts + 3 * i, rgba + 4 * i);
+}
+
+/* check_block_visibility / check_block_enlarged of n block positions (3 shorts each) under the
+   context's intrinsics, voxel size and image size */
+void tfo_test_block_visibility(const tfo_ctx* c, const float pose_rt[12], const int16_t* blocks, int n,
+                               uint8_t* visible, uint8_t* enlarged)
+{
+    float M[16];
+    rt_to_m4(pose_rt, M);
+    const float proj[4] = { c->p.fx, c->p.fy, c->p.cx, c->p.cy };
+    for (int i = 0; i < n; ++i) {
+        const int16_t* b = blocks + 3 * i;
+        visible[i] = (uint8_t)check_block_visibility(b[0], b[1], b[2], M, proj, c->p.voxelSize, c->p.cols, c->p.rows);
+        enlarged[i] = (uint8_t)check_block_enlarged(b[0], b[1], b[2], M, proj, c->p.voxelSize, c->p.cols, c->p.rows);
+    }
+}
+
+/* the request arrays buildHashAllocAndVisibleTypePP fills (entriesAllocType, blockCoords: 4 shorts per entry), as the
+   last tfo_alloc_ex left them; with only_update_visible the allocation pass did not consume them */
+uint8_t* tfo_test_alloc_type(tfo_ctx* c) { return c->allocType; }
+int16_t* tfo_test_block_coords(tfo_ctx* c) { return c->blockCoords; }
+
+/* project_block of n hash entries (by index): valid flag, box (upperLeft x, y, lowerRight x, y), depth range */
+void tfo_test_project_blocks(const tfo_ctx* c, const float pose_rt[12], const int* entries, int n, uint8_t* valid,
+                             int16_t* box, float* zrange)
+{
+    float M[16];
+    rt_to_m4(pose_rt, M);
+    for (int i = 0; i < n; ++i) {
+        int b[4] = { 0, 0, 0, 0 };
+        float z[2] = { 0, 0 };
+        const tfo_hash_entry* e = &c->hash[entries[i]];
+        valid[i] = (uint8_t)(e->ptr >= 0 && project_block(c, e, M, &b[0], &b[1], &b[2], &b[3], &z[0], &z[1]));
+        for (int k = 0; k < 4; ++k) box[4 * i + k] = (int16_t)(valid[i] ? b[k] : 0);
+        zrange[2 * i] = valid[i] ? z[0] : 0; zrange[2 * i + 1] = valid[i] ? z[1] : 0;
+    }
 }

@@ -12,8 +12,14 @@
  * (Matrix.hpp / Vector.hpp / MathUtils.hpp / VoxelTypes.hpp) are built by
  * oracle/ref_pin (outputs in oracle/_ref/) and pin this oracle's matrix inverse,
  * matrix-vector order, floor/round conversions and Voxel_s quantisation
- * (tests/golden/ref_pin_*.bin).  Everything else is "parity unpinned": restated
- * from the cited reference lines under the canonical numerics below.
+ * (tests/golden/ref_pin_*.bin).  The per-element functions the reference shares between host
+ * and device (RepresentationAccess.hpp, VisualisationEngine_Shared.hpp,
+ * SceneReconstructionEngine.hpp: the SDF reads, castRay, the voxel update and its colour half,
+ * the per-pixel allocation walk, block visibility, block projection into rendering blocks, the pixel shaders) are compiled
+ * for the host by oracle/ref_pin/ref_pin_stages.cpp behind declaration-only OpenCV / CUDA
+ * stand-ins and pin the stage functions here (tests/golden/stage_pin_*.bin,
+ * tests/test_oracle_stage_pin.py).  Everything else (imgproc.cu, proj_icp.cu, the allocation-list and visible-list kernels, the OpenCV algebra) is
+ * "parity unpinned": restated from the cited reference lines under the canonical numerics below.
  *
  * Canonical numerics (the reference's CUDA build uses --ftz --prec-div=false
  * --prec-sqrt=false and fast intrinsics, which are not reproducible off NVIDIA):
@@ -199,6 +205,19 @@ float* tfo_curr_normals(tfo_ctx* c, int level);
 uint16_t* tfo_curr_depth(tfo_ctx* c, int level);
 float* tfo_dists(tfo_ctx* c);
 uint8_t* tfo_frame_grey(tfo_ctx* c);    /* W*H rgba: renderImage inside the last tracked frame */
+/* test hooks for the reference stage pin: the static per-element functions, exposed unchanged
+   (readFromSDF_float_uninterpolated / _interpolated / readWithConfidence..., with a fresh or a
+   carried IndexCache; computeSingleNormalFromSDF; drawPixelColour's read; checkBlockVisibility; ProjectSingleBlock) */
+void tfo_test_sdf_read(const tfo_ctx* c, const float* pts, int n, int carried, float* uninterp, int* vm,
+                       float* interp, float* conf_sdf, float* conf);
+void tfo_test_normal_from_sdf(const tfo_ctx* c, const float* pts, int n, float* normals);
+void tfo_test_colour_at(const tfo_ctx* c, const float* pts, int n, uint8_t* rgba);
+uint8_t* tfo_test_alloc_type(tfo_ctx* c);      /* entriesAllocType of the last tfo_alloc_ex */
+int16_t* tfo_test_block_coords(tfo_ctx* c);    /* blockCoords, 4 shorts per entry */
+void tfo_test_project_blocks(const tfo_ctx* c, const float pose_rt[12], const int* entries, int n, uint8_t* valid,
+                             int16_t* box, float* zrange);     /* ProjectSingleBlock per hash entry */
+void tfo_test_block_visibility(const tfo_ctx* c, const float pose_rt[12], const int16_t* blocks, int n,
+                               uint8_t* visible, uint8_t* enlarged);
 
 #ifdef __cplusplus
 }
