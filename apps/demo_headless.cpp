@@ -8,6 +8,7 @@
 //   ./demo_headless [frames=100] [cols=640] [rows=480]
 //   ./demo_headless --pgm 'dir/%04d.pgm' [--ppm 'dir/%04d.ppm'] [max_frames]
 //   ... --mesh out.ply : the reconstructed surface after the last frame (TopFu::saveMesh)
+//   ... --mesh-normals : with per-vertex normals (nx ny nz) in that PLY
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -27,11 +28,13 @@ using namespace tfusion;
 int main(int argc, char** argv)
 {
     std::string pgm, ppm, mesh;
+    bool mesh_normals = false;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--pgm") && i + 1 < argc) pgm = argv[++i];
         else if (!std::strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh = argv[++i];
+        else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
         else pos.push_back(argv[i]);
     }
     int frames = pos.size() > 0 ? std::atoi(pos[0]) : (pgm.empty() ? 100 : 1 << 30);
@@ -92,7 +95,8 @@ int main(int argc, char** argv)
     std::printf("frames %d ok %d resets %d visible %d  pose t = (%.4f %.4f %.4f)\n", n, n_ok, st.n_resets,
                 st.noVisibleEntries, pose.translation()[0], pose.translation()[1], pose.translation()[2]);
     if (!mesh.empty()) {
-        topfu->saveMesh(mesh);
+        if (mesh_normals) topfu->saveMesh(mesh, TF_MESH_NORMALS);
+        else topfu->saveMesh(mesh);
         std::printf("mesh written to %s\n", mesh.c_str());
     }
     long lit = 0;

@@ -261,6 +261,26 @@ namespace tfusion
         }
         // the mesh as a binary PLY with welded vertices
         void saveMesh(const std::string& path) { check(tf_mesh_save_ply(ctx_, path.c_str()), "tf_mesh_save_ply"); }
+        // extractMesh with per-vertex attributes (tf_mesh_extract_attr): normals (9 floats per triangle,
+        // unit TSDF gradient per vertex) and colours (12 bytes per triangle, RGBA per vertex; voxel_rgb
+        // contexts only), each skipped when its pointer is null; the same triangles in the same order
+        long long extractMesh(cuda::DeviceArray<float>& triangles, cuda::DeviceArray<float>* normals,
+                              cuda::DeviceArray<unsigned char>* colours)
+        {
+            long long n = 0;
+            check(tf_mesh_extract_attr(ctx_, nullptr, nullptr, nullptr, 0, &n), "tf_mesh_extract_attr");
+            triangles.create((size_t)n * 9);
+            if (normals) normals->create((size_t)n * 9);
+            if (colours) colours->create((size_t)n * 12);
+            if (n > 0) {
+                long long m = 0;
+                check(tf_mesh_extract_attr(ctx_, triangles.ptr(), normals ? normals->ptr() : nullptr,
+                                           colours ? colours->ptr() : nullptr, n, &m), "tf_mesh_extract_attr");
+            }
+            return n;
+        }
+        // the mesh as a PLY with nx ny nz (TF_MESH_NORMALS) and / or red green blue alpha (TF_MESH_COLOURS)
+        void saveMesh(const std::string& path, int attrs) { check(tf_mesh_save_ply_attr(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_attr"); }
 
         tf_ctx* handle() { return ctx_; }
         hipStream_t stream() const { return (hipStream_t)tf_get_stream(ctx_); }

@@ -453,6 +453,33 @@ tf_status tf_mesh_write_ply(const char* path, const float* host_triangles, long 
  * tf_mesh_write_ply; TF_OOM when the buffers cannot be had */
 tf_status tf_mesh_save_ply(tf_ctx* ctx, const char* path);
 
+/* Per-vertex attributes (Mesh extraction, attributes).  Every vertex lies on a cube edge
+ * between two voxels; its normal is the TSDF's integer gradient at the two (central differences, one-sided
+ * next to a missing or unobserved voxel) interpolated like the position and normalised -- it points
+ * towards free space, as the triangles' right-hand normal does -- and its colour the colour plane's
+ * words at the two, interpolated where both have w_color > 0.  Both are functions of the edge alone. */
+#define TF_MESH_NORMALS 1
+#define TF_MESH_COLOURS 2
+/* addition (no reference counterpart): tf_mesh_extract with up to three outputs for the same triangles in
+ * the same order, each skipped when its pointer is NULL: positions float[n][9] (byte-identical to
+ * tf_mesh_extract's), unit normals float[n][9] (three xyz per triangle; (0, 0, 0) where the gradient
+ * vanishes), colours uint8[n][12] (RGBA per vertex, alpha 255, or 0 0 0 0 where neither end of the edge
+ * has colour; the buffer 4-byte aligned).  All are clipped at the same capacity; with all three NULL
+ * capacity must be 0 (count only).  dev_colours on a context without voxel_rgb is TF_INVALID_ARG.
+ * *n_triangles = the full count.  Synchronous; the scene is only read. */
+tf_status tf_mesh_extract_attr(tf_ctx* ctx, float* dev_triangles, float* dev_normals, uint8_t* dev_colours,
+                               long long capacity, long long* n_triangles);
+/* addition (no reference counterpart): host only, no context -- tf_mesh_write_ply with vertex properties
+ * x y z, then nx ny nz when host_normals is given, then red green blue alpha (uchar) when host_colours
+ * is; vertices welded by exact bit equality of the whole record (position and attributes), faces in the
+ * input order.  With both attribute pointers NULL the file is tf_mesh_write_ply's, byte for byte. */
+tf_status tf_mesh_write_ply_attr(const char* path, const float* host_triangles, const float* host_normals,
+                                 const uint8_t* host_colours, long long n);
+/* addition (no reference counterpart): count, extract into temporary device buffers, download,
+ * tf_mesh_write_ply_attr; attrs = TF_MESH_NORMALS | TF_MESH_COLOURS or either or 0; TF_OOM when the
+ * buffers cannot be had, TF_INVALID_ARG for TF_MESH_COLOURS without voxel_rgb */
+tf_status tf_mesh_save_ply_attr(tf_ctx* ctx, const char* path, int attrs);
+
 #ifdef __cplusplus
 }
 #endif

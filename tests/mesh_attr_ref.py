@@ -1,0 +1,247 @@
+"""CPU restatement of the mesh's per-vertex attributes (DESIGN.md §Mesh extraction, attributes) in
+numpy, float32 throughout, written from the specification and not from the kernel.
+
+Triangles, their order and their edges are mesh_ref's (its case tables and corner enumeration); this
+module adds, per triangle vertex, the normal (the integer TSDF gradient at the two ends of the
+crossed edge, interpolated and normalised) and the colour (the colour plane's words at the two ends).
+
+    extract_attr(hash, vba, rgb, voxel_size, n_buckets) -> (tris (n, 3, 3) f32, normals (n, 3, 3) f32,
+                                                            colours (n, 3, 4) u8 | None)
+"""
+import itertools
+
+import numpy as np
+
+import mesh_ref as M
+
+RULES = ("central", "forward", "backward", "none")      # how one axis of an end's gradient was formed
+COLOUR_RULES = ("both", "lower only", "upper only", "neither")
+
+
+def _tiles27(h, vba, rgb, n_buckets, live):
+    """sdf, w and colour word in a (n, 24, 24, 24) [z, y, x] box around each live entry's block: the
+    27 blocks at offsets -1 .. 1, local coordinate c at index c + 8.  A missing block (not in the hash,
+    swapped out, a coordinate outside the short range) reads sdf 32767, w 0, colour word 0."""
+    v = vba.reshape(-1, 8, 8, 8)
+    c = None if rgb is None else np.asarray(rgb, np.uint32).reshape(-1, 8, 8, 8)
+    n = len(live)
+    sdf = np.full((n, 24, 24, 24), 32767, np.int32)
+    w = np.zeros((n, 24, 24, 24), np.int32)
+    col = np.zeros((n, 24, 24, 24), np.uint32)
+    cache = {}
+    for i, e in enumerate(live):
+        b = (int(h["x"][e]), int(h["y"][e]), int(h["z"][e]))
+        for oz, oy, ox in itertools.product((-1, 0, 1), repeat=3):
+            if (ox, oy, oz) == (0, 0, 0):
+                p = int(h["ptr"][e])
+            else:
+                key = (b[0] + ox, b[1] + oy, b[2] + oz)
+                if key not in cache:
+                    cache[key] = M.find_block(h, n_buckets, key)
+                p = cache[key]
+            if p >= 0:
+                sl = (i, slice(8 * oz + 8, 8 * oz + 16), slice(8 * oy + 8, 8 * oy + 16), slice(8 * ox + 8, 8 * ox + 16))
+                sdf[sl] = v["sdf"][p]
+                w[sl] = v["w"][p]
+                if c is not None:
+                    col[sl] = c[p]
+    return sdf, w, col
+
+
+def _gradients(sdf, w):
+    """The integer gradient and the rule that formed it at every point of the boxes except their rim:
+    (n, 22, 22, 22, 3) int32 and int8, axis order x y z, index c + 7."""
+    usable = w > 0
+    mid = (slice(None), slice(1, 23), slice(1, 23), slice(1, 23))
+    s0 = sdf[mid]
+    G = np.zeros(s0.shape + (3,), np.int32)
+    rule = np.zeros(s0.shape + (3,), np.int8)
+    for a in range(3):                                    # array axis of x y z: 3 2 1
+        ax = 3 - a
+        up = [slice(None), slice(1, 23), slice(1, 23), slice(1, 23)]
+        dn = list(up)
+        up[ax] = slice(2, 24)
+        dn[ax] = slice(0, 22)
+        sp, sm, hp, hm = sdf[tuple(up)], sdf[tuple(dn)], usable[tuple(up)], usable[tuple(dn)]
+        G[..., a] = np.where(hp & hm, sp - sm, np.where(hp, 2 * (sp - s0), np.where(hm, 2 * (s0 - sm), 0)))
+        rule[..., a] = np.where(hp & hm, 0, np.where(hp, 1, np.where(hm, 2, 3)))
+    return G, rule, usable[mid]
+
+
+def vertex_normal(t, Gp, Gq):
+    """N = RN(Gp + RN(t (Gq - Gp))) per axis, normalised: L2 = RN(RN(Nx Nx + Ny Ny) + Nz Nz), L = sqrt,
+    N / L, (0, 0, 0) where L == 0.  t float32 (...), Gp, Gq int (..., 3)."""
+    t = np.asarray(t, np.float32)[..., None]
+    Gp, Gq = np.asarray(Gp, np.int64), np.asarray(Gq, np.int64)
+    N = Gp.astype(np.float32) + (t * (Gq - Gp).astype(np.float32)).astype(np.float32)
+    N = N.astype(np.float32)
+    sq = (N * N).astype(np.float32)
+    L2 = ((sq[..., 0] + sq[..., 1]).astype(np.float32) + sq[..., 2]).astype(np.float32)
+    L = np.sqrt(L2).astype(np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = (N / L[..., None]).astype(np.float32)
+    return np.where((L == 0)[..., None], np.float32(0), out)
+
+
+def vertex_colour(t, wp, wq, hp, hq):
+    """RGBA bytes (..., 4) from the ends' colour words and whether each end has colour."""
+    t = np.asarray(t, np.float32)
+    wp, wq = np.asarray(wp, np.uint32), np.asarray(wq, np.uint32)
+    out = np.zeros(t.shape + (4,), np.uint8)
+    for c in range(3):
+        cp = (wp >> np.uint32(8 * c) & np.uint32(255)).astype(np.int64)
+        cq = (wq >> np.uint32(8 * c) & np.uint32(255)).astype(np.int64)
+        f = (cp.astype(np.float32) + (t * (cq - cp).astype(np.float32)).astype(np.float32)).astype(np.float32)
+        both = (f + np.float32(0.5)).astype(np.float32).astype(np.int32).astype(np.uint8)
+        out[..., c] = np.where(hp & hq, both, np.where(hp, cp, np.where(hq, cq, 0)))
+    out[..., 3] = np.where(hp | hq, 255, 0)
+    return out
+
+
+def extract_attr(h, vba, rgb, voxel_size, n_buckets, chunk=32, stats=None):
+    """(triangles, normals, colours) of the scene in extraction order; colours None when rgb (the colour
+    plane, uint32 per voxel) is None.  stats (dict, optional) receives, over the distinct crossed
+    edges: 'edges'; 'rules' (3 axes x 4 RULES counts over the edges' ends); 'colour_rules' (4 counts);
+    'down_block' (ends that took a -1 neighbour from another block than their own); 'zero' (edges
+    whose normal is (0, 0, 0))."""
+    vs = np.float32(voxel_size)
+    corners, ntri, edges = M._tables()
+    live = np.nonzero(h["ptr"] >= 0)[0]
+    zz, yy, xx = np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij")
+    local = np.stack([xx, yy, zz], -1).reshape(512, 3)      # voxel = x + 8y + 64z
+    out_t, out_n, out_c, rec = [], [], [], []
+    for c0 in range(0, len(live), chunk):
+        ent = live[c0:c0 + chunk]
+        n = len(ent)
+        sdf, w, col = _tiles27(h, vba, rgb, n_buckets, ent)
+        G, rule, usable = _gradients(sdf, w)
+        at = lambda a, p: a[np.arange(n)[:, None, None, None], p[..., 2] + 8, p[..., 1] + 8, p[..., 0] + 8]
+        atg = lambda a, p: a[np.arange(n)[:, None, None, None], p[..., 2] + 7, p[..., 1] + 7, p[..., 0] + 7]
+        valid = np.ones((n, 512), bool)
+        for d in itertools.product((0, 1), repeat=3):
+            valid &= at(w, (local + np.array(d))[None, :, None, None, :])[:, :, 0, 0] > 0
+        origin = np.stack([h["x"][ent], h["y"][ent], h["z"][ent]], -1).astype(np.int64) * 8      # (n, 3)
+        for_k = []
+        for k in range(6):
+            cs = corners[k]                                            # (4, 3) xyz
+            s = np.stack([at(sdf, (local + c)[None, :, None, None, :])[:, :, 0, 0] for c in cs], -1)    # (n, 512, 4)
+            m = np.where(valid, ((s < 0) << np.arange(4)).sum(-1), 0)
+            e = edges[k][m]                                            # (n, 512, 2, 3, 2)
+            on = np.broadcast_to((np.arange(2)[None, None, :] < ntri[k][m][..., None])[..., None], e.shape[:-1])
+            p = local[None, :, None, None, :] + cs[e[..., 0]]          # lower end, local lattice coordinates
+            q = local[None, :, None, None, :] + cs[e[..., 1]]
+            sp, sq = at(sdf, p), at(sdf, q)
+            den = np.where(on, sp - sq, 1)
+            t = (sp.astype(np.float32) / den.astype(np.float32)).astype(np.float32)
+            gp = (origin[:, None, None, None, :] + p).astype(np.float32)
+            moved = ((gp + t[..., None]).astype(np.float32) * vs).astype(np.float32)
+            pos = np.where(q - p == 1, moved, (gp * vs).astype(np.float32))
+            nrm = vertex_normal(t, atg(G, p), atg(G, q))
+            hp = atg(usable, p) & (at(col, p) >> np.uint32(24) > 0)
+            hq = atg(usable, q) & (at(col, q) >> np.uint32(24) > 0)
+            rgba = vertex_colour(t, at(col, p), at(col, q), hp, hq)
+            for_k.append((on, pos, nrm, rgba))
+            if stats is not None:
+                sel = on
+                gl = origin[:, None, None, None, :]
+                # per vertex: the edge's global ends, then what the statistics need of each end
+                # an end takes a -1 neighbour from another block: a coordinate on a block face (8 | g) and
+                # that axis formed by the central or the backward rule
+                down = lambda x: (((gl + x) % 8 == 0) & ((atg(rule, x) == 0) | (atg(rule, x) == 2))).any(-1)
+                rec.append(np.concatenate([(gl + p)[sel], (gl + q)[sel], atg(rule, p)[sel], atg(rule, q)[sel],
+                                           hp[sel][:, None], hq[sel][:, None], down(p)[sel][:, None], down(q)[sel][:, None],
+                                           (nrm == 0).all(-1)[sel][:, None]], 1).astype(np.int64))
+        # extraction order: entry, voxel, tetrahedron, triangle, vertex
+        on = np.stack([f[0] for f in for_k], 2)                        # (n, 512, 6, 2, 3)
+        keep = on[..., 0]
+        out_t.append(np.stack([f[1] for f in for_k], 2)[keep])
+        out_n.append(np.stack([f[2] for f in for_k], 2)[keep])
+        out_c.append(np.stack([f[3] for f in for_k], 2)[keep])
+    cat = lambda parts, shape, dt: np.concatenate(parts).reshape(shape) if parts else np.zeros((0,) + shape[1:], dt)
+    tris = cat(out_t, (-1, 3, 3), np.float32)
+    normals = cat(out_n, (-1, 3, 3), np.float32)
+    colours = cat(out_c, (-1, 3, 4), np.uint8) if rgb is not None else None
+    if stats is not None:
+        r = np.unique(np.concatenate(rec), axis=0) if rec else np.zeros((0, 17), np.int64)
+        assert len(np.unique(r[:, :6], axis=0)) == len(r), "one edge, two sets of attributes"
+        ends = np.concatenate([r[:, 6:9], r[:, 9:12]])                 # (2 edges, 3 axes) rule codes
+        stats["edges"] = len(r)
+        stats["rules"] = np.array([[int((ends[:, a] == c).sum()) for c in range(4)] for a in range(3)])
+        hp, hq = r[:, 12] > 0, r[:, 13] > 0
+        stats["colour_rules"] = [int((hp & hq).sum()), int((hp & ~hq).sum()), int((~hp & hq).sum()), int((~hp & ~hq).sum())]
+        stats["down_block"] = int(r[:, 14].sum() + r[:, 15].sum())
+        stats["zero"] = int(r[:, 16].sum())
+    return tris, normals, colours
+
+
+def weld(tris, normals=None, colours=None):
+    """Vertices welded by exact bit equality of the whole record: (records (m, 3 | 6 | 7) uint32 -- position,
+    normal, RGBA word -- and faces (n, 3))."""
+    parts = [np.ascontiguousarray(tris, np.float32).reshape(-1, 3).view(np.uint32)]
+    if normals is not None:
+        parts.append(np.ascontiguousarray(normals, np.float32).reshape(-1, 3).view(np.uint32))
+    if colours is not None:
+        parts.append(np.ascontiguousarray(colours, np.uint8).reshape(-1, 4).view(np.uint32))
+    uniq, inv = np.unique(np.concatenate(parts, 1), axis=0, return_inverse=True)
+    return uniq, inv.reshape(-1, 3)
+
+
+# ---- the scenes both test files use, built and meshed once per session -----------------------------
+COLOUR_SEED = 5
+SLAB_SDF = (-3, -1, 1, -5, -5, -5, -5, -5)
+
+
+def colour_plane(n_voxels, seed=COLOUR_SEED, zeros=0.3):
+    """Random colour words, about `zeros` of them with w_color = 0."""
+    rng = np.random.default_rng(seed)
+    words = rng.integers(0, 1 << 32, n_voxels, dtype=np.uint64).astype(np.uint32)
+    words = np.where(words >> np.uint32(24) == 0, words | np.uint32(1 << 24), words)
+    return np.where(rng.random(n_voxels) < zeros, words & np.uint32(0xffffff), words).astype(np.uint32)
+
+
+def slab_scene():
+    """One block at the origin, all w = 1, sdf a function of x only (SLAB_SDF); capacities M.SMALL."""
+    from topfusion_amd import synth
+    from topfusion_amd.topfu import HASH_DTYPE, VOXEL_DTYPE
+    h, _, _ = synth.build_hash(np.array([(0, 0, 0)]), M.SMALL["n_buckets"], M.SMALL["n_excess"], HASH_DTYPE)
+    vba = np.zeros(M.SMALL["n_blocks"] * 512, VOXEL_DTYPE)
+    vba["sdf"] = 32767
+    v = vba.reshape(-1, 8, 8, 8)
+    v["sdf"][0] = np.array(SLAB_SDF, np.int16)[None, None, :]
+    v["w"][0] = 1
+    return h, vba
+
+
+_cache = {}
+
+
+def _case(name):
+    if name not in _cache:
+        if name == "slab":
+            cfg = M.SMALL
+            h, vba = slab_scene()
+            base = M.extract(h, vba, M.VOXEL_SIZE, cfg["n_buckets"])
+        else:
+            cfg = M.SMALL if name == "sphere" else M.RANDOM
+            h, vba, base, _ = M.sphere_case() if name == "sphere" else M.random_case()
+        rgb = colour_plane(vba.size)
+        stats = {}
+        tris, normals, colours = extract_attr(h, vba, rgb, M.VOXEL_SIZE, cfg["n_buckets"], stats=stats)
+        assert tris.tobytes() == base.tobytes(), f"{name}: the triangles are not mesh_ref.extract's"
+        for a in (h, vba, rgb, tris, normals, colours):
+            a.setflags(write=False)
+        _cache[name] = (h, vba, rgb, tris, normals, colours, stats)
+    return _cache[name]
+
+
+def sphere_case():
+    """(hash, vba, colour plane, triangles, normals, colours, stats) of mesh_ref's sphere."""
+    return _case("sphere")
+
+
+def random_case():
+    return _case("random")
+
+
+def slab_case():
+    return _case("slab")

@@ -12,12 +12,20 @@ runs (median of --reps after --warmup) and the bytes per second each achieves ag
 
 and that figure's ratio to the HBM peak.  One JSON line at the end.
 
-    python tools/mesh_time.py [--frames 32] [--reps 20] [--warmup 3]
+--attr adds tf_mesh_extract_attr on the same window, in the same run: normals only, normals + positions
+(both on the same context) and positions + normals + colours on a voxel_rgb context fused with the
+synthetic RGB stream of the colour tests (synth.render_colour at the orbit's poses), beside that
+context's own positions-only time.  Floor: live blocks x 2 KiB per pass + (36 + 36 + 12) B per triangle
+for what is written.  --parent-lib PATH (a libtfusion_hip.so built from the parent commit) runs the
+plain measurement once more in a child process on that library and records its positions-only time.
+
+    python tools/mesh_time.py [--frames 32] [--reps 20] [--warmup 3] [--attr] [--parent-lib PATH]
 """
 import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -35,6 +43,8 @@ def main():
     ap.add_argument("--rows", type=int, default=480)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--attr", action="store_true", help="also time tf_mesh_extract_attr")
+    ap.add_argument("--parent-lib", default=None, help="a parent-commit libtfusion_hip.so to time positions-only extraction on")
     args = ap.parse_args()
 
     from topfusion_amd import TopFu, default_params, synth, _lib as L
@@ -58,22 +68,28 @@ def main():
     dev = ctypes.c_void_p()
     assert hip.hipMalloc(ctypes.byref(dev), max(16, n * 36)) == 0, "hipMalloc"
 
-    def timed(buf, cap):
+    def timed_call(call, expect=None):
         got = ctypes.c_longlong()
         ms = []
         for i in range(args.warmup + args.reps):
             assert hip.hipEventRecord(e0, stream) == 0
-            L.check(lib.tf_mesh_extract(tf._h, buf, cap, ctypes.byref(got)), "tf_mesh_extract")
+            call(got)
             assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
             t = ctypes.c_float()
             assert hip.hipEventElapsedTime(ctypes.byref(t), e0, e1) == 0
-            assert got.value == n
+            assert got.value == (n if expect is None else expect)
             if i >= args.warmup:
                 ms.append(t.value)
         return float(np.median(ms)), float(np.min(ms))
 
+    def timed(buf, cap):
+        return timed_call(lambda got: L.check(lib.tf_mesh_extract(tf._h, buf, cap, ctypes.byref(got)), "tf_mesh_extract"))
+
     count_ms, count_min = timed(None, 0)
     full_ms, full_min = timed(dev, n)
+    attr = {}
+    if args.attr:
+        attr = time_attr(args, tf, n, live, dev, timed_call, full_ms)
     hip.hipFree(dev)
     hip.hipEventDestroy(e0)
     hip.hipEventDestroy(e1)
@@ -93,9 +109,80 @@ def main():
     print(f"live blocks {live}  triangles {n}")
     print(f"count only: {count_ms:.3f} ms  ({out['count_gbs']} GB/s of the floor's bytes, {100 * out['count_frac_of_hbm_peak']:.2f} % of peak)")
     print(f"full      : {full_ms:.3f} ms  ({out['full_gbs']} GB/s of the floor's bytes, {100 * out['full_frac_of_hbm_peak']:.2f} % of peak)")
+    for line in attr.pop("lines", []):
+        print(line)
+    out.update(attr)
+    if args.parent_lib:
+        cmd = [sys.executable, os.path.abspath(__file__), "--frames", str(args.frames), "--cols", str(W), "--rows", str(H),
+               "--reps", str(args.reps), "--warmup", str(args.warmup)]
+        r = subprocess.run(cmd, env=dict(os.environ, TFUSION_HIP_LIB=os.path.abspath(args.parent_lib)), capture_output=True, text=True,
+                           check=True)
+        parent = json.loads(r.stdout.strip().splitlines()[-1])
+        assert parent["triangles"] == n and parent["live_blocks"] == live
+        out["parent_full_ms"], out["parent_full_ms_min"], out["parent_count_ms"] = parent["full_ms"], parent["full_ms_min"], parent["count_ms"]
+        print(f"parent commit's library, same box: count only {parent['count_ms']:.3f} ms, full (positions only) {parent['full_ms']:.3f} ms"
+              f"  -- this build: {count_ms:.3f} / {full_ms:.3f} ms")
     print(json.dumps(out))
     frames.free()
     tf.close()
+
+
+def time_attr(args, tf, n, live, dev_tris, timed_call, full_ms):
+    """tf_mesh_extract_attr: normals only and normals + positions on `tf`; then a voxel_rgb context fused
+    with the same depth frames and the synthetic RGB stream: positions only (tf_mesh_extract) and all
+    three outputs.  Returns the JSON fields and the printed lines."""
+    from topfusion_amd import TopFu, default_params, synth, _lib as L
+    lib, hip = L.load(), L.hip_runtime()
+    W, H = args.cols, args.rows
+
+    def dev_alloc(nbytes):
+        d = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(d), max(16, nbytes)) == 0, "hipMalloc"
+        return d
+
+    dev_nrm, dev_col = dev_alloc(n * 36), dev_alloc(n * 12)
+
+    def attr_call(ctx, t, nr, co):
+        return lambda got: L.check(lib.tf_mesh_extract_attr(ctx._h, t, nr, co, n, ctypes.byref(got)), "tf_mesh_extract_attr")
+
+    gbs = lambda b, ms: b / (ms * 1e-3) / 1e9
+    fields, lines = {}, []
+
+    def report(key, label, ms, mn, per_tri, base_ms, tris=n):
+        floor = 2 * live * 2048 + per_tri * tris
+        fields.update({f"{key}_ms": round(ms, 4), f"{key}_ms_min": round(mn, 4), f"floor_bytes_{key}": floor,
+                       f"{key}_gbs": round(gbs(floor, ms), 2), f"{key}_over_positions_only": round(ms / base_ms, 3)})
+        lines.append(f"{label}: {ms:.3f} ms  ({fields[key + '_gbs']} GB/s of the floor's bytes, {100 * gbs(floor, ms) / PEAK_HBM_GBS:.2f} % of peak; "
+                     f"{ms / base_ms:.2f} x positions only, bytes written {per_tri} / 36 = {per_tri / 36:.2f} x)")
+
+    ms, mn = timed_call(attr_call(tf, None, dev_nrm, None))
+    report("normals", "normals only           ", ms, mn, 36, full_ms)
+    ms, mn = timed_call(attr_call(tf, dev_tris, dev_nrm, None))
+    report("pos_normals", "positions + normals    ", ms, mn, 72, full_ms)
+
+    # the colour context: the same depth frames, the colour tests' RGB stream (a registered colour camera)
+    fx, fy, cx, cy = synth.intrinsics(W, H)
+    tc = TopFu(default_params(cols=W, rows=H, fx=fx, fy=fy, cx=cx, cy=cy, voxel_rgb=1), device=0)
+    frames = synth.orbit_device(args.frames, W, H, seed=7)
+    rgbs = np.stack([synth.render_colour(*synth.orbit_pose(k), W, H) for k in range(args.frames)])
+    dev_rgb = dev_alloc(rgbs.nbytes)
+    assert hip.hipMemcpy(dev_rgb, rgbs.ctypes.data_as(ctypes.c_void_p), rgbs.nbytes, 1) == 0
+    tc.process_frames(frames.ptr, args.frames, rgb_frames=dev_rgb.value)
+    nc = tc.mesh_count()
+    assert nc <= n, (nc, n)                                    # (the buffers hold n; colour does not move the geometry)
+    plane = tc.vba_rgb()
+    fields.update({"rgb_ctx_triangles": nc, "coloured_voxels": int((plane >> 24 > 0).sum())})
+    ms_pos, mn_pos = timed_call(lambda got: L.check(lib.tf_mesh_extract(tc._h, dev_tris, n, ctypes.byref(got)), "tf_mesh_extract"), nc)
+    fields.update({"rgb_ctx_full_ms": round(ms_pos, 4), "rgb_ctx_full_ms_min": round(mn_pos, 4)})
+    lines.append(f"colour context ({nc} triangles), positions only (tf_mesh_extract): {ms_pos:.3f} ms")
+    ms, mn = timed_call(attr_call(tc, dev_tris, dev_nrm, dev_col), nc)
+    report("all", "positions + normals + colours", ms, mn, 84, ms_pos, nc)
+    for d in (dev_nrm, dev_col, dev_rgb):
+        hip.hipFree(d)
+    frames.free()
+    tc.close()
+    fields["lines"] = lines
+    return fields
 
 
 if __name__ == "__main__":

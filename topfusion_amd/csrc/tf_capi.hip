@@ -1710,3 +1710,110 @@ extern "C" tf_status tf_mesh_save_ply(tf_ctx* c, const char* path)
     free(host);
     return s;
 }
+
+// ---- mesh extraction with per-vertex attributes (additions; DESIGN.md §Mesh extraction, attributes) ----
+extern "C" tf_status tf_mesh_extract_attr(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity,
+                                          long long* n_triangles)
+{
+    TF_FLUSH(c);
+    const bool any = dev_triangles || dev_normals || dev_colours;
+    if (!c || !n_triangles || capacity < 0 || (capacity > 0 && !any)) return TF_INVALID_ARG;
+    if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long n = 0;
+    tf_status s = mesh_count(c, &n);
+    if (s != TF_OK) return s;
+    *n_triangles = n;
+    if (capacity == 0 || !any || n == 0) return TF_OK;
+    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
+    if (dev_normals || dev_colours) {
+        TF_CHECK(tfk_mesh_emit_attr(c, dev_triangles, dev_normals, dev_colours, capacity));
+    } else {
+        TF_CHECK(tfk_mesh_emit(c, dev_triangles, capacity));
+    }
+    return sync_checked(c);
+}
+
+// records of 3 (+ 3) (+ 1) dwords per vertex, welded by the exact bits of the whole record
+extern "C" tf_status tf_mesh_write_ply_attr(const char* path, const float* host_triangles, const float* host_normals,
+                                            const uint8_t* host_colours, long long n)
+{
+    if (!host_normals && !host_colours) return tf_mesh_write_ply(path, host_triangles, n);
+    if (!path || n < 0 || (n > 0 && !host_triangles) || n > (long long)(0x7fffffff / 3)) return TF_INVALID_ARG;
+    const size_t nv = (size_t)n * 3;
+    const size_t nw = 3 + (host_normals ? 3 : 0) + (host_colours ? 1 : 0);      // dwords per record
+    size_t cap = 16;
+    while (cap < nv * 2) cap <<= 1;
+    std::vector<int> slot, face;
+    std::vector<uint32_t> verts;                          // nw dwords per welded vertex
+    try { slot.assign(cap, 0); face.resize(nv); verts.reserve((nv / 4 + 16) * nw); } catch (const std::bad_alloc&) { return TF_OOM; }
+    try {
+        for (size_t i = 0; i < nv; ++i) {
+            uint32_t k[7];
+            memcpy(k, host_triangles + 3 * i, 12);
+            size_t w = 3;
+            if (host_normals) { memcpy(k + w, host_normals + 3 * i, 12); w += 3; }
+            if (host_colours) memcpy(k + w, host_colours + 4 * i, 4);
+            size_t h = 0;
+            for (size_t j = 0; j < nw; ++j) h = (h ^ k[j]) * 0x9e3779b1u;
+            h ^= h >> 15;
+            for (h &= cap - 1;; h = (h + 1) & (cap - 1)) {
+                if (!slot[h]) { verts.insert(verts.end(), k, k + nw); slot[h] = (int)(verts.size() / nw); break; }
+                if (!memcmp(&verts[((size_t)slot[h] - 1) * nw], k, 4 * nw)) break;
+            }
+            face[i] = slot[h] - 1;
+        }
+    } catch (const std::bad_alloc&) { return TF_OOM; }
+    FILE* f = fopen(path, "wb");
+    if (!f) return TF_INVALID_ARG;
+    bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\nelement vertex %zu\n"
+                         "property float x\nproperty float y\nproperty float z\n%s%selement face %lld\n"
+                         "property list uchar int vertex_indices\nend_header\n", verts.size() / nw,
+                      host_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
+                      host_colours ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "", n) > 0;
+    ok = ok && (verts.empty() || fwrite(verts.data(), 4, verts.size(), f) == verts.size());
+    std::vector<unsigned char> rec;
+    try { rec.resize((size_t)n * 13); } catch (const std::bad_alloc&) { fclose(f); return TF_OOM; }
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        rec[13 * i] = 3;
+        memcpy(&rec[13 * i + 1], &face[3 * i], 12);
+    }
+    ok = ok && (rec.empty() || fwrite(rec.data(), 1, rec.size(), f) == rec.size());
+    ok = (fclose(f) == 0) && ok;
+    return ok ? TF_OK : TF_INVALID_ARG;
+}
+
+extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attrs)
+{
+    if (c && path && attrs == 0) return tf_mesh_save_ply(c, path);
+    TF_FLUSH(c);
+    if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS))) return TF_INVALID_ARG;
+    if ((attrs & TF_MESH_COLOURS) && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long n = 0;
+    tf_status s = mesh_count(c, &n);
+    if (s != TF_OK) return s;
+    const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
+    // one allocation each side: positions, then normals, then colours
+    const size_t bt = sizeof(float) * 9 * (size_t)n, bn = nrm ? bt : 0, bc = col ? 12 * (size_t)n : 0;
+    char* dev = nullptr;
+    char* host = nullptr;
+    if (n > 0) {
+        host = (char*)malloc(bt + bn + bc);
+        if (!host) return TF_OOM;
+        if (hipMalloc((void**)&dev, bt + bn + bc) != hipSuccess) { (void)hipGetLastError(); free(host); return TF_OOM; }
+        hipError_t e = tfk_mesh_emit_attr(c, (float*)dev, nrm ? (float*)(dev + bt) : nullptr, col ? (unsigned char*)(dev + bt + bn) : nullptr, n);
+        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, bt + bn + bc, hipMemcpyDeviceToHost, c->stream);
+        s = tf_from_hip(e);
+        const tf_status s2 = sync_checked(c);          // (the stream is idle before the buffer goes)
+        if (s == TF_OK) s = s2;
+        (void)hipFree(dev);
+    }
+    if (s == TF_OK) {
+        // n == 0: the attribute columns are still declared (non-null dummies, never read)
+        static const float none = 0.0f;
+        const float* hn = nrm ? (host ? (const float*)(host + bt) : &none) : nullptr;
+        const uint8_t* hc = col ? (host ? (const uint8_t*)(host + bt + bn) : (const uint8_t*)&none) : nullptr;
+        s = tf_mesh_write_ply_attr(path, (const float*)host, hn, hc, n);
+    }
+    free(host);
+    return s;
+}

@@ -571,5 +571,8 @@ hipError_t tfk_swap(tf_ctx* c, int which = 3);   // 1 in, 2 out, 3 both
 // of the first `capacity` triangles (9 floats each) in entry / voxel / tetrahedron order
 hipError_t tfk_mesh_count(tf_ctx* c);
 hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity);
+// the emit pass with per-vertex attributes: positions (may be nullptr), normals and / or colours (one of
+// the two at least; colours only with the colour plane), clipped at the same capacity
+hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity);
 
 enum { TF_POSE_ALLOC = 1, TF_POSE_RAY = 2, TF_POSE_ALLOC_NOINV = 4 };

@@ -4,6 +4,8 @@
 // compilable as host C++ (the case rules can then be checked without a GPU).
 #pragma once
 
+#include <math.h>
+
 #if defined(__HIPCC__)
 #define TFM_HD __host__ __device__ __forceinline__
 #define TFM_TABLE static __constant__ const
@@ -162,5 +164,118 @@ TFM_HD int tfm_cube_emit(const TfmCube& q, int gx, int gy, int gz, float vs, Emi
     n += tfm_tet_emit<3>(q, m, gx, gy, gz, vs, emit);
     n += tfm_tet_emit<4>(q, m, gx, gy, gz, vs, emit);
     n += tfm_tet_emit<5>(q, m, gx, gy, gz, vs, emit);
+    return n;
+}
+
+// ---- per-vertex attributes (DESIGN.md §Mesh extraction, attributes) ---------------------------------
+// A vertex lies on the edge from the lattice voxel p (the cube corner `lo`) to q (`hi`); its normal and
+// colour are functions of the edge alone (t, and the gradients / colour words at p and q), so every
+// cube and tetrahedron that shares the edge computes the same bits.
+
+// One axis of the integer gradient at a voxel with sdf s0: sm / sp the sdf of the voxel one step down
+// / up the axis, um / up whether that voxel is usable (its block in the hash with ptr >= 0, w > 0).
+// Central where both are, one-sided and doubled where one is, 0 where neither is.  |result| <= 131070.
+TFM_HD int tfm_grad_axis(int sm, int s0, int sp, bool um, bool up)
+{
+    return um ? (up ? sp - sm : 2 * (s0 - sm)) : (up ? 2 * (sp - s0) : 0);
+}
+
+// the same from packed voxels (sdf | w << 16, as the kernels stage them)
+TFM_HD int tfm_grad_axis_packed(unsigned vm, unsigned v0, unsigned vp)
+{
+    return tfm_grad_axis((int)(short)(vm & 0xffffu), (int)(short)(v0 & 0xffffu), (int)(short)(vp & 0xffffu), (vm >> 16) != 0,
+                         (vp >> 16) != 0);
+}
+
+// the interpolation weight of the edge, the float tfm_vertex places the vertex with
+TFM_HD float tfm_edge_t(int sp, int sq) { return (float)sp / (float)(sp - sq); }
+
+// N_a = RN(Gp_a + RN(t (Gq_a - Gp_a))) (the difference in int, exact in float), normalised by
+// L = sqrt(RN(RN(Nx Nx + Ny Ny) + Nz Nz)) with IEEE sqrt and division; (0, 0, 0) when L == 0
+TFM_HD void tfm_normal(float t, const int* gp, const int* gq, float* out)
+{
+    const float nx = (float)gp[0] + t * (float)(gq[0] - gp[0]);
+    const float ny = (float)gp[1] + t * (float)(gq[1] - gp[1]);
+    const float nz = (float)gp[2] + t * (float)(gq[2] - gp[2]);
+    const float l2 = (nx * nx + ny * ny) + nz * nz;
+    const float l = sqrtf(l2);
+    const bool zero = l == 0.0f;
+    out[0] = zero ? 0.0f : nx / l;
+    out[1] = zero ? 0.0f : ny / l;
+    out[2] = zero ? 0.0f : nz / l;
+}
+
+// one channel: RN(cp + RN(t (cq - cp))), then + 0.5 and truncated (the value lies in [0, 255])
+TFM_HD unsigned tfm_colour_channel(float t, int cp, int cq)
+{
+    const float f = (float)cp + t * (float)(cq - cp);
+    return (unsigned)(unsigned char)(int)(f + 0.5f);
+}
+
+// The vertex's RGBA (r | g << 8 | b << 16 | a << 24) from the colour words of the edge's ends
+// (r | g << 8 | b << 16 | w_color << 24; an unusable end is passed as 0).  An end has colour when its
+// w_color > 0: both -> interpolated channels, one -> that end's, none -> 0; alpha 255 unless none.
+TFM_HD unsigned tfm_colour(float t, unsigned wp, unsigned wq)
+{
+    const bool hp = (wp >> 24) != 0, hq = (wq >> 24) != 0;
+    if (hp && hq) {
+        return tfm_colour_channel(t, (int)(wp & 255u), (int)(wq & 255u)) |
+               tfm_colour_channel(t, (int)(wp >> 8 & 255u), (int)(wq >> 8 & 255u)) << 8 |
+               tfm_colour_channel(t, (int)(wp >> 16 & 255u), (int)(wq >> 16 & 255u)) << 16 | 0xff000000u;
+    }
+    if (hp) return (wp & 0xffffffu) | 0xff000000u;
+    if (hq) return (wq & 0xffffffu) | 0xff000000u;
+    return 0u;
+}
+
+// tfm_tet_emit with attributes.  Src gives the lattice data at a cube corner (0..7):
+//   static constexpr bool normals, colours;  void grad(unsigned corner, int g[3]) const;
+//   unsigned colour(unsigned corner) const
+// and emit receives (const float tri[9], const float nrm[9], const unsigned rgba[3]); what Src does not
+// provide is passed as zeros.  Positions, order and count are tfm_tet_emit's.
+template <int K, class Src, class Emit>
+TFM_HD int tfm_tet_emit_attr(const TfmCube& q, unsigned inside8, int gx, int gy, int gz, float vs, const Src& src, Emit& emit)
+{
+    constexpr unsigned corners = tfm_tet_corners(K);
+    const unsigned info = tfm_cases[tfm_tet_case<K>(inside8)];
+    const int n = (int)(info & 3);
+    const bool flip = ((info >> 2 & 1) != 0) != tfm_tet_negative(K);
+    for (int tr = 0; tr < n; ++tr) {
+        float tri[9], nrm[9];
+        unsigned rgba[3];
+        for (int v = 0; v < 3; ++v) {
+            const int w = v == 0 ? 0 : (flip ? 3 - v : v) + tr;
+            const unsigned e = info >> (4 + 4 * w) & 15u;
+            const unsigned lo = corners >> (3 * (e & 3)) & 7u, hi = corners >> (3 * (e >> 2)) & 7u;
+            int sp = q.sdf[0], sq = q.sdf[0];
+            for (int i = 1; i < 8; ++i) { sp = lo == (unsigned)i ? q.sdf[i] : sp; sq = hi == (unsigned)i ? q.sdf[i] : sq; }
+            tfm_vertex(lo, hi, sp, sq, gx, gy, gz, vs, tri + 3 * v);
+            const float t = tfm_edge_t(sp, sq);
+            if (Src::normals) {
+                int gp[3], gq[3];
+                src.grad(lo, gp);
+                src.grad(hi, gq);
+                tfm_normal(t, gp, gq, nrm + 3 * v);
+            } else {
+                nrm[3 * v] = nrm[3 * v + 1] = nrm[3 * v + 2] = 0.0f;
+            }
+            rgba[v] = Src::colours ? tfm_colour(t, src.colour(lo), src.colour(hi)) : 0u;
+        }
+        emit(tri, nrm, rgba);
+    }
+    return n;
+}
+
+template <class Src, class Emit>
+TFM_HD int tfm_cube_emit_attr(const TfmCube& q, int gx, int gy, int gz, float vs, const Src& src, Emit& emit)
+{
+    if (!q.valid) return 0;
+    const unsigned m = tfm_inside_mask(q);
+    int n = tfm_tet_emit_attr<0>(q, m, gx, gy, gz, vs, src, emit);
+    n += tfm_tet_emit_attr<1>(q, m, gx, gy, gz, vs, src, emit);
+    n += tfm_tet_emit_attr<2>(q, m, gx, gy, gz, vs, src, emit);
+    n += tfm_tet_emit_attr<3>(q, m, gx, gy, gz, vs, src, emit);
+    n += tfm_tet_emit_attr<4>(q, m, gx, gy, gz, vs, src, emit);
+    n += tfm_tet_emit_attr<5>(q, m, gx, gy, gz, vs, src, emit);
     return n;
 }

@@ -10,6 +10,9 @@
 //   k_mesh_emit   : the classification again, an exclusive scan over the 512 voxels inside the
 //                   workgroup, triangles written at base + offset while below the caller's capacity
 //
+//   k_mesh_emit_attr<NORMALS, COLOURS> : k_mesh_emit with per-vertex normals (TSDF gradient) and / or colours
+//                   (colour plane) beside the positions, from a larger LDS tile of its own
+//
 // No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) is only read.
 #include "tf_internal.h"
 #include "tf_mesh.h"
@@ -226,6 +229,186 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit(MeshScene s, const long lo
     }
 }
 
+// ---- the emit pass with per-vertex attributes (normals, colours) -------------------------------------
+// Its own kernel beside k_mesh_emit: the larger tile, the gradients and the colour words live in its
+// LDS alone.  Per entry: the 11 x 11 x 11 voxels around the block (local coordinates -1 .. 9; only points
+// with at most one coordinate outside 0 .. 8 are read, the others never are) from the block and up to 19
+// neighbours, the 9 x 9 x 9 integer gradients formed once from it, the colour words of the same 9 x 9 x 9
+// corners; then k_mesh_emit's classification and scan, and per triangle vertex two LDS gradient / colour
+// reads per end.
+#define TFM_ATILE 11
+#define TFM_ATILE3 (TFM_ATILE * TFM_ATILE * TFM_ATILE)
+
+// mesh_block_voff for offsets that also step down: block -32769 does not exist either (blk_walk
+// compares shorts and would wrap)
+__device__ __forceinline__ int mesh_block_voff_attr(const MeshScene& s, int bx, int by, int bz)
+{
+    if (tf_grid_in(bx, by, bz)) return s.v.grid[tf_grid_cell(bx, by, bz)].y;
+    if (bx > 32767 || by > 32767 || bz > 32767 || bx < -32768 || by < -32768 || bz < -32768) return TF_VOFF_NONE;
+    return blk_walk(s.v, bx, by, bz).y;
+}
+
+// tile: sdf | w << 16 at (x + 1) + 11 (y + 1) + 121 (z + 1), x, y, z in -1 .. 9 (NORMALS; else 0 .. 8 only,
+// the rim reads as w = 0); ctile: colour words at x + 9 y + 81 z (COLOURS); nvoff: the 27 block offsets
+// (ox + 1) + 3 (oy + 1) + 9 (oz + 1), those with more than one -1 (without NORMALS: any -1) unused
+template <bool NORMALS, bool COLOURS>
+__device__ __forceinline__ void mesh_stage_attr(const MeshScene& s, const unsigned* __restrict__ rgb, const TfHashEntry& e, unsigned* tile,
+                                                unsigned* ctile, int* nvoff)
+{
+    const int t = threadIdx.x;
+    __syncthreads();             // the previous entry's reads of tile / gradients / ctile / nvoff are done
+    if (t < 27) {
+        const int ox = t % 3 - 1, oy = t / 3 % 3 - 1, oz = t / 9 - 1;
+        const int down = (ox < 0) + (oy < 0) + (oz < 0);
+        int voff = TF_VOFF_NONE;
+        if (t == 13) voff = e.ptr * TF_BLK3;
+        else if (down <= (NORMALS ? 1 : 0)) voff = mesh_block_voff_attr(s, e.x + ox, e.y + oy, e.z + oz);
+        nvoff[t] = voff;
+    }
+    __syncthreads();
+    for (int i = t; i < TFM_ATILE3; i += TFM_WG) {
+        const int zi = i / (TFM_ATILE * TFM_ATILE), r = i - zi * (TFM_ATILE * TFM_ATILE), yi = r / TFM_ATILE, xi = r - yi * TFM_ATILE;
+        const int x = xi - 1, y = yi - 1, z = zi - 1;
+        const int rim = ((unsigned)x > 8u) + ((unsigned)y > 8u) + ((unsigned)z > 8u);
+        unsigned packed = 0u;
+        if (rim <= (NORMALS ? 1 : 0)) {
+            const int voff = nvoff[((x >> 3) + 1) + 3 * ((y >> 3) + 1) + 9 * ((z >> 3) + 1)];
+            const int at = TF_BLK3 + voff + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6);
+            const TfVoxel v = s.v.vba[at];
+            packed = (unsigned)(unsigned short)v.sdf | (unsigned)v.w << 16;
+            if (COLOURS && rim == 0) ctile[x + TFM_TILE * y + TFM_TILE * TFM_TILE * z] = rgb[at];
+        }
+        tile[i] = packed;
+    }
+    __syncthreads();
+}
+
+// this thread's cube from the 11-wide tile
+__device__ __forceinline__ TfmCube mesh_cube_attr(const unsigned* tile)
+{
+    const int t = threadIdx.x, x = t & 7, y = t >> 3 & 7, z = t >> 6;
+    const int b = (x + 1) + TFM_ATILE * (y + 1) + TFM_ATILE * TFM_ATILE * (z + 1);
+    TfmCube q;
+    unsigned wmin = 255u;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const unsigned v = tile[b + (c & 1) + TFM_ATILE * (c >> 1 & 1) + TFM_ATILE * TFM_ATILE * (c >> 2)];
+        q.sdf[c] = (int)(short)(v & 0xffffu);
+        wmin = min(wmin, v >> 16);
+    }
+    q.valid = wmin > 0;
+    return q;
+}
+
+// the lattice data of this thread's cube corners, out of LDS
+template <bool NORMALS, bool COLOURS>
+struct MeshAttrSrc {
+    static constexpr bool normals = NORMALS, colours = COLOURS;
+    const int* grad3;            // [3][TFM_TILE3]
+    const unsigned* ctile;
+    int b;                       // corner 0 at x + 9 y + 81 z
+    __device__ __forceinline__ int at(unsigned c) const { return b + (int)(c & 1) + TFM_TILE * (int)(c >> 1 & 1) + TFM_TILE * TFM_TILE * (int)(c >> 2); }
+    __device__ __forceinline__ void grad(unsigned c, int* g) const
+    {
+        const int i = at(c);
+        g[0] = grad3[i]; g[1] = grad3[TFM_TILE3 + i]; g[2] = grad3[2 * TFM_TILE3 + i];
+    }
+    __device__ __forceinline__ unsigned colour(unsigned c) const { return ctile[at(c)]; }
+};
+
+__device__ __forceinline__ void mesh_store9(float* p, const float* v)
+{
+    tfm_f4 a, b;
+    a.x = v[0]; a.y = v[1]; a.z = v[2]; a.w = v[3];
+    b.x = v[4]; b.y = v[5]; b.z = v[6]; b.w = v[7];
+    *reinterpret_cast<tfm_f4*>(p) = a;
+    *reinterpret_cast<tfm_f4*>(p + 4) = b;
+    p[8] = v[8];
+}
+
+typedef unsigned tfm_u3 __attribute__((ext_vector_type(3), aligned(4)));
+
+template <bool NORMALS, bool COLOURS>
+struct MeshAttrWriter {
+    float* tri;                  // may be nullptr (uniform)
+    float* nrm;
+    unsigned* col;
+    long long idx;
+    long long capacity;
+    __device__ __forceinline__ void operator()(const float* t9, const float* n9, const unsigned* rgba)
+    {
+        if (idx < capacity) {
+            if (tri) mesh_store9(tri + idx * 9, t9);
+            if (NORMALS) mesh_store9(nrm + idx * 9, n9);
+            if (COLOURS) {
+                tfm_u3 c;
+                c.x = rgba[0]; c.y = rgba[1]; c.z = rgba[2];
+                *reinterpret_cast<tfm_u3*>(col + idx * 3) = c;
+            }
+        }
+        ++idx;
+    }
+};
+
+template <bool NORMALS, bool COLOURS>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const unsigned* __restrict__ rgb, const long long* __restrict__ count,
+                                                           const long long* __restrict__ base, float* __restrict__ outTri,
+                                                           float* __restrict__ outNrm, unsigned* __restrict__ outCol, long long capacity,
+                                                           float voxelSize)
+{
+    __shared__ unsigned tile[TFM_ATILE3];
+    __shared__ int grad3[NORMALS ? 3 * TFM_TILE3 : 1];
+    __shared__ unsigned ctile[COLOURS ? TFM_TILE3 : 1];
+    __shared__ int nvoff[27];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ int wsum[TFM_WG / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        __syncthreads();
+        if (t == 0) nlive = 0;
+        __syncthreads();
+        const int idx = g * TFM_WG + t;
+        if (idx < s.n_total && count[idx] > 0 && base[idx] < capacity) live[atomicAdd(&nlive, 1)] = idx;
+        __syncthreads();
+        const int n = nlive;
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            const TfHashEntry e = s.v.hash[ei];
+            mesh_stage_attr<NORMALS, COLOURS>(s, rgb, e, tile, ctile, nvoff);
+            if (NORMALS) {
+                // the 9^3 lattice gradients, once per entry (the tile is complete: mesh_stage_attr ends in a barrier)
+                for (int i = t; i < TFM_TILE3; i += TFM_WG) {
+                    const int z = i / (TFM_TILE * TFM_TILE), r = i - z * (TFM_TILE * TFM_TILE), y = r / TFM_TILE, x = r - y * TFM_TILE;
+                    const int c = (x + 1) + TFM_ATILE * (y + 1) + TFM_ATILE * TFM_ATILE * (z + 1);
+                    const unsigned v0 = tile[c];
+                    grad3[i] = tfm_grad_axis_packed(tile[c - 1], v0, tile[c + 1]);
+                    grad3[TFM_TILE3 + i] = tfm_grad_axis_packed(tile[c - TFM_ATILE], v0, tile[c + TFM_ATILE]);
+                    grad3[2 * TFM_TILE3 + i] = tfm_grad_axis_packed(tile[c - TFM_ATILE * TFM_ATILE], v0, tile[c + TFM_ATILE * TFM_ATILE]);
+                }
+            }
+            const TfmCube q = mesh_cube_attr(tile);
+            const int mine = tfm_cube_count(q);
+            int inc = mine;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            if (lane == 63) wsum[wave] = inc;
+            __syncthreads();         // wsum, and the gradients
+            int off = inc - mine;
+            for (int w = 0; w < wave; ++w) off += wsum[w];
+            if (mine) {
+                const MeshAttrSrc<NORMALS, COLOURS> src = { grad3, ctile, (t & 7) + TFM_TILE * (t >> 3 & 7) + TFM_TILE * TFM_TILE * (t >> 6) };
+                MeshAttrWriter<NORMALS, COLOURS> wr = { outTri, outNrm, outCol, base[ei] + off, capacity };
+                tfm_cube_emit_attr(q, e.x * TF_BLK + (t & 7), e.y * TF_BLK + (t >> 3 & 7), e.z * TF_BLK + (t >> 6), voxelSize, src, wr);
+            }
+        }
+    }
+}
+
 static MeshScene mesh_scene(const tf_ctx* c)
 {
     MeshScene s;
@@ -261,5 +444,24 @@ hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
     const int ng = mesh_groups(c);
     hipLaunchKernelGGL(k_mesh_emit, dim3(ng < TFM_GRID ? ng : TFM_GRID), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount,
                        c->meshBase, triangles, capacity, c->p.voxelSize);
+    return hipGetLastError();
+}
+
+// after tfk_mesh_count on the same stream: positions (may be nullptr), normals and / or colours (at
+// least one of the two; colours need the colour plane), all clipped at the same capacity
+hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity)
+{
+    const int ng = mesh_groups(c);
+    const dim3 grid(ng < TFM_GRID ? ng : TFM_GRID), wg(TFM_WG);
+    unsigned* col = reinterpret_cast<unsigned*>(colours);
+    if (normals && colours)
+        hipLaunchKernelGGL((k_mesh_emit_attr<true, true>), grid, wg, 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount, c->meshBase,
+                           triangles, normals, col, capacity, c->p.voxelSize);
+    else if (normals)
+        hipLaunchKernelGGL((k_mesh_emit_attr<true, false>), grid, wg, 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount, c->meshBase,
+                           triangles, normals, col, capacity, c->p.voxelSize);
+    else
+        hipLaunchKernelGGL((k_mesh_emit_attr<false, true>), grid, wg, 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount, c->meshBase,
+                           triangles, normals, col, capacity, c->p.voxelSize);
     return hipGetLastError();
 }

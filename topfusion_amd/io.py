@@ -71,13 +71,24 @@ def read_sequence(depth_pattern, first=0, count=None):
     return np.stack(out) if out else np.zeros((0, 0, 0), np.uint16)
 
 
-def write_ply(path, tris):
+def write_ply(path, tris, normals=None, colours=None):
     """Triangles (n, 3, 3) float32 as a binary little-endian PLY, vertices welded by exact bit
-    equality (tf_mesh_write_ply, the writer TopFu.save_mesh uses)."""
+    equality (tf_mesh_write_ply, the writer TopFu.save_mesh uses).  normals (n, 3, 3) float32 and
+    colours (n, 3, 4) uint8 RGBA, when given, become the vertex properties nx ny nz and red green blue
+    alpha, and vertices weld on the whole record (tf_mesh_write_ply_attr)."""
     import ctypes
     from . import _lib as L
     t = np.ascontiguousarray(tris, np.float32).reshape(-1, 3, 3)
-    L.check(L.load().tf_mesh_write_ply(str(path).encode(), t.ctypes.data_as(ctypes.c_void_p), len(t)), "tf_mesh_write_ply")
+    if normals is None and colours is None:
+        L.check(L.load().tf_mesh_write_ply(str(path).encode(), t.ctypes.data_as(ctypes.c_void_p), len(t)), "tf_mesh_write_ply")
+        return
+    nr = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3, 3)
+    co = None if colours is None else np.ascontiguousarray(colours, np.uint8).reshape(-1, 3, 4)
+    for a in (nr, co):
+        if a is not None and len(a) != len(t):
+            raise ValueError("attributes and triangles differ in length")
+    vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    L.check(L.load().tf_mesh_write_ply_attr(str(path).encode(), vp(t), vp(nr), vp(co), len(t)), "tf_mesh_write_ply_attr")
 
 
 def read_ply(path):
@@ -103,3 +114,45 @@ def read_ply(path):
     if nf and not (rec["n"] == 3).all():
         raise ValueError("PLY face that is not a triangle")
     return verts, rec["v"].astype(np.int32)
+
+
+def read_ply_attr(path):
+    """(vertices (m, 3) float32, faces (n, 3) int32, normals (m, 3) float32 or None, colours (m, 4)
+    uint8 RGBA or None) of a PLY as write_ply writes it, by the header's property list."""
+    buf = open(path, "rb").read()
+    end = buf.find(b"end_header\n")
+    if not buf.startswith(b"ply\nformat binary_little_endian 1.0\n") or end < 0:
+        raise ValueError("not a binary little-endian PLY")
+    types = {b"float": "<f4", b"uchar": "u1", b"int": "<i4"}
+    nv = nf = None
+    element, props = None, []
+    for line in buf[:end].split(b"\n"):
+        f = line.split()
+        if f[:1] == [b"element"]:
+            element = f[1]
+            if element == b"vertex":
+                nv = int(f[2])
+            elif element == b"face":
+                nf = int(f[2])
+        elif f[:1] == [b"property"] and element == b"vertex":
+            if f[1] not in types:
+                raise ValueError("PLY vertex property of an unknown type")
+            props.append((f[2].decode(), types[f[1]]))
+    if nv is None or nf is None:
+        raise ValueError("PLY header without vertex / face elements")
+    vdt = np.dtype(props)
+    names = vdt.names or ()
+    if names[:3] != ("x", "y", "z"):
+        raise ValueError("PLY vertices without x y z")
+    off = end + len(b"end_header\n")
+    if len(buf) != off + vdt.itemsize * nv + 13 * nf:
+        raise ValueError("PLY body size does not match its header")
+    v = np.frombuffer(buf, vdt, nv, off)
+    cols = lambda ns, dt: np.stack([v[k] for k in ns], -1).astype(dt) if nv else np.zeros((0, len(ns)), dt)
+    verts = cols(("x", "y", "z"), np.float32)
+    normals = cols(("nx", "ny", "nz"), np.float32) if all(k in names for k in ("nx", "ny", "nz")) else None
+    colours = cols(("red", "green", "blue", "alpha"), np.uint8) if all(k in names for k in ("red", "green", "blue", "alpha")) else None
+    rec = np.frombuffer(buf, np.dtype([("n", "u1"), ("v", "<i4", 3)]), nf, off + vdt.itemsize * nv)
+    if nf and not (rec["n"] == 3).all():
+        raise ValueError("PLY face that is not a triangle")
+    return verts, rec["v"].astype(np.int32), normals, colours

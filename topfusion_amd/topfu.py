@@ -352,9 +352,44 @@ class TopFu:
             hip.hipFree(dev)
         return out
 
-    def save_mesh(self, path):
-        """The mesh as a binary PLY with welded vertices (tf_mesh_save_ply)."""
-        L.check(L.load().tf_mesh_save_ply(self._h, str(path).encode()), "tf_mesh_save_ply")
+    def mesh_attr(self, normals=True, colours=False):
+        """mesh() with per-vertex attributes (tf_mesh_extract_attr): (triangles (n, 3, 3) float32,
+        normals (n, 3, 3) float32 or None, colours (n, 3, 4) uint8 RGBA or None), the same triangles
+        in the same order.  Normals are the normalised TSDF gradient (towards free space), colours
+        come from the colour plane (voxel_rgb contexts only)."""
+        n = self.mesh_count()
+        outs = [np.empty((n, 3, 3), np.float32), np.empty((n, 3, 3), np.float32) if normals else None,
+                np.empty((n, 3, 4), np.uint8) if colours else None]
+        if n == 0 and not (colours and not self.params_.voxel_rgb):     # (that one is the library's TF_INVALID_ARG)
+            return tuple(outs)
+        hip = L.hip_runtime()
+        devs = []
+        try:
+            for o in outs:
+                d = ctypes.c_void_p()
+                if o is not None and hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(max(o.nbytes, 16))) != 0:
+                    raise L.TfError(L.TF_OOM, "hipMalloc (mesh)")
+                devs.append(d)
+            m = ctypes.c_longlong()
+            L.check(L.load().tf_mesh_extract_attr(self._h, devs[0], devs[1], devs[2], n, ctypes.byref(m)), "tf_mesh_extract_attr")
+            assert m.value == n, (m.value, n)
+            for o, d in zip(outs, devs):
+                if o is not None and n and hip.hipMemcpy(_ptr(o), d, ctypes.c_size_t(o.nbytes), 2) != 0:   # hipMemcpyDeviceToHost
+                    raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (mesh)")
+        finally:
+            for d in devs:
+                if d:
+                    hip.hipFree(d)
+        return tuple(outs)
+
+    def save_mesh(self, path, normals=False, colours=False):
+        """The mesh as a binary PLY with welded vertices (tf_mesh_save_ply); with normals / colours,
+        nx ny nz / red green blue alpha per vertex (tf_mesh_save_ply_attr)."""
+        if not normals and not colours:
+            L.check(L.load().tf_mesh_save_ply(self._h, str(path).encode()), "tf_mesh_save_ply")
+            return
+        attrs = (L.TF_MESH_NORMALS if normals else 0) | (L.TF_MESH_COLOURS if colours else 0)
+        L.check(L.load().tf_mesh_save_ply_attr(self._h, str(path).encode(), attrs), "tf_mesh_save_ply_attr")
 
     # typed views
     def hash(self):
