@@ -9,6 +9,7 @@
 //   ./demo_headless --pgm 'dir/%04d.pgm' [--ppm 'dir/%04d.ppm'] [max_frames]
 //   ... --mesh out.ply : the reconstructed surface after the last frame (TopFu::saveMesh)
 //   ... --mesh-normals : with per-vertex normals (nx ny nz) in that PLY
+//   ... --mesh-indexed : the indexed vertex table as the GPU extracts it, no host weld
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -17,6 +18,7 @@
 #include <cstring>
 #include <string>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -28,13 +30,14 @@ using namespace tfusion;
 int main(int argc, char** argv)
 {
     std::string pgm, ppm, mesh;
-    bool mesh_normals = false;
+    bool mesh_normals = false, mesh_indexed = false;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--pgm") && i + 1 < argc) pgm = argv[++i];
         else if (!std::strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
+        else if (!std::strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
         else pos.push_back(argv[i]);
     }
     int frames = pos.size() > 0 ? std::atoi(pos[0]) : (pgm.empty() ? 100 : 1 << 30);
@@ -95,7 +98,19 @@ int main(int argc, char** argv)
     std::printf("frames %d ok %d resets %d visible %d  pose t = (%.4f %.4f %.4f)\n", n, n_ok, st.n_resets,
                 st.noVisibleEntries, pose.translation()[0], pose.translation()[1], pose.translation()[2]);
     if (!mesh.empty()) {
-        if (mesh_normals) topfu->saveMesh(mesh, TF_MESH_NORMALS);
+        if (mesh_indexed) {
+            topfu->saveMesh(mesh, TF_MESH_INDEXED | (mesh_normals ? TF_MESH_NORMALS : 0));
+            // the same mesh through extractMeshIndexed: the file's vertices and faces, and no index past the table
+            cuda::DeviceArray<float> vertices;
+            cuda::DeviceArray<unsigned> indices;
+            const long long nt = topfu->extractMeshIndexed(vertices, indices);
+            std::vector<unsigned> idx;
+            indices.download(idx);
+            unsigned top = 0;
+            for (unsigned i : idx) top = std::max(top, i);
+            std::printf("indexed mesh: %zu vertices, %lld triangles, highest index %u\n", vertices.size() / 3, nt, top);
+        }
+        else if (mesh_normals) topfu->saveMesh(mesh, TF_MESH_NORMALS);
         else topfu->saveMesh(mesh);
         std::printf("mesh written to %s\n", mesh.c_str());
     }

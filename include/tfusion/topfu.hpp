@@ -280,7 +280,32 @@ namespace tfusion
             return n;
         }
         // the mesh as a PLY with nx ny nz (TF_MESH_NORMALS) and / or red green blue alpha (TF_MESH_COLOURS)
-        void saveMesh(const std::string& path, int attrs) { check(tf_mesh_save_ply_attr(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_attr"); }
+        // with TF_MESH_INDEXED: the indexed vertex table as it leaves the GPU, no host weld (tf_mesh_save_ply_indexed)
+        void saveMesh(const std::string& path, int attrs)
+        {
+            if (attrs & TF_MESH_INDEXED) check(tf_mesh_save_ply_indexed(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_indexed");
+            else check(tf_mesh_save_ply_attr(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_attr");
+        }
+        // The mesh with shared vertices (tf_mesh_extract_indexed): 3 floats per vertex, 3 vertex numbers per
+        // triangle (extractMesh's triangles in its order), and per vertex 3 normal floats / 4 RGBA bytes where
+        // the pointer is not null; all resized to fit.  Returns the triangle count; vertices.size() / 3 is
+        // the vertex count.
+        long long extractMeshIndexed(cuda::DeviceArray<float>& vertices, cuda::DeviceArray<unsigned>& indices,
+                                     cuda::DeviceArray<float>* normals = nullptr, cuda::DeviceArray<unsigned char>* colours = nullptr)
+        {
+            long long nv = 0, nt = 0;
+            check(tf_mesh_extract_indexed(ctx_, nullptr, nullptr, nullptr, 0, nullptr, 0, &nv, &nt), "tf_mesh_extract_indexed");
+            vertices.create((size_t)nv * 3);
+            indices.create((size_t)nt * 3);
+            if (normals) normals->create((size_t)nv * 3);
+            if (colours) colours->create((size_t)nv * 4);
+            if (nt > 0) {
+                long long mv = 0, mt = 0;
+                check(tf_mesh_extract_indexed(ctx_, vertices.ptr(), normals ? normals->ptr() : nullptr, colours ? colours->ptr() : nullptr, nv,
+                                              indices.ptr(), nt, &mv, &mt), "tf_mesh_extract_indexed");
+            }
+            return nt;
+        }
 
         tf_ctx* handle() { return ctx_; }
         hipStream_t stream() const { return (hipStream_t)tf_get_stream(ctx_); }

@@ -44,7 +44,8 @@ typedef enum tf_status {
     TF_INVALID_ARG = 2,
     TF_OOM = 3,
     TF_HIP_ERROR = 4,
-    TF_NO_DEVICE = 5
+    TF_NO_DEVICE = 5,
+    TF_INDEX_RANGE = 6      /* tf_mesh_extract_indexed: the mesh has more than 2^32 - 1 vertices, nothing written */
 } tf_status;
 
 /* TopFuParams (tfusion/include/tfusion/topfu.hpp:28-60) restricted to the fields the
@@ -479,6 +480,37 @@ tf_status tf_mesh_write_ply_attr(const char* path, const float* host_triangles, 
  * tf_mesh_write_ply_attr; attrs = TF_MESH_NORMALS | TF_MESH_COLOURS or either or 0; TF_OOM when the
  * buffers cannot be had, TF_INVALID_ARG for TF_MESH_COLOURS without voxel_rgb */
 tf_status tf_mesh_save_ply_attr(tf_ctx* ctx, const char* path, int attrs);
+
+/* The indexed form (Mesh extraction, indexed): the same triangles with shared vertices.  A vertex
+ * is the cube edge it lies on -- (p, d), p the edge's lower voxel, d in {0,1}^3 \ {0} -- and exists when a
+ * triangle of tf_mesh_extract has a vertex there; two edges are never merged, even where their positions
+ * are equal bit for bit, and no vertex is unreferenced.  Vertices are numbered by ascending hash entry of
+ * p's block, then p's voxel index x + 8y + 64z in it, then dx | dy << 1 | dz << 2. */
+#define TF_MESH_INDEXED 4
+/* addition (no reference counterpart): the vertex table -- positions float[nv][3], unit normals float[nv][3],
+ * colours uint8[nv][4] RGBA (voxel_rgb contexts only), each skipped when its pointer is NULL and clipped at
+ * vertex_capacity -- and indices uint32[nt][3], clipped at triangle_capacity, for tf_mesh_extract's triangles
+ * in its order: vertices[indices] is tf_mesh_extract's float[nt][9] bit for bit, and normals / colours
+ * [indices] are tf_mesh_extract_attr's.  An index keeps its true value even when it points past
+ * vertex_capacity.  *n_vertices and *n_triangles are always the full counts.  A capacity of 0 (its buffers may
+ * be NULL) writes nothing of that part; both 0 only counts.  TF_INVALID_ARG: a negative capacity, a non-zero
+ * capacity with its buffers NULL, a NULL count pointer or ctx, dev_colours without voxel_rgb.
+ * TF_INDEX_RANGE: more than 2^32 - 1 vertices -- the counts are returned, nothing is written.  TF_OOM when the
+ * scratch (448 B of edge bits and as much of prefixes per VBA block, allocated by the first call and kept
+ * by the context) cannot be had.  Two extractions of one scene are byte-identical.  Synchronous; the scene
+ * is only read. */
+tf_status tf_mesh_extract_indexed(tf_ctx* ctx, float* dev_vertices, float* dev_normals, uint8_t* dev_colours,
+                                  long long vertex_capacity, uint32_t* dev_indices, long long triangle_capacity,
+                                  long long* n_vertices, long long* n_triangles);
+/* addition (no reference counterpart): host only, no context -- the vertex table as given (no welding, order
+ * and duplicate positions kept) and nt faces as a binary little-endian PLY with tf_mesh_write_ply_attr's
+ * property layout and face format.  TF_INVALID_ARG also for nv > 2^31 - 1 or an index >= nv. */
+tf_status tf_mesh_write_ply_indexed(const char* path, const float* host_vertices, const float* host_normals,
+                                    const uint8_t* host_colours, long long nv, const uint32_t* host_indices, long long nt);
+/* addition (no reference counterpart): count, extract the indexed buffers into a temporary device buffer,
+ * download them (and nothing else), tf_mesh_write_ply_indexed; attrs as tf_mesh_save_ply_attr's
+ * (TF_MESH_INDEXED may be set and changes nothing); TF_INDEX_RANGE beyond 2^31 - 1 vertices */
+tf_status tf_mesh_save_ply_indexed(tf_ctx* ctx, const char* path, int attrs);
 
 #ifdef __cplusplus
 }

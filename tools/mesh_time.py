@@ -19,7 +19,13 @@ context's own positions-only time.  Floor: live blocks x 2 KiB per pass + (36 + 
 for what is written.  --parent-lib PATH (a libtfusion_hip.so built from the parent commit) runs the
 plain measurement once more in a child process on that library and records its positions-only time.
 
-    python tools/mesh_time.py [--frames 32] [--reps 20] [--warmup 3] [--attr] [--parent-lib PATH]
+--indexed adds tf_mesh_extract_indexed on the same window, in the same run: the count passes alone, then
+positions, positions + normals, and (on the voxel_rgb context) all attributes, each beside the soup
+extraction of the same outputs timed in this run, with the bytes each form writes -- what a caller then
+downloads.  Floor: live blocks x 2 KiB per pass (count, mark, vertices, indices) + 448 B of edge bits per
+VBA block cleared + 12 B per triangle + (12 + 12 + 4) B per vertex for what is written.
+
+    python tools/mesh_time.py [--frames 32] [--reps 20] [--warmup 3] [--attr] [--indexed] [--parent-lib PATH]
 """
 import argparse
 import ctypes
@@ -44,6 +50,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--attr", action="store_true", help="also time tf_mesh_extract_attr")
+    ap.add_argument("--indexed", action="store_true", help="also time tf_mesh_extract_indexed beside the soup calls")
     ap.add_argument("--parent-lib", default=None, help="a parent-commit libtfusion_hip.so to time positions-only extraction on")
     args = ap.parse_args()
 
@@ -90,6 +97,10 @@ def main():
     attr = {}
     if args.attr:
         attr = time_attr(args, tf, n, live, dev, timed_call, full_ms)
+    if args.indexed:
+        idx = time_indexed(args, tf, n, live, dev, timed_call, full_ms)
+        attr.setdefault("lines", []).extend(idx.pop("lines"))
+        attr.update(idx)
     hip.hipFree(dev)
     hip.hipEventDestroy(e0)
     hip.hipEventDestroy(e1)
@@ -160,14 +171,7 @@ def time_attr(args, tf, n, live, dev_tris, timed_call, full_ms):
     ms, mn = timed_call(attr_call(tf, dev_tris, dev_nrm, None))
     report("pos_normals", "positions + normals    ", ms, mn, 72, full_ms)
 
-    # the colour context: the same depth frames, the colour tests' RGB stream (a registered colour camera)
-    fx, fy, cx, cy = synth.intrinsics(W, H)
-    tc = TopFu(default_params(cols=W, rows=H, fx=fx, fy=fy, cx=cx, cy=cy, voxel_rgb=1), device=0)
-    frames = synth.orbit_device(args.frames, W, H, seed=7)
-    rgbs = np.stack([synth.render_colour(*synth.orbit_pose(k), W, H) for k in range(args.frames)])
-    dev_rgb = dev_alloc(rgbs.nbytes)
-    assert hip.hipMemcpy(dev_rgb, rgbs.ctypes.data_as(ctypes.c_void_p), rgbs.nbytes, 1) == 0
-    tc.process_frames(frames.ptr, args.frames, rgb_frames=dev_rgb.value)
+    tc = colour_context(args)
     nc = tc.mesh_count()
     assert nc <= n, (nc, n)                                    # (the buffers hold n; colour does not move the geometry)
     plane = tc.vba_rgb()
@@ -177,9 +181,90 @@ def time_attr(args, tf, n, live, dev_tris, timed_call, full_ms):
     lines.append(f"colour context ({nc} triangles), positions only (tf_mesh_extract): {ms_pos:.3f} ms")
     ms, mn = timed_call(attr_call(tc, dev_tris, dev_nrm, dev_col), nc)
     report("all", "positions + normals + colours", ms, mn, 84, ms_pos, nc)
-    for d in (dev_nrm, dev_col, dev_rgb):
+    for d in (dev_nrm, dev_col):
         hip.hipFree(d)
+    tc.close()
+    fields["lines"] = lines
+    return fields
+
+
+def colour_context(args):
+    """A voxel_rgb context fused with the same depth frames and the colour tests' RGB stream (a registered
+    colour camera)."""
+    from topfusion_amd import TopFu, default_params, synth, _lib as L
+    hip = L.hip_runtime()
+    W, H = args.cols, args.rows
+    fx, fy, cx, cy = synth.intrinsics(W, H)
+    tc = TopFu(default_params(cols=W, rows=H, fx=fx, fy=fy, cx=cx, cy=cy, voxel_rgb=1), device=0)
+    frames = synth.orbit_device(args.frames, W, H, seed=7)
+    rgbs = np.stack([synth.render_colour(*synth.orbit_pose(k), W, H) for k in range(args.frames)])
+    dev_rgb = ctypes.c_void_p()
+    assert hip.hipMalloc(ctypes.byref(dev_rgb), rgbs.nbytes) == 0, "hipMalloc"
+    assert hip.hipMemcpy(dev_rgb, rgbs.ctypes.data_as(ctypes.c_void_p), rgbs.nbytes, 1) == 0
+    tc.process_frames(frames.ptr, args.frames, rgb_frames=dev_rgb.value)
+    tc.mesh_count()                                           # (synchronises: the frames are done with their inputs)
+    hip.hipFree(dev_rgb)
     frames.free()
+    return tc
+
+
+def time_indexed(args, tf, n, live, dev_tris, timed_call, full_ms):
+    """tf_mesh_extract_indexed beside the soup calls with the same outputs: count only, positions, positions +
+    normals on `tf`; all attributes on a voxel_rgb context.  Returns the JSON fields and the printed lines."""
+    from topfusion_amd import _lib as L
+    lib, hip = L.load(), L.hip_runtime()
+
+    def dev_alloc(nbytes):
+        d = ctypes.c_void_p()
+        assert hip.hipMalloc(ctypes.byref(d), max(16, nbytes)) == 0, "hipMalloc"
+        return d
+
+    nv, nt = tf.mesh_indexed_count()
+    assert nt == n
+    dev_v, dev_vn, dev_vc, dev_i = dev_alloc(nv * 12), dev_alloc(nv * 12), dev_alloc(nv * 4), dev_alloc(nt * 12)
+    dev_nrm, dev_col = dev_alloc(n * 36), dev_alloc(n * 12)
+    n_blocks = tf.params_.n_blocks
+    gbs = lambda b, ms: b / (ms * 1e-3) / 1e9
+    fields, lines = {"indexed_vertices": nv, "indexed_triangles": nt}, []
+    lines.append(f"indexed: {nv} vertices, {nt} triangles ({3 * nt / nv:.2f} triangle corners per vertex)")
+
+    def indexed_call(ctx, v, vn, vc, vcap, i, icap, want_nv):
+        def call(got):
+            gv = ctypes.c_longlong()
+            L.check(lib.tf_mesh_extract_indexed(ctx._h, v, vn, vc, vcap, i, icap, ctypes.byref(gv), ctypes.byref(got)),
+                    "tf_mesh_extract_indexed")
+            assert gv.value == want_nv
+        return call
+
+    def report(key, label, ms, mn, soup_ms, per_vertex, per_tri_soup, verts, tris):
+        written, soup = 12 * tris + per_vertex * verts, per_tri_soup * tris
+        floor = 4 * live * 2048 + n_blocks * 448 + written
+        fields.update({f"indexed_{key}_ms": round(ms, 4), f"indexed_{key}_ms_min": round(mn, 4), f"soup_{key}_ms": round(soup_ms, 4),
+                       f"indexed_{key}_bytes": written, f"soup_{key}_bytes": soup, f"floor_bytes_indexed_{key}": floor,
+                       f"indexed_{key}_gbs": round(gbs(floor, ms), 2)})
+        lines.append(f"indexed {label}: {ms:.3f} ms against the soup's {soup_ms:.3f} ms ({ms / soup_ms:.2f} x); bytes written "
+                     f"{written} against {soup} ({written / tris:.1f} against {per_tri_soup} B per triangle, {written / soup:.2f} x); "
+                     f"{fields[f'indexed_{key}_gbs']} GB/s of the floor's bytes, {100 * gbs(floor, ms) / PEAK_HBM_GBS:.2f} % of peak")
+
+    ms, mn = timed_call(indexed_call(tf, None, None, None, 0, None, 0, nv))
+    fields.update({"indexed_count_ms": round(ms, 4), "indexed_count_ms_min": round(mn, 4)})
+    lines.append(f"indexed count only (triangle count + edge marks + vertex count): {ms:.3f} ms")
+    ms, mn = timed_call(indexed_call(tf, dev_v, None, None, nv, dev_i, nt, nv))
+    report("pos", "positions            ", ms, mn, full_ms, 12, 36, nv, nt)
+    soup_ms, _ = timed_call(lambda got: L.check(lib.tf_mesh_extract_attr(tf._h, dev_tris, dev_nrm, None, n, ctypes.byref(got)),
+                                                "tf_mesh_extract_attr"))
+    ms, mn = timed_call(indexed_call(tf, dev_v, dev_vn, None, nv, dev_i, nt, nv))
+    report("pos_normals", "positions + normals  ", ms, mn, soup_ms, 24, 72, nv, nt)
+
+    tc = colour_context(args)
+    cv, ct = tc.mesh_indexed_count()
+    assert ct <= n and cv <= nv, (ct, n, cv, nv)             # (the buffers hold n / nv; colour does not move the geometry)
+    soup_ms, _ = timed_call(lambda got: L.check(lib.tf_mesh_extract_attr(tc._h, dev_tris, dev_nrm, dev_col, n, ctypes.byref(got)),
+                                                "tf_mesh_extract_attr"), ct)
+    ms, mn = timed_call(indexed_call(tc, dev_v, dev_vn, dev_vc, nv, dev_i, nt, cv), ct)
+    report("all", "all attributes       ", ms, mn, soup_ms, 28, 84, cv, ct)
+    for d in (dev_v, dev_vn, dev_vc, dev_i, dev_nrm, dev_col):
+        hip.hipFree(d)
     tc.close()
     fields["lines"] = lines
     return fields

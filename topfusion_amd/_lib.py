@@ -14,7 +14,9 @@ LIB_PATH = os.environ.get("TFUSION_HIP_LIB") or os.path.join(_HERE, "libtfusion_
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tfusion_hip.h")
 
 TF_OK, TF_ICP_FAIL, TF_INVALID_ARG, TF_OOM, TF_HIP_ERROR, TF_NO_DEVICE = range(6)
+TF_INDEX_RANGE = 6                             # tf_mesh_extract_indexed: more vertices than a u32 numbers
 TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2        # tf_mesh_save_ply_attr's attrs
+TF_MESH_INDEXED = 4
 
 STAGE_NAMES = ("preprocess", "icp", "alloc", "integrate", "raycast_render", "grey", "expected_depths",
                "raycast_icp", "icp_maps")
@@ -177,6 +179,10 @@ def load():
         "tf_mesh_extract_attr": ([P, P, P, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)], I),
         "tf_mesh_write_ply_attr": ([ctypes.c_char_p, P, P, P, ctypes.c_longlong], I),
         "tf_mesh_save_ply_attr": ([P, ctypes.c_char_p, I], I),
+        "tf_mesh_extract_indexed": ([P, P, P, P, ctypes.c_longlong, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong),
+                                     ctypes.POINTER(ctypes.c_longlong)], I),
+        "tf_mesh_write_ply_indexed": ([ctypes.c_char_p, P, P, P, ctypes.c_longlong, P, ctypes.c_longlong], I),
+        "tf_mesh_save_ply_indexed": ([P, ctypes.c_char_p, I], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():

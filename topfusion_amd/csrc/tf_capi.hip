@@ -36,6 +36,7 @@ extern "C" const char* tf_status_string(tf_status s)
     case TF_OOM: return "out of device memory";
     case TF_HIP_ERROR: return "HIP error";
     case TF_NO_DEVICE: return "no HIP device";
+    case TF_INDEX_RANGE: return "more mesh vertices than a 32-bit index can number";
     }
     return "unknown";
 }
@@ -155,7 +156,7 @@ static void ctx_free(tf_ctx* c)
                      c->blockRec, c->blockTiles, c->blockOff, c->edChunk, c->edSpill, c->edBins, c->edBinCnt, c->edDone, c->depth_in, c->dists, c->icp_partial, c->icp_ticket, c->icp_tagged, c->st,
                      c->swapState, c->swapFlags, c->swapStore, c->swapCounts,
                      c->vba_rgb_guard, c->rgb_in, c->integ_cnt, c->fuse_pose, c->fuse_rec, c->fuse_dists, c->tile_cost, c->tile_order,
-                     c->meshCount, c->meshBase };
+                     c->meshCount, c->meshBase, c->meshMask, c->meshWPre, c->meshVCount, c->meshVBase };
     for (void* b : bufs) if (b) (void)hipFree(b);
     // pyramid maps: one allocation per map (level 0 is the base; swaps keep levels together)
     float4* maps[4] = { c->curr_pts[0], c->curr_nrm[0], c->prev_pts[0], c->prev_nrm[0] };
@@ -1813,6 +1814,113 @@ extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attr
         const float* hn = nrm ? (host ? (const float*)(host + bt) : &none) : nullptr;
         const uint8_t* hc = col ? (host ? (const uint8_t*)(host + bt + bn) : (const uint8_t*)&none) : nullptr;
         s = tf_mesh_write_ply_attr(path, (const float*)host, hn, hc, n);
+    }
+    free(host);
+    return s;
+}
+
+// ---- indexed mesh extraction (additions; DESIGN.md §Mesh extraction, indexed) ---------------------------
+// triangle and vertex totals after the count passes
+static tf_status mesh_index_count(tf_ctx* c, long long* nv, long long* nt)
+{
+    const hipError_t e = tfk_mesh_index_count(c);
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return TF_OOM; }
+    TF_CHECK(e);
+    TF_CHECK(hipMemcpyAsync(nt, c->meshBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipMemcpyAsync(nv, c->meshVBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    return sync_checked(c);
+}
+
+extern "C" tf_status tf_mesh_extract_indexed(tf_ctx* c, float* dev_vertices, float* dev_normals, uint8_t* dev_colours,
+                                             long long vertex_capacity, uint32_t* dev_indices, long long triangle_capacity,
+                                             long long* n_vertices, long long* n_triangles)
+{
+    TF_FLUSH(c);
+    const bool any = dev_vertices || dev_normals || dev_colours;
+    if (!c || !n_vertices || !n_triangles || vertex_capacity < 0 || triangle_capacity < 0) return TF_INVALID_ARG;
+    if ((vertex_capacity > 0 && !any) || (triangle_capacity > 0 && !dev_indices)) return TF_INVALID_ARG;
+    if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long nv = 0, nt = 0;
+    tf_status s = mesh_index_count(c, &nv, &nt);
+    if (s != TF_OK) return s;
+    *n_vertices = nv;
+    *n_triangles = nt;
+    if (nv > 0xffffffffLL) return TF_INDEX_RANGE;
+    const bool verts = any && vertex_capacity > 0 && nv > 0, tris = dev_indices && triangle_capacity > 0 && nt > 0;
+    if (!verts && !tris) return TF_OK;
+    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
+    if (verts) TF_CHECK(tfk_mesh_emit_vertices(c, dev_vertices, dev_normals, dev_colours, vertex_capacity));
+    if (tris) TF_CHECK(tfk_mesh_emit_indices(c, dev_indices, triangle_capacity));
+    return sync_checked(c);
+}
+
+// the vertex table as given (no welding): records of 3 (+ 3) (+ 1) dwords, then the attributed writer's faces
+extern "C" tf_status tf_mesh_write_ply_indexed(const char* path, const float* host_vertices, const float* host_normals,
+                                               const uint8_t* host_colours, long long nv, const uint32_t* host_indices, long long nt)
+{
+    if (!path || nv < 0 || nt < 0 || (nv > 0 && !host_vertices) || (nt > 0 && !host_indices) || nv > 0x7fffffffLL) return TF_INVALID_ARG;
+    for (long long i = 0; i < 3 * nt; ++i)
+        if ((long long)host_indices[i] >= nv) return TF_INVALID_ARG;
+    const size_t nw = 3 + (host_normals ? 3 : 0) + (host_colours ? 1 : 0);      // dwords per record
+    std::vector<uint32_t> verts;
+    std::vector<unsigned char> rec;
+    try { verts.resize((size_t)nv * nw); rec.resize((size_t)nt * 13); } catch (const std::bad_alloc&) { return TF_OOM; }
+    for (size_t i = 0; i < (size_t)nv; ++i) {
+        uint32_t* k = &verts[i * nw];
+        memcpy(k, host_vertices + 3 * i, 12);
+        size_t w = 3;
+        if (host_normals) { memcpy(k + w, host_normals + 3 * i, 12); w += 3; }
+        if (host_colours) memcpy(k + w, host_colours + 4 * i, 4);
+    }
+    for (size_t i = 0; i < (size_t)nt; ++i) {
+        rec[13 * i] = 3;
+        memcpy(&rec[13 * i + 1], host_indices + 3 * i, 12);
+    }
+    FILE* f = fopen(path, "wb");
+    if (!f) return TF_INVALID_ARG;
+    bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\nelement vertex %lld\n"
+                         "property float x\nproperty float y\nproperty float z\n%s%selement face %lld\n"
+                         "property list uchar int vertex_indices\nend_header\n", nv,
+                      host_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
+                      host_colours ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "", nt) > 0;
+    ok = ok && (verts.empty() || fwrite(verts.data(), 4, verts.size(), f) == verts.size());
+    ok = ok && (rec.empty() || fwrite(rec.data(), 1, rec.size(), f) == rec.size());
+    ok = (fclose(f) == 0) && ok;
+    return ok ? TF_OK : TF_INVALID_ARG;
+}
+
+extern "C" tf_status tf_mesh_save_ply_indexed(tf_ctx* c, const char* path, int attrs)
+{
+    TF_FLUSH(c);
+    if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS | TF_MESH_INDEXED))) return TF_INVALID_ARG;
+    if ((attrs & TF_MESH_COLOURS) && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long nv = 0, nt = 0;
+    tf_status s = mesh_index_count(c, &nv, &nt);
+    if (s != TF_OK) return s;
+    if (nv > 0x7fffffffLL) return TF_INDEX_RANGE;       // (the PLY's indices are int)
+    const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
+    // one allocation each side: positions, normals, colours, indices
+    const size_t bp = 12 * (size_t)nv, bn = nrm ? bp : 0, bc = col ? 4 * (size_t)nv : 0, bi = 12 * (size_t)nt, all = bp + bn + bc + bi;
+    char* dev = nullptr;
+    char* host = nullptr;
+    if (nt > 0) {
+        host = (char*)malloc(all);
+        if (!host) return TF_OOM;
+        if (hipMalloc((void**)&dev, all) != hipSuccess) { (void)hipGetLastError(); free(host); return TF_OOM; }
+        hipError_t e = tfk_mesh_emit_vertices(c, (float*)dev, nrm ? (float*)(dev + bp) : nullptr, col ? (unsigned char*)(dev + bp + bn) : nullptr, nv);
+        if (e == hipSuccess) e = tfk_mesh_emit_indices(c, (unsigned*)(dev + bp + bn + bc), nt);
+        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, all, hipMemcpyDeviceToHost, c->stream);
+        s = tf_from_hip(e);
+        const tf_status s2 = sync_checked(c);          // (the stream is idle before the buffer goes)
+        if (s == TF_OK) s = s2;
+        (void)hipFree(dev);
+    }
+    if (s == TF_OK) {
+        // nt == 0: the attribute columns are still declared (non-null dummies, never read)
+        static const float none = 0.0f;
+        const float* hn = nrm ? (host ? (const float*)(host + bp) : &none) : nullptr;
+        const uint8_t* hc = col ? (host ? (const uint8_t*)(host + bp + bn) : (const uint8_t*)&none) : nullptr;
+        s = tf_mesh_write_ply_indexed(path, (const float*)host, hn, hc, nt > 0 ? nv : 0, host ? (const uint32_t*)(host + bp + bn + bc) : nullptr, nt);
     }
     free(host);
     return s;

@@ -467,6 +467,12 @@ struct tf_ctx {
     // allocated by the first extraction
     long long* meshCount;                // [n_total] counts, then one total per 512-entry group
     long long* meshBase;                 // [n_total + 1]
+    // indexed extraction: per VBA block its 512 x 7 edge bits and the words' exclusive popcount prefixes, per
+    // hash entry its vertex count and base (+ the total); allocated by the first indexed extraction
+    unsigned* meshMask;                  // [n_blocks][112]
+    unsigned* meshWPre;                  // [n_blocks][112]
+    long long* meshVCount;               // [n_total] counts, then one total per 512-entry group
+    long long* meshVBase;                // [n_total + 1]
 };
 #define TF_VERDICT_WORDS 16
 
@@ -574,5 +580,12 @@ hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity);
 // the emit pass with per-vertex attributes: positions (may be nullptr), normals and / or colours (one of
 // the two at least; colours only with the colour plane), clipped at the same capacity
 hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity);
+// the indexed form: tfk_mesh_count plus the edge marks and the vertex count + prefix (the vertex total lands
+// in meshVBase[n_total]); then the vertex table's columns (positions, normals, RGBA; nullptr skips one)
+// clipped at `capacity` vertices, and three u32 vertex numbers per triangle clipped at `capacity` triangles
+hipError_t tfk_mesh_prefix(tf_ctx* c, const long long* count, const long long* groupTot, long long* base);   // k_mesh_prefix alone
+hipError_t tfk_mesh_index_count(tf_ctx* c);
+hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity);
+hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity);
 
 enum { TF_POSE_ALLOC = 1, TF_POSE_RAY = 2, TF_POSE_ALLOC_NOINV = 4 };

@@ -279,3 +279,94 @@ TFM_HD int tfm_cube_emit_attr(const TfmCube& q, int gx, int gy, int gz, float vs
     n += tfm_tet_emit_attr<5>(q, m, gx, gy, gz, vs, src, emit);
     return n;
 }
+
+// ---- indexed extraction (DESIGN.md §Mesh extraction, indexed) ----------------------------------------
+// A vertex IS its Kuhn edge (p, d): p the edge's lower end (a lattice voxel), d in {0,1}^3 \ {0} with the
+// direction code dc = dx | dy << 1 | dz << 2.  The edge belongs to the block of p (its owner); inside the
+// owner it is bit lp * 7 + dc - 1 of a 512 x 7-bit mask (lp = p's voxel index x + 8 y + 64 z), and its
+// vertex number is the owner's base plus the number of set bits below it.
+#define TFM_EDGE_WORDS 112       // 512 * 7 / 32
+
+struct TfmEdgeRef {
+    unsigned owner;              // which of the entry's eight blocks holds p: (px >> 3) | (py >> 3) << 1 | (pz >> 3) << 2
+    unsigned bit;                // the edge's bit in the owner's mask
+};
+
+TFM_HD unsigned tfm_edge_bit(unsigned lp, unsigned dc) { return lp * 7u + dc - 1u; }
+
+// the edge whose lower end is the lattice point (px, py, pz) of an entry's tile, 0 .. 8 each
+TFM_HD TfmEdgeRef tfm_edge_ref(int px, int py, int pz, unsigned dc)
+{
+    TfmEdgeRef r;
+    r.owner = (unsigned)((px >> 3) | (py >> 3) << 1 | (pz >> 3) << 2);
+    r.bit = tfm_edge_bit((unsigned)((px & 7) | (py & 7) << 3 | (pz & 7) << 6), dc);
+    return r;
+}
+
+// the edge's rank inside its owner from the mask word that holds its bit and that word's exclusive
+// popcount prefix
+TFM_HD unsigned tfm_edge_rank(unsigned word, unsigned prefix, unsigned bit)
+{
+    return prefix + (unsigned)__builtin_popcount(word & ((1u << (bit & 31u)) - 1u));
+}
+
+// The sign-changing Kuhn edges of the cube whose corner 0 is the tile's lattice point (x, y, z), 0 .. 7
+// each, through mark(TfmEdgeRef): the 19 corner pairs lo, hi = lo | dc with lo & dc == 0.  Each is an
+// edge of one of the six tetrahedra at least, and a tetrahedron puts a triangle vertex on every edge
+// of its own whose ends differ, so these are exactly the edges tfm_cube_emit's triangles touch.
+template <class Mark>
+TFM_HD void tfm_cube_mark(const TfmCube& q, int x, int y, int z, Mark& mark)
+{
+    if (!q.valid) return;
+    const unsigned m = tfm_inside_mask(q);
+    if (m == 0u || m == 255u) return;
+    for (unsigned lo = 0; lo < 7; ++lo)
+        for (unsigned dc = 1; dc < 8; ++dc) {
+            if (lo & dc) continue;
+            if (((m >> lo) ^ (m >> (lo | dc))) & 1u) mark(tfm_edge_ref(x + (int)(lo & 1), y + (int)(lo >> 1 & 1), z + (int)(lo >> 2), dc));
+        }
+}
+
+// tfm_tet_emit without the floats: tetrahedron K's triangles through emit(const unsigned lo[3], const
+// unsigned hi[3]) -- per triangle vertex the cube corners its edge joins (lo a subset of hi) -- in the same
+// order, with the same per-triangle vertex order.
+template <int K, class Emit>
+TFM_HD int tfm_tet_emit_edges(unsigned inside8, Emit& emit)
+{
+    constexpr unsigned corners = tfm_tet_corners(K);
+    const unsigned info = tfm_cases[tfm_tet_case<K>(inside8)];
+    const int n = (int)(info & 3);
+    const bool flip = ((info >> 2 & 1) != 0) != tfm_tet_negative(K);
+    for (int tr = 0; tr < n; ++tr) {
+        unsigned lo[3], hi[3];
+        for (int v = 0; v < 3; ++v) {
+            const int w = v == 0 ? 0 : (flip ? 3 - v : v) + tr;
+            const unsigned e = info >> (4 + 4 * w) & 15u;
+            lo[v] = corners >> (3 * (e & 3)) & 7u;
+            hi[v] = corners >> (3 * (e >> 2)) & 7u;
+        }
+        emit(lo, hi);
+    }
+    return n;
+}
+
+template <class Emit>
+TFM_HD int tfm_cube_emit_edges(const TfmCube& q, Emit& emit)
+{
+    if (!q.valid) return 0;
+    const unsigned m = tfm_inside_mask(q);
+    int n = tfm_tet_emit_edges<0>(m, emit);
+    n += tfm_tet_emit_edges<1>(m, emit);
+    n += tfm_tet_emit_edges<2>(m, emit);
+    n += tfm_tet_emit_edges<3>(m, emit);
+    n += tfm_tet_emit_edges<4>(m, emit);
+    n += tfm_tet_emit_edges<5>(m, emit);
+    return n;
+}
+
+// The vertex of the edge (p, dc) from its lower end: p's global voxel coordinate, the sdf shorts at p and
+// q = p + d.  tfm_vertex with the cube's corner 0 at p, so the bits every cube sharing the edge computes.
+TFM_HD void tfm_edge_vertex(unsigned dc, int sp, int sq, int px, int py, int pz, float vs, float* out)
+{
+    tfm_vertex(0u, dc, sp, sq, px, py, pz, vs, out);
+}

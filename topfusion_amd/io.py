@@ -4,7 +4,7 @@ Same pixels as OpenCV's imread(path, CV_16U) / imread(path) for binary netpbm fi
 maxval > 255 holds big-endian 16-bit samples; P6 holds RGB, returned as BGR like imread.
 The C++ side is include/tfusion/io.hpp (readPGM16 / readPPM / FrameSequenceSource).
 
-Mesh output (an addition): write_ply / read_ply, the binary PLY of tf_mesh_write_ply."""
+Mesh output (an addition): write_ply / write_ply_indexed / read_ply, the binary PLY of tf_mesh_write_ply."""
 import numpy as np
 
 
@@ -89,6 +89,26 @@ def write_ply(path, tris, normals=None, colours=None):
             raise ValueError("attributes and triangles differ in length")
     vp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
     L.check(L.load().tf_mesh_write_ply_attr(str(path).encode(), vp(t), vp(nr), vp(co), len(t)), "tf_mesh_write_ply_attr")
+
+
+def write_ply_indexed(path, vertices, indices, normals=None, colours=None):
+    """An indexed mesh -- vertices (m, 3) float32, indices (n, 3) uint32, optionally normals (m, 3) float32 and
+    colours (m, 4) uint8 RGBA per vertex -- as a binary little-endian PLY with write_ply's layout: the vertex
+    table as given, nothing welded (tf_mesh_write_ply_indexed).  read_ply / read_ply_attr read it."""
+    import ctypes
+    from . import _lib as L
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    nr = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    co = None if colours is None else np.ascontiguousarray(colours, np.uint8).reshape(-1, 4)
+    for a in (nr, co):
+        if a is not None and len(a) != len(v):
+            raise ValueError("attributes and vertices differ in length")
+    vp = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+    dummy = np.zeros(4, np.float32)           # an empty attribute column is still declared
+    at = lambda a: None if a is None else (vp(a) or dummy.ctypes.data_as(ctypes.c_void_p))
+    L.check(L.load().tf_mesh_write_ply_indexed(str(path).encode(), vp(v), at(nr), at(co), len(v), vp(f), len(f)),
+            "tf_mesh_write_ply_indexed")
 
 
 def read_ply(path):

@@ -382,13 +382,57 @@ class TopFu:
                     hip.hipFree(d)
         return tuple(outs)
 
-    def save_mesh(self, path, normals=False, colours=False):
+    def mesh_indexed_count(self):
+        """(vertices, triangles) the scene's indexed mesh has (the count passes alone)."""
+        nv, nt = ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(L.load().tf_mesh_extract_indexed(self._h, None, None, None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)),
+                "tf_mesh_extract_indexed")
+        return nv.value, nt.value
+
+    def mesh_indexed(self, normals=False, colours=False):
+        """mesh() with shared vertices (tf_mesh_extract_indexed): (vertices (nv, 3) float32, indices (nt, 3)
+        uint32, normals (nv, 3) float32 or None, colours (nv, 4) uint8 RGBA or None).  vertices[indices] is
+        mesh() bit for bit, normals[indices] / colours[indices] are mesh_attr()'s.  A vertex is the cube edge it
+        lies on: edges are never merged, even where their positions coincide."""
+        if colours and not self.params_.voxel_rgb:
+            raise L.TfError(L.TF_INVALID_ARG, "mesh_indexed (colours without voxel_rgb)")
+        nv, nt = self.mesh_indexed_count()
+        outs = [np.empty((nv, 3), np.float32), np.empty((nv, 3), np.float32) if normals else None,
+                np.empty((nv, 4), np.uint8) if colours else None, np.empty((nt, 3), np.uint32)]
+        if nt == 0:
+            return outs[0], outs[3], outs[1], outs[2]
+        hip = L.hip_runtime()
+        devs = []
+        try:
+            for o in outs:
+                d = ctypes.c_void_p()
+                if o is not None and hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(max(o.nbytes, 16))) != 0:
+                    raise L.TfError(L.TF_OOM, "hipMalloc (mesh)")
+                devs.append(d)
+            mv, mt = ctypes.c_longlong(), ctypes.c_longlong()
+            L.check(L.load().tf_mesh_extract_indexed(self._h, devs[0], devs[1], devs[2], nv, devs[3], nt, ctypes.byref(mv),
+                                                     ctypes.byref(mt)), "tf_mesh_extract_indexed")
+            assert (mv.value, mt.value) == (nv, nt), (mv.value, mt.value, nv, nt)
+            for o, d in zip(outs, devs):
+                if o is not None and hip.hipMemcpy(_ptr(o), d, ctypes.c_size_t(o.nbytes), 2) != 0:   # hipMemcpyDeviceToHost
+                    raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (mesh)")
+        finally:
+            for d in devs:
+                if d:
+                    hip.hipFree(d)
+        return outs[0], outs[3], outs[1], outs[2]
+
+    def save_mesh(self, path, normals=False, colours=False, indexed=False):
         """The mesh as a binary PLY with welded vertices (tf_mesh_save_ply); with normals / colours,
-        nx ny nz / red green blue alpha per vertex (tf_mesh_save_ply_attr)."""
+        nx ny nz / red green blue alpha per vertex (tf_mesh_save_ply_attr).  indexed: the vertex table of
+        mesh_indexed() as it is, no host weld (tf_mesh_save_ply_indexed)."""
+        attrs = (L.TF_MESH_NORMALS if normals else 0) | (L.TF_MESH_COLOURS if colours else 0)
+        if indexed:
+            L.check(L.load().tf_mesh_save_ply_indexed(self._h, str(path).encode(), attrs), "tf_mesh_save_ply_indexed")
+            return
         if not normals and not colours:
             L.check(L.load().tf_mesh_save_ply(self._h, str(path).encode()), "tf_mesh_save_ply")
             return
-        attrs = (L.TF_MESH_NORMALS if normals else 0) | (L.TF_MESH_COLOURS if colours else 0)
         L.check(L.load().tf_mesh_save_ply_attr(self._h, str(path).encode(), attrs), "tf_mesh_save_ply_attr")
 
     # typed views
