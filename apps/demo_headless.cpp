@@ -10,6 +10,8 @@
 //   ... --mesh out.ply : the reconstructed surface after the last frame (TopFu::saveMesh)
 //   ... --mesh-normals : with per-vertex normals (nx ny nz) in that PLY
 //   ... --mesh-indexed : the indexed vertex table as the GPU extracts it, no host weld
+//   ... --load-scene F : resume from the checkpoint F before the first frame (TopFu::loadScene)
+//   ... --save-scene F : write the checkpoint F after the last frame (TopFu::saveScene)
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -29,13 +31,15 @@ using namespace tfusion;
 
 int main(int argc, char** argv)
 {
-    std::string pgm, ppm, mesh;
+    std::string pgm, ppm, mesh, load_scene, save_scene;
     bool mesh_normals = false, mesh_indexed = false;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--pgm") && i + 1 < argc) pgm = argv[++i];
         else if (!std::strcmp(argv[i], "--ppm") && i + 1 < argc) ppm = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh = argv[++i];
+        else if (!std::strcmp(argv[i], "--load-scene") && i + 1 < argc) load_scene = argv[++i];
+        else if (!std::strcmp(argv[i], "--save-scene") && i + 1 < argc) save_scene = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
         else if (!std::strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
         else pos.push_back(argv[i]);
@@ -64,6 +68,15 @@ int main(int argc, char** argv)
     const double s = cols / 640.0;
     params.intr = Intr(504.261f * s, 503.905f * s, 352.457f * s, 272.202f * s);
     TopFu::Ptr topfu(new TopFu(params));
+    auto scene_line = [](const char* what, const std::string& path) {
+        const struct tf_scene_file_info info = TopFu::sceneFileInfo(path);
+        std::printf("scene %s %s: %lld records, %lld blocks, %lld bytes\n", what, path.c_str(), info.n_records,
+                    info.n_blocks_stored, info.file_bytes);
+    };
+    if (!load_scene.empty()) {
+        topfu->loadScene(load_scene);
+        scene_line("loaded from", load_scene);
+    }
 
     cuda::Depth depth_device;
     cuda::image4u view_device;
@@ -97,6 +110,10 @@ int main(int argc, char** argv)
     const tf_stats st = topfu->stats();
     std::printf("frames %d ok %d resets %d visible %d  pose t = (%.4f %.4f %.4f)\n", n, n_ok, st.n_resets,
                 st.noVisibleEntries, pose.translation()[0], pose.translation()[1], pose.translation()[2]);
+    if (!save_scene.empty()) {
+        topfu->saveScene(save_scene);
+        scene_line("saved to", save_scene);
+    }
     if (!mesh.empty()) {
         if (mesh_indexed) {
             topfu->saveMesh(mesh, TF_MESH_INDEXED | (mesh_normals ? TF_MESH_NORMALS : 0));

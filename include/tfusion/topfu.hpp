@@ -307,6 +307,27 @@ namespace tfusion
             return nt;
         }
 
+        // Scene checkpoints (additions: tf_scene_save / tf_scene_load / tf_scene_file_info).  saveScene writes
+        // the state a sequence resumes from; loadScene replaces this TopFu's scene, pose and frame counter by
+        // the file's (the pose history restarts at the loaded pose); the capacities, image size and scene
+        // parameters must be the file's.  sceneFileInfo reads a file's header without a context.
+        void saveScene(const std::string& path) { check(tf_scene_save(ctx_, path.c_str()), "tf_scene_save"); }
+        void loadScene(const std::string& path)
+        {
+            check(tf_scene_load(ctx_, path.c_str()), "tf_scene_load");
+            float rt[12];
+            check(tf_get_pose(ctx_, rt), "tf_get_pose");
+            frame_counter_ = stats().frame_counter;
+            poses_.clear();
+            poses_.push_back(affine_from_rt(rt));
+        }
+        static struct tf_scene_file_info sceneFileInfo(const std::string& path)
+        {
+            struct tf_scene_file_info info;
+            check(tf_scene_file_info(path.c_str(), &info), "tf_scene_file_info");
+            return info;
+        }
+
         tf_ctx* handle() { return ctx_; }
         hipStream_t stream() const { return (hipStream_t)tf_get_stream(ctx_); }
 

@@ -512,6 +512,49 @@ tf_status tf_mesh_write_ply_indexed(const char* path, const float* host_vertices
  * (TF_MESH_INDEXED may be set and changes nothing); TF_INDEX_RANGE beyond 2^31 - 1 vertices */
 tf_status tf_mesh_save_ply_indexed(tf_ctx* ctx, const char* path, int attrs);
 
+/* ---- scene checkpoints (additions: the reference cannot save its map; DESIGN.md §5 Scene checkpoints) --
+ * A checkpoint is the state a sequence resumes from, sized by what is live: the hash entries that differ
+ * from ResetScene's, their voxel (and colour) blocks, visType where non-zero, visibleIds[0, noVisibleEntries),
+ * the live parts of the two free lists, the counters, frame_counter, the pose and the previous points /
+ * normals pyramid.  A context that loads a checkpoint is indistinguishable, bit for bit, from the one that
+ * saved it, now and after any further frames.  Contexts with use_swapping are refused (TF_INVALID_ARG): the
+ * GlobalCache has its own tf_swap_save / tf_swap_load, and a file that combines the two is not built. */
+/* addition (no reference counterpart): writes the checkpoint of the current state to path.  Synchronous, the
+ * scene is only read; two saves of one state are byte-identical, and a save straight after tf_scene_load of
+ * file F is byte-identical to F.  TF_INVALID_ARG: NULL arguments, use_swapping, a path that cannot be
+ * written, and a state that tf_scene_load would refuse -- tables or counters that came through tf_upload /
+ * tf_set_counters with a ptr outside the VBA or named twice, a chain offset past the excess list, a counter
+ * or a live list / visible-list value outside its table (checked by load's own rule; no file is left);
+ * TF_HIP_ERROR on a context in error; TF_OOM.  The blocks travel through a bounded staging buffer
+ * (TFUSION_CKPT_CHUNK_BLOCKS blocks, read at tf_create; default 4096), kept by the context after the first call. */
+tf_status tf_scene_save(tf_ctx* ctx, const char* path);
+/* addition (no reference counterpart): replaces the context's scene, pose, frame counter and tracker maps by
+ * the file's.  The context must agree with the file in cols, rows, n_buckets, n_excess, n_blocks, voxel_rgb,
+ * use_swapping == 0 and the bits of voxelSize, mu, maxW; its tracker parameters, pose algebra and intrinsics
+ * stay its own.  The whole file is read and validated on the host first: TF_INVALID_ARG (a missing, truncated,
+ * corrupt or mismatched file, use_swapping) leaves the context exactly as it was.  Synchronous. */
+tf_status tf_scene_load(tf_ctx* ctx, const char* path);
+/* what a checkpoint file holds, from its header */
+struct tf_scene_file_info {
+    tf_params params;               /* the saving context's tf_get_params */
+    int pose_algebra, frame_counter;
+    int lastFreeBlockId, lastFreeExcessListId, noVisibleEntries;
+    long long n_records, n_blocks_stored, file_bytes;
+    float pose[12];
+};
+/* addition (no reference counterpart): host only, no context, no GPU call -- the header of the file at path,
+ * checked against its checksum and the file's length.  (The struct is named by its tag: C has one name
+ * space for typedefs and functions.) */
+tf_status tf_scene_file_info(const char* path, struct tf_scene_file_info* info);
+/* addition (measurement; no reference counterpart): what the context's last tf_scene_save / tf_scene_load
+ * spent, in milliseconds, by the host clock: ms[2] the D2H / H2D copies, ms[3] the file reads / writes, ms[6]
+ * the record check and checksum (load: the whole validation), ms[4] the whole call.  On a context created
+ * with the environment variable TFUSION_CKPT_TIMING=1 the kernels are also timed, by HIP events on the context
+ * stream and a wait after each group (0 otherwise): ms[0] the index kernels (save: count + prefix + records;
+ * load: records -> hash, visType, block grid), ms[1] the block kernels (gather / scatter, summed over the
+ * chunks).  ms[5] is not a time: the bytes the block kernels read + wrote.  ms[7] is 0. */
+tf_status tf_scene_ckpt_times(tf_ctx* ctx, double ms[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,14 @@ class TfStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TfSceneFileInfo(ctypes.Structure):
+    """struct tf_scene_file_info: a scene checkpoint's header."""
+    _fields_ = [("params", TfParams), ("pose_algebra", ctypes.c_int), ("frame_counter", ctypes.c_int),
+                ("lastFreeBlockId", ctypes.c_int), ("lastFreeExcessListId", ctypes.c_int),
+                ("noVisibleEntries", ctypes.c_int), ("n_records", ctypes.c_longlong),
+                ("n_blocks_stored", ctypes.c_longlong), ("file_bytes", ctypes.c_longlong), ("pose", ctypes.c_float * 12)]
+
+
 class TfTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_longlong) for n in ("frames", "frames_tracked", "resets", "visible_sum", "tiles_sum",
                                                  "swapped_in", "swapped_out", "integrate_lanes_read",
@@ -183,6 +191,10 @@ def load():
                                      ctypes.POINTER(ctypes.c_longlong)], I),
         "tf_mesh_write_ply_indexed": ([ctypes.c_char_p, P, P, P, ctypes.c_longlong, P, ctypes.c_longlong], I),
         "tf_mesh_save_ply_indexed": ([P, ctypes.c_char_p, I], I),
+        "tf_scene_save": ([P, ctypes.c_char_p], I),
+        "tf_scene_load": ([P, ctypes.c_char_p], I),
+        "tf_scene_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfSceneFileInfo)], I),
+        "tf_scene_ckpt_times": ([P, P], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():
@@ -252,3 +264,18 @@ def default_params(**kw):
         else:
             setattr(p, k, v)
     return p
+
+
+def scene_file_info(path):
+    """The header of a scene checkpoint (tf_scene_file_info; host only, no context): a dict with the
+    saving context's `params` (TfParams), pose_algebra, frame_counter, the three counters, n_records,
+    n_blocks_stored, file_bytes and the 3 x 4 `pose`."""
+    info = TfSceneFileInfo()
+    check(load().tf_scene_file_info(str(path).encode(), ctypes.byref(info)), "tf_scene_file_info")
+    out = {n: getattr(info, n) for n in ("pose_algebra", "frame_counter", "lastFreeBlockId", "lastFreeExcessListId",
+                                         "noVisibleEntries", "n_records", "n_blocks_stored", "file_bytes")}
+    p = TfParams()
+    ctypes.memmove(ctypes.byref(p), ctypes.byref(info.params), ctypes.sizeof(TfParams))
+    out["params"] = p
+    out["pose"] = np.array(list(info.pose), np.float32).reshape(3, 4)
+    return out

@@ -473,7 +473,18 @@ struct tf_ctx {
     unsigned* meshWPre;                  // [n_blocks][112]
     long long* meshVCount;               // [n_total] counts, then one total per 512-entry group
     long long* meshVBase;                // [n_total + 1]
+    // scene checkpoints (tf_scene_ckpt.hip): per 256-entry group its (records, stored blocks) counts, then their
+    // exclusive bases + the totals, then a flag; the bounded block staging buffer and its pinned twin;
+    // allocated by the first save / load
+    int ckpt_chunk_blocks;               // blocks per staging chunk (TFUSION_CKPT_CHUNK_BLOCKS; default TF_CKPT_CHUNK_BLOCKS)
+    int2* ckptGroup;
+    unsigned char* ckptStage;
+    unsigned char* ckptPinned;
+    hipEvent_t ckptEv[2];                // around the checkpoint kernels (tf_scene_ckpt_times)
+    double ckpt_ms[8];                   // the last save / load: see tf_scene_ckpt_times
+    int ckpt_timing;                     // TFUSION_CKPT_TIMING=1: the kernels are timed by events (and waited for)
 };
+#define TF_CKPT_CHUNK_BLOCKS 4096        // 8 MiB of voxels (16 MiB with colour) per chunk, whatever n_blocks is
 #define TF_VERDICT_WORDS 16
 
 // the launch of a stage's single kernel: timed by the dispatch's own timestamps when the
@@ -587,5 +598,17 @@ hipError_t tfk_mesh_prefix(tf_ctx* c, const long long* count, const long long* g
 hipError_t tfk_mesh_index_count(tf_ctx* c);
 hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity);
 hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity);
+
+// scene checkpoints (tf_scene_ckpt.hip): the scratch; count + prefix (totals: device address of {records,
+// blocks} and, behind it, the "a ptr lies outside the VBA" flag); the records and the stored blocks' ptr
+// list into caller device buffers; nb <= ckpt_chunk_blocks listed blocks VBA -> staging / staging -> VBA;
+// hash and visType from n records
+hipError_t tfk_ckpt_scratch(tf_ctx* c);
+size_t tfk_ckpt_stage_bytes(const tf_ctx* c);
+hipError_t tfk_ckpt_count(tf_ctx* c, const int2** totals);
+hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr);
+hipError_t tfk_ckpt_gather(tf_ctx* c, const int* blockPtr, int nb);
+hipError_t tfk_ckpt_scatter(tf_ctx* c, const int* blockPtr, int nb);
+hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_records);
 
 enum { TF_POSE_ALLOC = 1, TF_POSE_RAY = 2, TF_POSE_ALLOC_NOINV = 4 };

@@ -1,0 +1,62 @@
+// tf_scene_file.h -- the scene checkpoint file (DESIGN.md §5 Scene checkpoints): layout, header
+// encoding and validation.  Host C++ with no HIP call: this is the code that reads untrusted
+// bytes, and it compiles on its own for a CPU (tests/test_scene_ckpt_ref.py runs it under
+// AddressSanitizer / UBSan from a stand-alone program).
+//
+// Little-endian, fixed order:
+//   header   TF_SCENE_HEADER_BYTES
+//   records  n_records x 24 B: u32 entry index, the 16-byte HashEntry, u8 visType, 3 zero bytes;
+//            ascending entry index; an entry has one when its HashEntry is not ResetScene's
+//            {0,0,0,0, 0, -2} or its visType is non-zero
+//   blocks   in record order, for records with ptr >= 0: 2048 B of voxels, then (voxel_rgb) 2048 B of colour
+//   visibleIds[0, noVisibleEntries)                       4 B each
+//   allocList[0, lastFreeBlockId + 1)                     4 B each
+//   excessList[0, lastFreeExcessListId + 1)               4 B each
+//   maps     previous points then normals of level 0, 1, 2: 16 B x (cols >> l) x (rows >> l) each
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include "../../include/tfusion_hip.h"
+
+#define TF_SCENE_VERSION 1u
+#define TF_SCENE_HEADER_BYTES 296
+#define TF_SCENE_RECORD_BYTES 24
+#define TF_SCENE_BLOCK_BYTES 2048          // 512 voxels x 4 B (and as much colour)
+#define TF_SCENE_LEVELS 3
+// header offsets
+#define TF_SCENE_OFF_MAGIC 0               // "TFSCENE\0"
+#define TF_SCENE_OFF_VERSION 8             // u32
+#define TF_SCENE_OFF_PARAMS_BYTES 12       // u32 sizeof(tf_params)
+#define TF_SCENE_OFF_PARAMS 16             // tf_params (180 B)
+#define TF_SCENE_OFF_ALGEBRA 196           // i32 x 5: pose_algebra, frame_counter, lastFreeBlockId,
+#define TF_SCENE_OFF_COUNTS 216            //   lastFreeExcessListId, noVisibleEntries; i64 x 3: n_records,
+#define TF_SCENE_OFF_POSE 240              //   n_blocks_stored, file_bytes; float[12] pose
+#define TF_SCENE_OFF_CRC 288               // u32 CRC-32 (IEEE, zlib's) of the header bytes [0, 288)
+#define TF_SCENE_OFF_RECORDS_CRC 292       // u32 CRC-32 of the records section
+
+// where the sections of a file with these counts lie
+struct TfSceneLayout {
+    size_t records_off, blocks_off, vis_off, alloc_off, excess_off, maps_off, file_bytes;
+    size_t block_bytes;                    // per stored block: 2048, or 4096 with colour
+    size_t n_vis, n_alloc, n_excess;       // list slots stored
+    size_t map_bytes[TF_SCENE_LEVELS];     // one map (points or normals) of the level
+};
+
+// zlib's crc32: start with crc = 0, feed the result back in to continue
+uint32_t tf_scene_crc32(uint32_t crc, const unsigned char* p, size_t n);
+// true when the params and counters describe a file (sizes positive and bounded, counters within
+// their lists); fills the layout from them (n_records / n_blocks_stored as given in info)
+bool tf_scene_layout(const struct tf_scene_file_info* info, TfSceneLayout* lay);
+// the header of a file with info's params, counters, counts, file_bytes and pose, and the records' checksum
+void tf_scene_header_encode(const struct tf_scene_file_info* info, uint32_t records_crc, unsigned char hdr[TF_SCENE_HEADER_BYTES]);
+// the header alone: magic, version, sizes, its checksum, tf_scene_layout, file_bytes == the layout's
+tf_status tf_scene_header_decode(const unsigned char* hdr, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay);
+// the record table on its own (save checks what it is about to write by the rule load will apply): ascending
+// indices < n_total, zero padding, chain offsets and ptr within the tables, no record for ResetScene's entry,
+// ptr >= 0 distinct and n_blocks_stored of them; and n list values within [0, bound)
+tf_status tf_scene_records_check(const unsigned char* records, long long n_records, const tf_params* p, long long n_blocks_stored);
+bool tf_scene_list_within(const unsigned char* values, size_t n, int32_t bound);
+// a whole file in memory: the header, len == file_bytes, the records (their checksum; ascending indices < n_total,
+// canonical, chain offsets and ptr within the tables, ptr >= 0 distinct and n_blocks_stored of
+// them), the list values within their tables.  TF_OK or TF_INVALID_ARG (TF_OOM: no scratch).
+tf_status tf_scene_file_validate(const unsigned char* data, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay);

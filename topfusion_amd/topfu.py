@@ -323,6 +323,52 @@ class TopFu:
     def swap_load(self, path):
         L.check(L.load().tf_swap_load(self._h, str(path).encode()), "tf_swap_load")
 
+    # -- scene checkpoints (additions: tf_scene_save / tf_scene_load; the reference cannot save its map) ----
+    def save_scene(self, path):
+        """The state a sequence resumes from -- live hash entries and their blocks, visible list, free
+        lists, counters, pose, tracker maps -- as a file sized by what is live (tf_scene_save)."""
+        L.check(L.load().tf_scene_save(self._h, str(path).encode()), "tf_scene_save")
+
+    def load_scene(self, path):
+        """Replaces this context's scene, pose and frame counter by the file's (tf_scene_load): from here
+        on it is the saving context, bit for bit.  Capacities, image size and scene parameters must be the
+        file's; a refused file (TfError, TF_INVALID_ARG) leaves the context as it was."""
+        L.check(L.load().tf_scene_load(self._h, str(path).encode()), "tf_scene_load")
+        self._framed = True
+
+    def scene_ckpt_times(self):
+        """What the last save_scene / load_scene spent (tf_scene_ckpt_times): a dict of milliseconds --
+        copies, file, check (the record check and checksum), call (host clock), and on a context created with
+        TFUSION_CKPT_TIMING=1 index_kernels, block_kernels (HIP events) -- and block_kernel_bytes."""
+        ms = np.zeros(8, np.float64)
+        L.check(L.load().tf_scene_ckpt_times(self._h, _ptr(ms)), "tf_scene_ckpt_times")
+        return dict(zip(("index_kernels", "block_kernels", "copies", "file", "call", "block_kernel_bytes", "check"), ms.tolist()))
+
+    @classmethod
+    def from_scene(cls, path, device=None, **overrides):
+        """A context built from the file's params (with `overrides` applied, as default_params takes
+        them) that has loaded the file; the pose algebra is the file's too."""
+        info = L.scene_file_info(path)
+        p = info["params"]
+        for k, v in overrides.items():
+            if k == "icp_iter_num":
+                for i in range(4):
+                    p.icp_iter_num[i] = int(v[i]) if i < len(v) else 0
+            elif k in ("rgb_intr", "depth_to_rgb"):
+                arr = getattr(p, k)
+                for i, x in enumerate(v):
+                    arr[i] = float(x)
+            else:
+                setattr(p, k, v)
+        t = cls(p, device=device)
+        try:
+            t.set_pose_algebra(info["pose_algebra"])
+            t.load_scene(path)
+        except Exception:
+            t.close()
+            raise
+        return t
+
     # -- mesh extraction (additions: tf_mesh_*; the reference has no mesher) ------------------------
     def mesh_count(self):
         """Triangles the scene's mesh has (the count pass alone)."""
