@@ -1,5 +1,5 @@
 """Indexed mesh extraction on the GPU (tf_mesh_extract_indexed and the layers above it, the kernels of
-topfusion_amd/csrc/tf_mesh_indexed.hip) against the numpy restatement of its specification
+topfusion_amd/csrc/tf_mesh.hip) against the numpy restatement of its specification
 (tests/mesh_indexed_ref.py), bit for bit: both counts, every position and normal float, every colour byte
 and every index.  Scenes are built by hand (synth.build_hash + uploads) in small contexts, except the
 pipeline and demo tests, which mesh what real frames fused."""

@@ -140,6 +140,88 @@ def test_ply_attr_round_trip(tmp_path):
     assert len(verts) == 0 and len(faces) == 0 and vn.shape == (0, 3) and vc is None
 
 
+def _ply_bytes(records, faces, normals, colours):
+    """The file of DESIGN.md §Mesh extraction (PLY), built here: the header text, the vertex records (3 | 6 | 7
+    little-endian dwords each), then per face the byte 3 and three little-endian int32."""
+    head = "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\n" + f"element vertex {len(records)}\n" + \
+           "property float x\nproperty float y\nproperty float z\n" + \
+           ("property float nx\nproperty float ny\nproperty float nz\n" if normals else "") + \
+           ("property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" if colours else "") + \
+           f"element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n"
+    rec = np.zeros(len(faces), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    assert rec.dtype.itemsize == 13
+    rec["n"], rec["i"] = 3, np.asarray(faces).reshape(-1, 3)
+    return head.encode("ascii") + np.ascontiguousarray(records, "<u4").tobytes() + rec.tobytes()
+
+
+def _first_appearance(records, faces):
+    """A.weld's (sorted) records and faces renumbered in the order in which the triangles' vertices first
+    name each record: the order the welding writers keep."""
+    flat = np.asarray(faces).reshape(-1)
+    first = np.full(len(records), -1, np.int64)
+    first[flat[::-1]] = np.arange(len(flat))[::-1]
+    assert (first >= 0).all()
+    order = np.argsort(first)
+    rank = np.empty(len(records), np.int64)
+    rank[order] = np.arange(len(records))
+    return records[order], rank[flat].reshape(-1, 3)
+
+
+def test_ply_bytes(tmp_path):
+    """Every byte of the three writers' files against _ply_bytes, independently of the writers' hash: the
+    random attributed case (all column combinations; for the indexed writer its welded records as the vertex
+    table), two vertices at one position with different normals, and the empty mesh with a declared normal
+    column."""
+    from topfusion_amd import io
+    _, _, _, tris, normals, colours, _ = A.random_case()
+    t2 = np.zeros((2, 3, 3), np.float32)
+    n2 = np.zeros((2, 3, 3), np.float32)
+    n2[1, :, 2] = 1
+    e3 = np.zeros((0, 3, 3), np.float32)
+    cases = [(tris, nr, co) for nr in (None, normals) for co in (None, colours)] + [(t2, n2, None), (e3, e3, None)]
+    path = tmp_path / "bytes.ply"
+    for t, nr, co in cases:
+        records, faces = _first_appearance(*A.weld(t, nr, co)) if len(t) else (np.zeros((0, 6), np.uint32), np.zeros((0, 3), np.int64))
+        want = _ply_bytes(records, faces, nr is not None, co is not None)
+        io.write_ply(path, t, normals=nr, colours=co)
+        assert path.read_bytes() == want, (len(t), nr is not None, co is not None)
+        # the same table through the indexed writer: nothing welded, nothing reordered
+        v = records[:, :3].view(np.float32)
+        vn = None if nr is None else records[:, 3:6].view(np.float32)
+        vc = None if co is None else np.ascontiguousarray(records[:, -1:]).view(np.uint8)
+        io.write_ply_indexed(path, v, faces.astype(np.uint32), normals=vn, colours=vc)
+        assert path.read_bytes() == want, (len(t), nr is not None, co is not None)
+    assert len(_first_appearance(*A.weld(t2, n2))[0]) == 2
+    # a table with repeated rows and a reversed order stays as given
+    records, faces = A.weld(tris, normals, colours)
+    rep = np.concatenate([records[::-1], records[:5]])
+    f = (len(records) - 1 - faces).astype(np.uint32)
+    io.write_ply_indexed(path, rep[:, :3].view(np.float32), f, normals=rep[:, 3:6].view(np.float32),
+                         colours=np.ascontiguousarray(rep[:, -1:]).view(np.uint8))
+    assert path.read_bytes() == _ply_bytes(rep, f, True, True)
+
+
+def test_ply_writers_under_asan_ubsan(tmp_path):
+    """tf_mesh_ply.cpp built for the CPU with -fsanitize=address,undefined and driven by tests/mesh_ply_main.cpp
+    in one process: the three writers on 300 random triangles with duplicated vertices (every column
+    combination, the files expanding back bit for bit), 0.0f beside -0.0f, empty meshes with and without
+    attribute columns, an index equal to the vertex count and the null / negative arguments (refused) -- with
+    no sanitizer report."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "mesh_ply_main")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-o", exe, os.path.join(ROOT, "tests", "mesh_ply_main.cpp"),
+                        os.path.join(ROOT, "topfusion_amd", "csrc", "tf_mesh_ply.cpp")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = tmp_path / "files"
+    out.mkdir()
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, str(out)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok ") and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr
+
+
 _HOST_SRC = r"""
 #include "tf_mesh.h"
 extern "C" int h_grad(int sm, int s0, int sp, int um, int up) { return tfm_grad_axis(sm, s0, sp, um != 0, up != 0); }

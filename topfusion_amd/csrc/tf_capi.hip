@@ -1634,6 +1634,7 @@ extern "C" tf_status tf_reset_totals(tf_ctx* c)
 }
 
 // ---- mesh extraction (additions: the reference has no mesher; DESIGN.md §Mesh extraction) ------------
+// The kernels are tf_mesh.hip's, the PLY writers (tf_mesh_write_ply*) host code of their own in tf_mesh_ply.cpp.
 // count + prefix on the stream, then the total
 static tf_status mesh_count(tf_ctx* c, long long* n)
 {
@@ -1642,94 +1643,9 @@ static tf_status mesh_count(tf_ctx* c, long long* n)
     return sync_checked(c);
 }
 
-extern "C" tf_status tf_mesh_extract(tf_ctx* c, float* dev_triangles, long long capacity, long long* n_triangles)
+// tf_mesh_extract and tf_mesh_extract_attr, after the flush
+static tf_status mesh_extract(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity, long long* n_triangles)
 {
-    TF_FLUSH(c);
-    if (!c || !n_triangles || capacity < 0 || (capacity > 0 && !dev_triangles)) return TF_INVALID_ARG;
-    long long n = 0;
-    tf_status s = mesh_count(c, &n);
-    if (s != TF_OK) return s;
-    *n_triangles = n;
-    if (capacity == 0 || !dev_triangles || n == 0) return TF_OK;
-    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffer on stream 0
-    TF_CHECK(tfk_mesh_emit(c, dev_triangles, capacity));
-    return sync_checked(c);
-}
-
-// binary little-endian PLY: vertices welded by the exact bits of their three floats (-0.0f and 0.0f
-// stay apart), faces of int indices in the input order
-extern "C" tf_status tf_mesh_write_ply(const char* path, const float* host_triangles, long long n)
-{
-    if (!path || n < 0 || (n > 0 && !host_triangles) || n > (long long)(0x7fffffff / 3)) return TF_INVALID_ARG;
-    struct Key { uint32_t v[3]; };
-    const size_t nv = (size_t)n * 3;
-    // open addressing over the vertex bits; slots hold vertex index + 1
-    size_t cap = 16;
-    while (cap < nv * 2) cap <<= 1;
-    std::vector<int> slot, face;
-    std::vector<Key> verts;
-    try { slot.assign(cap, 0); face.resize(nv); verts.reserve(nv / 4 + 16); } catch (const std::bad_alloc&) { return TF_OOM; }
-    try {
-        for (size_t i = 0; i < nv; ++i) {
-            Key k;
-            memcpy(k.v, host_triangles + 3 * i, sizeof(k.v));
-            size_t h = (k.v[0] * 73856093u) ^ (k.v[1] * 19349669u) ^ (k.v[2] * 83492791u);
-            h ^= h >> 15;
-            for (h &= cap - 1;; h = (h + 1) & (cap - 1)) {
-                if (!slot[h]) { verts.push_back(k); slot[h] = (int)verts.size(); break; }
-                if (!memcmp(verts[(size_t)slot[h] - 1].v, k.v, sizeof(k.v))) break;
-            }
-            face[i] = slot[h] - 1;
-        }
-    } catch (const std::bad_alloc&) { return TF_OOM; }
-    FILE* f = fopen(path, "wb");
-    if (!f) return TF_INVALID_ARG;
-    bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\nelement vertex %zu\n"
-                         "property float x\nproperty float y\nproperty float z\nelement face %lld\n"
-                         "property list uchar int vertex_indices\nend_header\n", verts.size(), n) > 0;
-    ok = ok && (verts.empty() || fwrite(verts.data(), sizeof(Key), verts.size(), f) == verts.size());
-    std::vector<unsigned char> rec;
-    try { rec.resize((size_t)n * 13); } catch (const std::bad_alloc&) { fclose(f); return TF_OOM; }
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        rec[13 * i] = 3;
-        memcpy(&rec[13 * i + 1], &face[3 * i], 12);
-    }
-    ok = ok && (rec.empty() || fwrite(rec.data(), 1, rec.size(), f) == rec.size());
-    ok = (fclose(f) == 0) && ok;
-    return ok ? TF_OK : TF_INVALID_ARG;
-}
-
-extern "C" tf_status tf_mesh_save_ply(tf_ctx* c, const char* path)
-{
-    TF_FLUSH(c);
-    if (!c || !path) return TF_INVALID_ARG;
-    long long n = 0;
-    tf_status s = mesh_count(c, &n);
-    if (s != TF_OK) return s;
-    float* dev = nullptr;
-    float* host = nullptr;
-    if (n > 0) {
-        const size_t bytes = sizeof(float) * 9 * (size_t)n;
-        host = (float*)malloc(bytes);
-        if (!host) return TF_OOM;
-        if (hipMalloc((void**)&dev, bytes) != hipSuccess) { (void)hipGetLastError(); free(host); return TF_OOM; }
-        hipError_t e = tfk_mesh_emit(c, dev, n);
-        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
-        s = tf_from_hip(e);
-        const tf_status s2 = sync_checked(c);          // (the stream is idle before the buffer goes)
-        if (s == TF_OK) s = s2;
-        (void)hipFree(dev);
-    }
-    if (s == TF_OK) s = tf_mesh_write_ply(path, host, n);
-    free(host);
-    return s;
-}
-
-// ---- mesh extraction with per-vertex attributes (additions; DESIGN.md §Mesh extraction, attributes) ----
-extern "C" tf_status tf_mesh_extract_attr(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity,
-                                          long long* n_triangles)
-{
-    TF_FLUSH(c);
     const bool any = dev_triangles || dev_normals || dev_colours;
     if (!c || !n_triangles || capacity < 0 || (capacity > 0 && !any)) return TF_INVALID_ARG;
     if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
@@ -1747,59 +1663,51 @@ extern "C" tf_status tf_mesh_extract_attr(tf_ctx* c, float* dev_triangles, float
     return sync_checked(c);
 }
 
-// records of 3 (+ 3) (+ 1) dwords per vertex, welded by the exact bits of the whole record
-extern "C" tf_status tf_mesh_write_ply_attr(const char* path, const float* host_triangles, const float* host_normals,
-                                            const uint8_t* host_colours, long long n)
+extern "C" tf_status tf_mesh_extract(tf_ctx* c, float* dev_triangles, long long capacity, long long* n_triangles)
 {
-    if (!host_normals && !host_colours) return tf_mesh_write_ply(path, host_triangles, n);
-    if (!path || n < 0 || (n > 0 && !host_triangles) || n > (long long)(0x7fffffff / 3)) return TF_INVALID_ARG;
-    const size_t nv = (size_t)n * 3;
-    const size_t nw = 3 + (host_normals ? 3 : 0) + (host_colours ? 1 : 0);      // dwords per record
-    size_t cap = 16;
-    while (cap < nv * 2) cap <<= 1;
-    std::vector<int> slot, face;
-    std::vector<uint32_t> verts;                          // nw dwords per welded vertex
-    try { slot.assign(cap, 0); face.resize(nv); verts.reserve((nv / 4 + 16) * nw); } catch (const std::bad_alloc&) { return TF_OOM; }
-    try {
-        for (size_t i = 0; i < nv; ++i) {
-            uint32_t k[7];
-            memcpy(k, host_triangles + 3 * i, 12);
-            size_t w = 3;
-            if (host_normals) { memcpy(k + w, host_normals + 3 * i, 12); w += 3; }
-            if (host_colours) memcpy(k + w, host_colours + 4 * i, 4);
-            size_t h = 0;
-            for (size_t j = 0; j < nw; ++j) h = (h ^ k[j]) * 0x9e3779b1u;
-            h ^= h >> 15;
-            for (h &= cap - 1;; h = (h + 1) & (cap - 1)) {
-                if (!slot[h]) { verts.insert(verts.end(), k, k + nw); slot[h] = (int)(verts.size() / nw); break; }
-                if (!memcmp(&verts[((size_t)slot[h] - 1) * nw], k, 4 * nw)) break;
-            }
-            face[i] = slot[h] - 1;
-        }
-    } catch (const std::bad_alloc&) { return TF_OOM; }
-    FILE* f = fopen(path, "wb");
-    if (!f) return TF_INVALID_ARG;
-    bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\nelement vertex %zu\n"
-                         "property float x\nproperty float y\nproperty float z\n%s%selement face %lld\n"
-                         "property list uchar int vertex_indices\nend_header\n", verts.size() / nw,
-                      host_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
-                      host_colours ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "", n) > 0;
-    ok = ok && (verts.empty() || fwrite(verts.data(), 4, verts.size(), f) == verts.size());
-    std::vector<unsigned char> rec;
-    try { rec.resize((size_t)n * 13); } catch (const std::bad_alloc&) { fclose(f); return TF_OOM; }
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        rec[13 * i] = 3;
-        memcpy(&rec[13 * i + 1], &face[3 * i], 12);
-    }
-    ok = ok && (rec.empty() || fwrite(rec.data(), 1, rec.size(), f) == rec.size());
-    ok = (fclose(f) == 0) && ok;
-    return ok ? TF_OK : TF_INVALID_ARG;
+    TF_FLUSH(c);
+    return mesh_extract(c, dev_triangles, nullptr, nullptr, capacity, n_triangles);
 }
 
-extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attrs)
+extern "C" tf_status tf_mesh_extract_attr(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity,
+                                          long long* n_triangles)
 {
-    if (c && path && attrs == 0) return tf_mesh_save_ply(c, path);
     TF_FLUSH(c);
+    return mesh_extract(c, dev_triangles, dev_normals, dev_colours, capacity, n_triangles);
+}
+
+// What the tf_mesh_save_ply* share: `bytes` of output, written by emit(dev) on the context stream into a
+// temporary device buffer, brought to *host (malloc'd, the caller frees; nullptr when bytes == 0)
+template <class Emit>
+static tf_status mesh_download(tf_ctx* c, size_t bytes, char** host, Emit emit)
+{
+    *host = nullptr;
+    if (bytes == 0) return TF_OK;
+    char* dev = nullptr;
+    *host = (char*)malloc(bytes);
+    if (!*host) return TF_OOM;
+    if (hipMalloc((void**)&dev, bytes) != hipSuccess) { (void)hipGetLastError(); free(*host); *host = nullptr; return TF_OOM; }
+    hipError_t e = emit(dev);
+    if (e == hipSuccess) e = hipMemcpyAsync(*host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+    tf_status s = tf_from_hip(e);
+    const tf_status s2 = sync_checked(c);              // (the stream is idle before the buffer goes)
+    if (s == TF_OK) s = s2;
+    (void)hipFree(dev);
+    return s;
+}
+
+// The attribute column at `off` of the downloaded buffer when `want`ed, else nullptr.  An empty mesh has no
+// buffer: its columns are still declared in the file (a non-null dummy, never read).
+template <class T>
+static const T* mesh_column(const char* host, size_t off, bool want)
+{
+    static const float none = 0.0f;
+    return !want ? nullptr : host ? (const T*)(host + off) : (const T*)&none;
+}
+
+// tf_mesh_save_ply (attrs 0) and tf_mesh_save_ply_attr, after the flush
+static tf_status mesh_save_ply(tf_ctx* c, const char* path, int attrs)
+{
     if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS))) return TF_INVALID_ARG;
     if ((attrs & TF_MESH_COLOURS) && !c->p.voxel_rgb) return TF_INVALID_ARG;
     long long n = 0;
@@ -1808,28 +1716,27 @@ extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attr
     const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
     // one allocation each side: positions, then normals, then colours
     const size_t bt = sizeof(float) * 9 * (size_t)n, bn = nrm ? bt : 0, bc = col ? 12 * (size_t)n : 0;
-    char* dev = nullptr;
     char* host = nullptr;
-    if (n > 0) {
-        host = (char*)malloc(bt + bn + bc);
-        if (!host) return TF_OOM;
-        if (hipMalloc((void**)&dev, bt + bn + bc) != hipSuccess) { (void)hipGetLastError(); free(host); return TF_OOM; }
-        hipError_t e = tfk_mesh_emit_attr(c, (float*)dev, nrm ? (float*)(dev + bt) : nullptr, col ? (unsigned char*)(dev + bt + bn) : nullptr, n);
-        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, bt + bn + bc, hipMemcpyDeviceToHost, c->stream);
-        s = tf_from_hip(e);
-        const tf_status s2 = sync_checked(c);          // (the stream is idle before the buffer goes)
-        if (s == TF_OK) s = s2;
-        (void)hipFree(dev);
-    }
-    if (s == TF_OK) {
-        // n == 0: the attribute columns are still declared (non-null dummies, never read)
-        static const float none = 0.0f;
-        const float* hn = nrm ? (host ? (const float*)(host + bt) : &none) : nullptr;
-        const uint8_t* hc = col ? (host ? (const uint8_t*)(host + bt + bn) : (const uint8_t*)&none) : nullptr;
-        s = tf_mesh_write_ply_attr(path, (const float*)host, hn, hc, n);
-    }
+    s = mesh_download(c, bt + bn + bc, &host, [&](char* dev) {
+        if (!nrm && !col) return tfk_mesh_emit(c, (float*)dev, n);
+        return tfk_mesh_emit_attr(c, (float*)dev, nrm ? (float*)(dev + bt) : nullptr, col ? (unsigned char*)(dev + bt + bn) : nullptr, n);
+    });
+    if (s == TF_OK)
+        s = tf_mesh_write_ply_attr(path, (const float*)host, mesh_column<float>(host, bt, nrm), mesh_column<uint8_t>(host, bt + bn, col), n);
     free(host);
     return s;
+}
+
+extern "C" tf_status tf_mesh_save_ply(tf_ctx* c, const char* path)
+{
+    TF_FLUSH(c);
+    return mesh_save_ply(c, path, 0);
+}
+
+extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attrs)
+{
+    TF_FLUSH(c);
+    return mesh_save_ply(c, path, attrs);
 }
 
 // ---- indexed mesh extraction (additions; DESIGN.md §Mesh extraction, indexed) ---------------------------
@@ -1867,41 +1774,6 @@ extern "C" tf_status tf_mesh_extract_indexed(tf_ctx* c, float* dev_vertices, flo
     return sync_checked(c);
 }
 
-// the vertex table as given (no welding): records of 3 (+ 3) (+ 1) dwords, then the attributed writer's faces
-extern "C" tf_status tf_mesh_write_ply_indexed(const char* path, const float* host_vertices, const float* host_normals,
-                                               const uint8_t* host_colours, long long nv, const uint32_t* host_indices, long long nt)
-{
-    if (!path || nv < 0 || nt < 0 || (nv > 0 && !host_vertices) || (nt > 0 && !host_indices) || nv > 0x7fffffffLL) return TF_INVALID_ARG;
-    for (long long i = 0; i < 3 * nt; ++i)
-        if ((long long)host_indices[i] >= nv) return TF_INVALID_ARG;
-    const size_t nw = 3 + (host_normals ? 3 : 0) + (host_colours ? 1 : 0);      // dwords per record
-    std::vector<uint32_t> verts;
-    std::vector<unsigned char> rec;
-    try { verts.resize((size_t)nv * nw); rec.resize((size_t)nt * 13); } catch (const std::bad_alloc&) { return TF_OOM; }
-    for (size_t i = 0; i < (size_t)nv; ++i) {
-        uint32_t* k = &verts[i * nw];
-        memcpy(k, host_vertices + 3 * i, 12);
-        size_t w = 3;
-        if (host_normals) { memcpy(k + w, host_normals + 3 * i, 12); w += 3; }
-        if (host_colours) memcpy(k + w, host_colours + 4 * i, 4);
-    }
-    for (size_t i = 0; i < (size_t)nt; ++i) {
-        rec[13 * i] = 3;
-        memcpy(&rec[13 * i + 1], host_indices + 3 * i, 12);
-    }
-    FILE* f = fopen(path, "wb");
-    if (!f) return TF_INVALID_ARG;
-    bool ok = fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment topfusion mesh\nelement vertex %lld\n"
-                         "property float x\nproperty float y\nproperty float z\n%s%selement face %lld\n"
-                         "property list uchar int vertex_indices\nend_header\n", nv,
-                      host_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "",
-                      host_colours ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "", nt) > 0;
-    ok = ok && (verts.empty() || fwrite(verts.data(), 4, verts.size(), f) == verts.size());
-    ok = ok && (rec.empty() || fwrite(rec.data(), 1, rec.size(), f) == rec.size());
-    ok = (fclose(f) == 0) && ok;
-    return ok ? TF_OK : TF_INVALID_ARG;
-}
-
 extern "C" tf_status tf_mesh_save_ply_indexed(tf_ctx* c, const char* path, int attrs)
 {
     TF_FLUSH(c);
@@ -1913,28 +1785,15 @@ extern "C" tf_status tf_mesh_save_ply_indexed(tf_ctx* c, const char* path, int a
     if (nv > 0x7fffffffLL) return TF_INDEX_RANGE;       // (the PLY's indices are int)
     const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
     // one allocation each side: positions, normals, colours, indices
-    const size_t bp = 12 * (size_t)nv, bn = nrm ? bp : 0, bc = col ? 4 * (size_t)nv : 0, bi = 12 * (size_t)nt, all = bp + bn + bc + bi;
-    char* dev = nullptr;
+    const size_t bp = 12 * (size_t)nv, bn = nrm ? bp : 0, bc = col ? 4 * (size_t)nv : 0, bi = 12 * (size_t)nt;
     char* host = nullptr;
-    if (nt > 0) {
-        host = (char*)malloc(all);
-        if (!host) return TF_OOM;
-        if (hipMalloc((void**)&dev, all) != hipSuccess) { (void)hipGetLastError(); free(host); return TF_OOM; }
-        hipError_t e = tfk_mesh_emit_vertices(c, (float*)dev, nrm ? (float*)(dev + bp) : nullptr, col ? (unsigned char*)(dev + bp + bn) : nullptr, nv);
-        if (e == hipSuccess) e = tfk_mesh_emit_indices(c, (unsigned*)(dev + bp + bn + bc), nt);
-        if (e == hipSuccess) e = hipMemcpyAsync(host, dev, all, hipMemcpyDeviceToHost, c->stream);
-        s = tf_from_hip(e);
-        const tf_status s2 = sync_checked(c);          // (the stream is idle before the buffer goes)
-        if (s == TF_OK) s = s2;
-        (void)hipFree(dev);
-    }
-    if (s == TF_OK) {
-        // nt == 0: the attribute columns are still declared (non-null dummies, never read)
-        static const float none = 0.0f;
-        const float* hn = nrm ? (host ? (const float*)(host + bp) : &none) : nullptr;
-        const uint8_t* hc = col ? (host ? (const uint8_t*)(host + bp + bn) : (const uint8_t*)&none) : nullptr;
-        s = tf_mesh_write_ply_indexed(path, (const float*)host, hn, hc, nt > 0 ? nv : 0, host ? (const uint32_t*)(host + bp + bn + bc) : nullptr, nt);
-    }
+    s = mesh_download(c, nt > 0 ? bp + bn + bc + bi : 0, &host, [&](char* dev) {
+        const hipError_t e = tfk_mesh_emit_vertices(c, (float*)dev, nrm ? (float*)(dev + bp) : nullptr, col ? (unsigned char*)(dev + bp + bn) : nullptr, nv);
+        return e == hipSuccess ? tfk_mesh_emit_indices(c, (unsigned*)(dev + bp + bn + bc), nt) : e;
+    });
+    if (s == TF_OK)
+        s = tf_mesh_write_ply_indexed(path, (const float*)host, mesh_column<float>(host, bp, nrm), mesh_column<uint8_t>(host, bp + bn, col),
+                                      nt > 0 ? nv : 0, host ? (const uint32_t*)(host + bp + bn + bc) : nullptr, nt);
     free(host);
     return s;
 }

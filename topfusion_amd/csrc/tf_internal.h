@@ -594,7 +594,6 @@ hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsig
 // the indexed form: tfk_mesh_count plus the edge marks and the vertex count + prefix (the vertex total lands
 // in meshVBase[n_total]); then the vertex table's columns (positions, normals, RGBA; nullptr skips one)
 // clipped at `capacity` vertices, and three u32 vertex numbers per triangle clipped at `capacity` triangles
-hipError_t tfk_mesh_prefix(tf_ctx* c, const long long* count, const long long* groupTot, long long* base);   // k_mesh_prefix alone
 hipError_t tfk_mesh_index_count(tf_ctx* c);
 hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity);
 hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity);

@@ -1,7 +1,10 @@
 // tf_mesh.h -- the per-cube part of mesh extraction (DESIGN.md §Mesh extraction): marching tetrahedra on
 // the Kuhn split of a voxel cube.  No reference counterpart (the reference has no mesher).  Plain
-// functions of eight corner voxels, shared by the count and the emit kernels of tf_mesh.hip; also
-// compilable as host C++ (the case rules can then be checked without a GPU).
+// functions of eight corner voxels, shared by every kernel of tf_mesh.hip; also compilable as host C++
+// (the case rules can then be checked without a GPU).  Each rule is written once: the case table is
+// decoded by tfm_tet_emit_edges alone, the six tetrahedra are driven by tfm_cube_emit_edges alone, a
+// corner's sdf is selected by tfm_corner_sdf, an edge's weight is tfm_edge_t; positions, attributes
+// and indices are emit functors over that walk.
 #pragma once
 
 #include <math.h>
@@ -9,9 +12,11 @@
 #if defined(__HIPCC__)
 #define TFM_HD __host__ __device__ __forceinline__
 #define TFM_TABLE static __constant__ const
+#define TFM_UNROLL _Pragma("unroll")        // on the three-vertex loops: their small arrays must never be indexed at run time
 #else
 #define TFM_HD inline
 #define TFM_TABLE static constexpr
+#define TFM_UNROLL
 #endif
 
 // Tetrahedron k of the cube, axis permutation (a, b, c) in the order xyz xzy yxz yzx zxy zyx: corners
@@ -113,58 +118,73 @@ TFM_HD int tfm_cube_count(const TfmCube& q)
            tfm_case_tris(tfm_tet_case<3>(m)) + tfm_case_tris(tfm_tet_case<4>(m)) + tfm_case_tris(tfm_tet_case<5>(m));
 }
 
-// The vertex on the edge from the cube corner `lo` (sdf sp, global voxel gx, gy, gz of the cube's
-// corner 0) to `hi` (sdf sq): t = RN(sp / (sp - sq)) (the difference in int, exact in float), then per
-// axis RN(RN(g + t) * voxelSize) where the edge moves, RN(g * voxelSize) where it does not.  Both
-// cubes (and all tetrahedra) that share the edge compute the same three floats.
-TFM_HD void tfm_vertex(unsigned lo, unsigned hi, int sp, int sq, int gx, int gy, int gz, float vs, float* out)
-{
-    const float t = (float)sp / (float)(sp - sq);
-    const unsigned d = hi & ~lo;
-    const float px = (float)(gx + (int)(lo & 1)), py = (float)(gy + (int)(lo >> 1 & 1)), pz = (float)(gz + (int)(lo >> 2 & 1));
-    const float ax = px + t, ay = py + t, az = pz + t;
-    out[0] = ((d & 1) ? ax : px) * vs;
-    out[1] = ((d & 2) ? ay : py) * vs;
-    out[2] = ((d & 4) ? az : pz) * vs;
-}
-
-// Tetrahedron K's triangles of the cube through emit(const float tri[9]), in case order; returns
-// their number.  The cube must be valid.
+// ---- the triangle walk (the only decoder of tfm_cases) ------------------------------------------------
+// Tetrahedron K's triangles through emit(const unsigned lo[3], const unsigned hi[3]) -- per triangle
+// vertex the cube corners its edge joins (lo a subset of hi) -- in case order; returns their number.
+// Every emission (positions, attributes, indices) is a functor over this walk.
 template <int K, class Emit>
-TFM_HD int tfm_tet_emit(const TfmCube& q, unsigned inside8, int gx, int gy, int gz, float vs, Emit& emit)
+TFM_HD int tfm_tet_emit_edges(unsigned inside8, Emit& emit)
 {
     constexpr unsigned corners = tfm_tet_corners(K);
     const unsigned info = tfm_cases[tfm_tet_case<K>(inside8)];
     const int n = (int)(info & 3);
     const bool flip = ((info >> 2 & 1) != 0) != tfm_tet_negative(K);
     for (int tr = 0; tr < n; ++tr) {
-        float tri[9];
+        unsigned lo[3], hi[3];
+        TFM_UNROLL               // (lo / hi stay registers only while v is a constant)
         for (int v = 0; v < 3; ++v) {
             // triangle 0: v0 v1 v2, triangle 1: v0 v2 v3; flipped: the last two swapped
             const int w = v == 0 ? 0 : (flip ? 3 - v : v) + tr;
             const unsigned e = info >> (4 + 4 * w) & 15u;
-            const unsigned lo = corners >> (3 * (e & 3)) & 7u, hi = corners >> (3 * (e >> 2)) & 7u;
-            int sp = q.sdf[0], sq = q.sdf[0];
-            for (int i = 1; i < 8; ++i) { sp = lo == (unsigned)i ? q.sdf[i] : sp; sq = hi == (unsigned)i ? q.sdf[i] : sq; }
-            tfm_vertex(lo, hi, sp, sq, gx, gy, gz, vs, tri + 3 * v);
+            lo[v] = corners >> (3 * (e & 3)) & 7u;
+            hi[v] = corners >> (3 * (e >> 2)) & 7u;
         }
-        emit(tri);
+        emit(lo, hi);
     }
     return n;
 }
 
+// the six tetrahedra of a cube; 0 triangles when the cube is not valid
 template <class Emit>
-TFM_HD int tfm_cube_emit(const TfmCube& q, int gx, int gy, int gz, float vs, Emit& emit)
+TFM_HD int tfm_cube_emit_edges(const TfmCube& q, Emit& emit)
 {
     if (!q.valid) return 0;
     const unsigned m = tfm_inside_mask(q);
-    int n = tfm_tet_emit<0>(q, m, gx, gy, gz, vs, emit);
-    n += tfm_tet_emit<1>(q, m, gx, gy, gz, vs, emit);
-    n += tfm_tet_emit<2>(q, m, gx, gy, gz, vs, emit);
-    n += tfm_tet_emit<3>(q, m, gx, gy, gz, vs, emit);
-    n += tfm_tet_emit<4>(q, m, gx, gy, gz, vs, emit);
-    n += tfm_tet_emit<5>(q, m, gx, gy, gz, vs, emit);
+    int n = tfm_tet_emit_edges<0>(m, emit);
+    n += tfm_tet_emit_edges<1>(m, emit);
+    n += tfm_tet_emit_edges<2>(m, emit);
+    n += tfm_tet_emit_edges<3>(m, emit);
+    n += tfm_tet_emit_edges<4>(m, emit);
+    n += tfm_tet_emit_edges<5>(m, emit);
     return n;
+}
+
+// The sdf at the cube corners lo and hi (0 .. 7, run-time values) by select chains: q.sdf[] is never
+// indexed with a run-time value, so it stays in registers.  (Both chains read each q.sdf[i] once, in one
+// loop: a load with a single select behind it is what a compiler turns back into an indexed load.)
+TFM_HD void tfm_corner_sdf(const TfmCube& q, unsigned lo, unsigned hi, int& sp, int& sq)
+{
+    sp = sq = q.sdf[0];
+    for (int i = 1; i < 8; ++i) { sp = lo == (unsigned)i ? q.sdf[i] : sp; sq = hi == (unsigned)i ? q.sdf[i] : sq; }
+}
+
+// the interpolation weight of an edge whose ends have the sdf sp and sq (the difference in int, exact in
+// float): the one float that places the vertex and weighs its attributes
+TFM_HD float tfm_edge_t(int sp, int sq) { return (float)sp / (float)(sp - sq); }
+
+// The vertex on the edge from the cube corner `lo` (sdf sp, global voxel gx, gy, gz of the cube's
+// corner 0) to `hi` (sdf sq): t = tfm_edge_t, then per axis RN(RN(g + t) * voxelSize) where the edge
+// moves, RN(g * voxelSize) where it does not.  Both cubes (and all tetrahedra) that share the edge
+// compute the same three floats.
+TFM_HD void tfm_vertex(unsigned lo, unsigned hi, int sp, int sq, int gx, int gy, int gz, float vs, float* out)
+{
+    const float t = tfm_edge_t(sp, sq);
+    const unsigned d = hi & ~lo;
+    const float px = (float)(gx + (int)(lo & 1)), py = (float)(gy + (int)(lo >> 1 & 1)), pz = (float)(gz + (int)(lo >> 2 & 1));
+    const float ax = px + t, ay = py + t, az = pz + t;
+    out[0] = ((d & 1) ? ax : px) * vs;
+    out[1] = ((d & 2) ? ay : py) * vs;
+    out[2] = ((d & 4) ? az : pz) * vs;
 }
 
 // ---- per-vertex attributes (DESIGN.md §Mesh extraction, attributes) ---------------------------------
@@ -186,9 +206,6 @@ TFM_HD int tfm_grad_axis_packed(unsigned vm, unsigned v0, unsigned vp)
     return tfm_grad_axis((int)(short)(vm & 0xffffu), (int)(short)(v0 & 0xffffu), (int)(short)(vp & 0xffffu), (vm >> 16) != 0,
                          (vp >> 16) != 0);
 }
-
-// the interpolation weight of the edge, the float tfm_vertex places the vertex with
-TFM_HD float tfm_edge_t(int sp, int sq) { return (float)sp / (float)(sp - sq); }
 
 // N_a = RN(Gp_a + RN(t (Gq_a - Gp_a))) (the difference in int, exact in float), normalised by
 // L = sqrt(RN(RN(Nx Nx + Ny Ny) + Nz Nz)) with IEEE sqrt and division; (0, 0, 0) when L == 0
@@ -228,56 +245,55 @@ TFM_HD unsigned tfm_colour(float t, unsigned wp, unsigned wq)
     return 0u;
 }
 
-// tfm_tet_emit with attributes.  Src gives the lattice data at a cube corner (0..7):
+// ---- triangles as floats: an emit functor over the edge walk --------------------------------------------
+// Src gives the lattice data at a cube corner (0 .. 7):
 //   static constexpr bool normals, colours;  void grad(unsigned corner, int g[3]) const;
 //   unsigned colour(unsigned corner) const
 // and emit receives (const float tri[9], const float nrm[9], const unsigned rgba[3]); what Src does not
-// provide is passed as zeros.  Positions, order and count are tfm_tet_emit's.
-template <int K, class Src, class Emit>
-TFM_HD int tfm_tet_emit_attr(const TfmCube& q, unsigned inside8, int gx, int gy, int gz, float vs, const Src& src, Emit& emit)
-{
-    constexpr unsigned corners = tfm_tet_corners(K);
-    const unsigned info = tfm_cases[tfm_tet_case<K>(inside8)];
-    const int n = (int)(info & 3);
-    const bool flip = ((info >> 2 & 1) != 0) != tfm_tet_negative(K);
-    for (int tr = 0; tr < n; ++tr) {
+// provide is passed as zeros.  TfmNoAttr provides nothing: positions only.
+struct TfmNoAttr {
+    static constexpr bool normals = false, colours = false;
+    TFM_HD void grad(unsigned, int*) const {}
+    TFM_HD unsigned colour(unsigned) const { return 0u; }
+};
+
+template <class Src, class Emit>
+struct TfmVertexEmit {
+    const TfmCube& q;
+    int gx, gy, gz;              // the global voxel of the cube's corner 0
+    float vs;
+    const Src& src;
+    Emit& emit;
+    TFM_HD void operator()(const unsigned* lo, const unsigned* hi)
+    {
         float tri[9], nrm[9];
         unsigned rgba[3];
+        TFM_UNROLL               // (a rolled loop indexes tri / nrm / rgba with a run-time value: they leave the registers)
         for (int v = 0; v < 3; ++v) {
-            const int w = v == 0 ? 0 : (flip ? 3 - v : v) + tr;
-            const unsigned e = info >> (4 + 4 * w) & 15u;
-            const unsigned lo = corners >> (3 * (e & 3)) & 7u, hi = corners >> (3 * (e >> 2)) & 7u;
-            int sp = q.sdf[0], sq = q.sdf[0];
-            for (int i = 1; i < 8; ++i) { sp = lo == (unsigned)i ? q.sdf[i] : sp; sq = hi == (unsigned)i ? q.sdf[i] : sq; }
-            tfm_vertex(lo, hi, sp, sq, gx, gy, gz, vs, tri + 3 * v);
+            int sp, sq;
+            tfm_corner_sdf(q, lo[v], hi[v], sp, sq);
+            tfm_vertex(lo[v], hi[v], sp, sq, gx, gy, gz, vs, tri + 3 * v);
             const float t = tfm_edge_t(sp, sq);
             if (Src::normals) {
                 int gp[3], gq[3];
-                src.grad(lo, gp);
-                src.grad(hi, gq);
+                src.grad(lo[v], gp);
+                src.grad(hi[v], gq);
                 tfm_normal(t, gp, gq, nrm + 3 * v);
             } else {
                 nrm[3 * v] = nrm[3 * v + 1] = nrm[3 * v + 2] = 0.0f;
             }
-            rgba[v] = Src::colours ? tfm_colour(t, src.colour(lo), src.colour(hi)) : 0u;
+            rgba[v] = Src::colours ? tfm_colour(t, src.colour(lo[v]), src.colour(hi[v])) : 0u;
         }
         emit(tri, nrm, rgba);
     }
-    return n;
-}
+};
 
+// the cube's triangles with Src's attributes; order and count are tfm_cube_emit_edges'
 template <class Src, class Emit>
 TFM_HD int tfm_cube_emit_attr(const TfmCube& q, int gx, int gy, int gz, float vs, const Src& src, Emit& emit)
 {
-    if (!q.valid) return 0;
-    const unsigned m = tfm_inside_mask(q);
-    int n = tfm_tet_emit_attr<0>(q, m, gx, gy, gz, vs, src, emit);
-    n += tfm_tet_emit_attr<1>(q, m, gx, gy, gz, vs, src, emit);
-    n += tfm_tet_emit_attr<2>(q, m, gx, gy, gz, vs, src, emit);
-    n += tfm_tet_emit_attr<3>(q, m, gx, gy, gz, vs, src, emit);
-    n += tfm_tet_emit_attr<4>(q, m, gx, gy, gz, vs, src, emit);
-    n += tfm_tet_emit_attr<5>(q, m, gx, gy, gz, vs, src, emit);
-    return n;
+    TfmVertexEmit<Src, Emit> ve = { q, gx, gy, gz, vs, src, emit };
+    return tfm_cube_emit_edges(q, ve);
 }
 
 // ---- indexed extraction (DESIGN.md §Mesh extraction, indexed) ----------------------------------------
@@ -313,7 +329,7 @@ TFM_HD unsigned tfm_edge_rank(unsigned word, unsigned prefix, unsigned bit)
 // The sign-changing Kuhn edges of the cube whose corner 0 is the tile's lattice point (x, y, z), 0 .. 7
 // each, through mark(TfmEdgeRef): the 19 corner pairs lo, hi = lo | dc with lo & dc == 0.  Each is an
 // edge of one of the six tetrahedra at least, and a tetrahedron puts a triangle vertex on every edge
-// of its own whose ends differ, so these are exactly the edges tfm_cube_emit's triangles touch.
+// of its own whose ends differ, so these are exactly the edges tfm_cube_emit_edges' triangles touch.
 template <class Mark>
 TFM_HD void tfm_cube_mark(const TfmCube& q, int x, int y, int z, Mark& mark)
 {
@@ -327,42 +343,6 @@ TFM_HD void tfm_cube_mark(const TfmCube& q, int x, int y, int z, Mark& mark)
         }
 }
 
-// tfm_tet_emit without the floats: tetrahedron K's triangles through emit(const unsigned lo[3], const
-// unsigned hi[3]) -- per triangle vertex the cube corners its edge joins (lo a subset of hi) -- in the same
-// order, with the same per-triangle vertex order.
-template <int K, class Emit>
-TFM_HD int tfm_tet_emit_edges(unsigned inside8, Emit& emit)
-{
-    constexpr unsigned corners = tfm_tet_corners(K);
-    const unsigned info = tfm_cases[tfm_tet_case<K>(inside8)];
-    const int n = (int)(info & 3);
-    const bool flip = ((info >> 2 & 1) != 0) != tfm_tet_negative(K);
-    for (int tr = 0; tr < n; ++tr) {
-        unsigned lo[3], hi[3];
-        for (int v = 0; v < 3; ++v) {
-            const int w = v == 0 ? 0 : (flip ? 3 - v : v) + tr;
-            const unsigned e = info >> (4 + 4 * w) & 15u;
-            lo[v] = corners >> (3 * (e & 3)) & 7u;
-            hi[v] = corners >> (3 * (e >> 2)) & 7u;
-        }
-        emit(lo, hi);
-    }
-    return n;
-}
-
-template <class Emit>
-TFM_HD int tfm_cube_emit_edges(const TfmCube& q, Emit& emit)
-{
-    if (!q.valid) return 0;
-    const unsigned m = tfm_inside_mask(q);
-    int n = tfm_tet_emit_edges<0>(m, emit);
-    n += tfm_tet_emit_edges<1>(m, emit);
-    n += tfm_tet_emit_edges<2>(m, emit);
-    n += tfm_tet_emit_edges<3>(m, emit);
-    n += tfm_tet_emit_edges<4>(m, emit);
-    n += tfm_tet_emit_edges<5>(m, emit);
-    return n;
-}
 
 // The vertex of the edge (p, dc) from its lower end: p's global voxel coordinate, the sdf shorts at p and
 // q = p + d.  tfm_vertex with the cube's corner 0 at p, so the bits every cube sharing the edge computes.

@@ -1,7 +1,10 @@
 // tf_mesh.hip -- mesh extraction from the voxel block hash for gfx950 (an addition: the reference has no
 // mesher).  Marching tetrahedra on the Kuhn split of every voxel cube (tf_mesh.h, DESIGN.md §Mesh
-// extraction), as three plain launches on the context stream:
+// extraction), as plain launches on the context stream.  The kernels are assembled from the pieces of
+// tf_mesh_dev.h (live list, staging, cube read, scan, gradient fill, stores) and differ in what they do
+// with an entry's cubes.
 //
+// The triangle soup:
 //   k_mesh_count  : per live hash entry (ptr >= 0) the 9 x 9 x 9 corner voxels of its 512 cubes staged in
 //                   LDS (own block + up to seven neighbours, found through the block grid, outside it by
 //                   the hash walk), every cube classified, the entry's triangle count (64-bit) written;
@@ -9,12 +12,20 @@
 //   k_mesh_prefix : exclusive scan of the counts in entry order -> every entry's base, and the total
 //   k_mesh_emit   : the classification again, an exclusive scan over the 512 voxels inside the
 //                   workgroup, triangles written at base + offset while below the caller's capacity
-//
 //   k_mesh_emit_attr<NORMALS, COLOURS> : k_mesh_emit with per-vertex normals (TSDF gradient) and / or colours
-//                   (colour plane) beside the positions, from a larger LDS tile of its own
+//                   (colour plane) beside the positions, from the larger tile (mesh_stage_attr)
 //
-//   k_mesh_mark, k_mesh_vcount, k_mesh_emit_vertices<NORMALS, COLOURS>, k_mesh_emit_indices : the indexed
-//                   form of the same mesh (shared vertices, u32 indices), in tf_mesh_indexed.hip
+// The indexed form (shared vertices, u32 indices; DESIGN.md §Mesh extraction, indexed).  A vertex is its
+// Kuhn edge (tf_mesh.h): per VBA block a mask of 512 x 7 edge bits (TFM_EDGE_WORDS words, indexed by the
+// block number ptr) and the words' exclusive popcount prefixes; per hash entry its vertex count and
+// base, by k_mesh_prefix on a second pair of arrays.
+//   k_mesh_mark          : k_mesh_count's loop; every valid cube ORs its sign-changing Kuhn edges into the
+//                          owners' masks -- gathered in LDS, flushed with one global atomicOr per non-zero
+//                          word (integer OR: the result does not depend on the order of arrival)
+//   k_mesh_vcount        : one wave per live entry: the 112 words' popcounts, scanned -> prefixes, count
+//   k_mesh_emit_vertices : per live entry with vertices, each thread its voxel's seven edges; a set bit is
+//                          the vertex base + prefix + popcount below
+//   k_mesh_emit_indices  : k_mesh_emit's structure; a triangle vertex (lo, hi) -> owner block, bit, index
 //
 // No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) is only read.
 #include "tf_mesh_dev.h"
@@ -26,6 +37,25 @@ __device__ __forceinline__ int wave_sum(int v)
     return v;
 }
 
+// the live-list predicates: entries with a block (a dead one gets its count of 0 here, where `count` is
+// given), and entries with output below the capacity (count and base are uniform per entry)
+struct MeshHasBlock {
+    const TfHashEntry* hash;
+    long long* count;            // may be nullptr
+    __device__ __forceinline__ bool operator()(int idx) const
+    {
+        if (hash[idx].ptr >= 0) return true;
+        if (count) count[idx] = 0;
+        return false;
+    }
+};
+struct MeshHasOutput {
+    const long long* count;
+    const long long* base;
+    long long capacity;
+    __device__ __forceinline__ bool operator()(int idx) const { return count[idx] > 0 && base[idx] < capacity; }
+};
+
 __global__ __launch_bounds__(TFM_WG) void k_mesh_count(MeshScene s, long long* __restrict__ count, long long* __restrict__ groupTot)
 {
     __shared__ unsigned tile[TFM_TILE3];
@@ -36,22 +66,12 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_count(MeshScene s, long long* _
     const int t = threadIdx.x;
     const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        __syncthreads();
-        if (t == 0) nlive = 0;
-        __syncthreads();
-        const int idx = g * TFM_WG + t;
-        if (idx < s.n_total) {
-            if (s.v.hash[idx].ptr >= 0) live[atomicAdd(&nlive, 1)] = idx;      // (any order: each entry's count stands alone)
-            else count[idx] = 0;
-        }
-        __syncthreads();
-        const int n = nlive;
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasBlock{ s.v.hash, count });      // (any order: each entry's count stands alone)
         long long tot = 0;
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
-            const TfHashEntry e = s.v.hash[ei];
-            mesh_stage(s, e, tile, nvoff);
-            const int c = wave_sum(tfm_cube_count(mesh_cube(tile)));
+            mesh_stage(s, ei, s.v.hash[ei], tile, nvoff);
+            const int c = wave_sum(tfm_cube_count(mesh_cube<TFM_TILE, 0>(tile)));
             if ((t & 63) == 0) wsum[t >> 6] = c;
             __syncthreads();
             if (t == 0) {
@@ -108,98 +128,13 @@ __global__ __launch_bounds__(256) void k_mesh_prefix(const long long* __restrict
     if (last == n_total && t == 0) base[n_total] = carry;
 }
 
-// 4-byte aligned 16-byte store: a triangle is 36 bytes, so its address is only dword aligned
-typedef float tfm_f4 __attribute__((ext_vector_type(4), aligned(4)));
-
-struct MeshWriter {
-    float* out;
-    long long idx;           // the next triangle's index
-    long long capacity;
-    __device__ __forceinline__ void operator()(const float* tri)
-    {
-        if (idx < capacity) {
-            float* p = out + idx * 9;
-            tfm_f4 a, b;
-            a.x = tri[0]; a.y = tri[1]; a.z = tri[2]; a.w = tri[3];
-            b.x = tri[4]; b.y = tri[5]; b.z = tri[6]; b.w = tri[7];
-            *reinterpret_cast<tfm_f4*>(p) = a;
-            *reinterpret_cast<tfm_f4*>(p + 4) = b;
-            p[8] = tri[8];
-        }
-        ++idx;
-    }
-};
-
-__global__ __launch_bounds__(TFM_WG) void k_mesh_emit(MeshScene s, const long long* __restrict__ count, const long long* __restrict__ base,
-                                                      float* __restrict__ out, long long capacity, float voxelSize)
-{
-    __shared__ unsigned tile[TFM_TILE3];
-    __shared__ int nvoff[8];
-    __shared__ int live[TFM_WG];
-    __shared__ int nlive;
-    __shared__ int wsum[TFM_WG / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
-    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        __syncthreads();
-        if (t == 0) nlive = 0;
-        __syncthreads();
-        const int idx = g * TFM_WG + t;
-        // entries with triangles below the capacity (count and base are uniform per entry)
-        if (idx < s.n_total && count[idx] > 0 && base[idx] < capacity) live[atomicAdd(&nlive, 1)] = idx;
-        __syncthreads();
-        const int n = nlive;
-        for (int k = 0; k < n; ++k) {
-            const int ei = live[k];
-            const TfHashEntry e = s.v.hash[ei];
-            mesh_stage(s, e, tile, nvoff);
-            const TfmCube q = mesh_cube(tile);
-            const int mine = tfm_cube_count(q);
-            // exclusive scan over the 512 voxels: inclusive within the wave, then the lower waves' sums
-            int inc = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int up = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += up;
-            }
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            int off = inc - mine;
-            for (int w = 0; w < wave; ++w) off += wsum[w];
-            if (mine) {
-                MeshWriter wr = { out, base[ei] + off, capacity };
-                tfm_cube_emit(q, e.x * TF_BLK + (t & 7), e.y * TF_BLK + (t >> 3 & 7), e.z * TF_BLK + (t >> 6), voxelSize, wr);
-            }
-        }
-    }
-}
-
-// ---- the emit pass with per-vertex attributes (normals, colours) -------------------------------------
-// Its own kernel beside k_mesh_emit: the larger tile, the gradients and the colour words live in its
-// LDS alone.  Per entry: the 11 x 11 x 11 voxels around the block (local coordinates -1 .. 9; only points
-// with at most one coordinate outside 0 .. 8 are read, the others never are) from the block and up to 19
-// neighbours, the 9 x 9 x 9 integer gradients formed once from it, the colour words of the same 9 x 9 x 9
-// corners; then k_mesh_emit's classification and scan, and per triangle vertex two LDS gradient / colour
-// reads per end.  (The tile itself -- mesh_stage_attr, MeshAttrSrc -- is in tf_mesh_dev.h: the indexed
-// form's vertex pass stages the same one.)
-__device__ __forceinline__ void mesh_store9(float* p, const float* v)
-{
-    tfm_f4 a, b;
-    a.x = v[0]; a.y = v[1]; a.z = v[2]; a.w = v[3];
-    b.x = v[4]; b.y = v[5]; b.z = v[6]; b.w = v[7];
-    *reinterpret_cast<tfm_f4*>(p) = a;
-    *reinterpret_cast<tfm_f4*>(p + 4) = b;
-    p[8] = v[8];
-}
-
-typedef unsigned tfm_u3 __attribute__((ext_vector_type(3), aligned(4)));
-
+// a triangle's positions (tri may be nullptr, uniform), normals and colours, clipped at the capacity
 template <bool NORMALS, bool COLOURS>
 struct MeshAttrWriter {
-    float* tri;                  // may be nullptr (uniform)
+    float* tri;
     float* nrm;
     unsigned* col;
-    long long idx;
+    long long idx;               // the next triangle's index
     long long capacity;
     __device__ __forceinline__ void operator()(const float* t9, const float* n9, const unsigned* rgba)
     {
@@ -216,6 +151,38 @@ struct MeshAttrWriter {
     }
 };
 
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit(MeshScene s, const long long* __restrict__ count, const long long* __restrict__ base,
+                                                      float* __restrict__ out, long long capacity, float voxelSize)
+{
+    __shared__ unsigned tile[TFM_TILE3];
+    __shared__ int nvoff[8];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ int wsum[TFM_WG / 64];
+    const int t = threadIdx.x;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasOutput{ count, base, capacity });
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            const TfHashEntry e = s.v.hash[ei];
+            mesh_stage(s, ei, e, tile, nvoff);
+            const TfmCube q = mesh_cube<TFM_TILE, 0>(tile);
+            const int mine = tfm_cube_count(q);
+            const int off = mesh_scan(mine, wsum);
+            if (mine) {
+                MeshAttrWriter<false, false> wr = { out, nullptr, nullptr, base[ei] + off, capacity };
+                tfm_cube_emit_attr(q, e.x * TF_BLK + (t & 7), e.y * TF_BLK + (t >> 3 & 7), e.z * TF_BLK + (t >> 6), voxelSize, TfmNoAttr(), wr);
+            }
+        }
+    }
+}
+
+// The emit pass with per-vertex attributes: per entry the 11 x 11 x 11 voxels around the block (local
+// coordinates -1 .. 9; only points with at most one coordinate outside 0 .. 8 are read) from the block and
+// up to 19 neighbours, the 9 x 9 x 9 integer gradients formed once from it, the colour words of the same
+// 9 x 9 x 9 corners; then k_mesh_emit's classification and scan, and per triangle vertex two LDS gradient /
+// colour reads per end.
 template <bool NORMALS, bool COLOURS>
 __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const unsigned* __restrict__ rgb, const long long* __restrict__ count,
                                                            const long long* __restrict__ base, float* __restrict__ outTri,
@@ -229,43 +196,18 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const un
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
     __shared__ int wsum[TFM_WG / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        __syncthreads();
-        if (t == 0) nlive = 0;
-        __syncthreads();
-        const int idx = g * TFM_WG + t;
-        if (idx < s.n_total && count[idx] > 0 && base[idx] < capacity) live[atomicAdd(&nlive, 1)] = idx;
-        __syncthreads();
-        const int n = nlive;
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasOutput{ count, base, capacity });
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
             const TfHashEntry e = s.v.hash[ei];
             mesh_stage_attr<NORMALS, COLOURS>(s, rgb, e, tile, ctile, nvoff);
-            if (NORMALS) {
-                // the 9^3 lattice gradients, once per entry (the tile is complete: mesh_stage_attr ends in a barrier)
-                for (int i = t; i < TFM_TILE3; i += TFM_WG) {
-                    const int z = i / (TFM_TILE * TFM_TILE), r = i - z * (TFM_TILE * TFM_TILE), y = r / TFM_TILE, x = r - y * TFM_TILE;
-                    const int c = (x + 1) + TFM_ATILE * (y + 1) + TFM_ATILE * TFM_ATILE * (z + 1);
-                    const unsigned v0 = tile[c];
-                    grad3[i] = tfm_grad_axis_packed(tile[c - 1], v0, tile[c + 1]);
-                    grad3[TFM_TILE3 + i] = tfm_grad_axis_packed(tile[c - TFM_ATILE], v0, tile[c + TFM_ATILE]);
-                    grad3[2 * TFM_TILE3 + i] = tfm_grad_axis_packed(tile[c - TFM_ATILE * TFM_ATILE], v0, tile[c + TFM_ATILE * TFM_ATILE]);
-                }
-            }
-            const TfmCube q = mesh_cube_attr(tile);
+            if (NORMALS) mesh_grad_fill(tile, grad3);
+            const TfmCube q = mesh_cube<TFM_ATILE, 1>(tile);
             const int mine = tfm_cube_count(q);
-            int inc = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int up = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += up;
-            }
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();         // wsum, and the gradients
-            int off = inc - mine;
-            for (int w = 0; w < wave; ++w) off += wsum[w];
+            const int off = mesh_scan(mine, wsum);       // (its barrier also publishes the gradients)
             if (mine) {
                 const MeshAttrSrc<NORMALS, COLOURS> src = { grad3, ctile, (t & 7) + TFM_TILE * (t >> 3 & 7) + TFM_TILE * TFM_TILE * (t >> 6) };
                 MeshAttrWriter<NORMALS, COLOURS> wr = { outTri, outNrm, outCol, base[ei] + off, capacity };
@@ -275,31 +217,261 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const un
     }
 }
 
+// ---- the indexed form -------------------------------------------------------------------------------------
+struct MeshMarker {
+    unsigned* lmask;             // LDS, [8][TFM_EDGE_WORDS]
+    __device__ __forceinline__ void operator()(const TfmEdgeRef& r) { atomicOr(&lmask[r.owner * TFM_EDGE_WORDS + (r.bit >> 5)], 1u << (r.bit & 31u)); }
+};
+
+__global__ __launch_bounds__(TFM_WG) void k_mesh_mark(MeshScene s, unsigned* __restrict__ mask, int n_blocks)
+{
+    __shared__ unsigned tile[TFM_TILE3];
+    __shared__ int nvoff[8];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ unsigned lmask[8 * TFM_EDGE_WORDS];
+    const int t = threadIdx.x;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasBlock{ s.v.hash, nullptr });    // (any order: OR commutes)
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            mesh_stage(s, ei, s.v.hash[ei], tile, nvoff);        // (its leading barrier: the previous entry's flush is done)
+            for (int i = t; i < 8 * TFM_EDGE_WORDS; i += TFM_WG) lmask[i] = 0u;
+            __syncthreads();
+            MeshMarker mk = { lmask };
+            tfm_cube_mark(mesh_cube<TFM_TILE, 0>(tile), t & 7, t >> 3 & 7, t >> 6, mk);
+            __syncthreads();
+            for (int i = t; i < 8 * TFM_EDGE_WORDS; i += TFM_WG) {
+                const unsigned w = lmask[i];
+                if (w) {
+                    // the owner holds a corner of a valid cube (w > 0), so its block exists; the guards only bound the store
+                    const int o = i / TFM_EDGE_WORDS, blk = nvoff[o] >> 9;
+                    if (nvoff[o] >= 0 && blk < n_blocks) atomicOr(&mask[(size_t)blk * TFM_EDGE_WORDS + (i - o * TFM_EDGE_WORDS)], w);
+                }
+            }
+        }
+    }
+}
+
+// Per live entry (one wave each) the exclusive popcount prefix of its block's mask words and its vertex
+// count; dead entries count 0; each 512-entry group's total beside, as k_mesh_count leaves them.
+__global__ __launch_bounds__(TFM_WG) void k_mesh_vcount(MeshScene s, const unsigned* __restrict__ mask, unsigned* __restrict__ wpre, int n_blocks,
+                                                        long long* __restrict__ count, long long* __restrict__ groupTot)
+{
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ int gsum;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        if (t == 0) gsum = 0;            // (thread 0 read the previous group's sum itself; the list's barriers stand before the adds)
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasBlock{ s.v.hash, count });
+        for (int k = wave; k < n; k += TFM_WG / 64) {
+            const int ei = live[k];
+            const int blk = s.v.hash[ei].ptr;
+            int total = 0;
+            if (blk < n_blocks) {
+                const size_t at = (size_t)blk * TFM_EDGE_WORDS;
+                const int ca = __popc(mask[at + lane]);
+                const int cb = lane < TFM_EDGE_WORDS - 64 ? __popc(mask[at + 64 + lane]) : 0;
+                const int ia = mesh_wave_scan(ca), ib = mesh_wave_scan(cb);
+                const int ta = __shfl(ia, 63, 64);
+                total = ta + __shfl(ib, 63, 64);
+                wpre[at + lane] = (unsigned)(ia - ca);
+                if (lane < TFM_EDGE_WORDS - 64) wpre[at + 64 + lane] = (unsigned)(ta + ib - cb);
+            }
+            if (lane == 0) {
+                count[ei] = total;
+                atomicAdd(&gsum, total);             // (an integer sum: any order)
+            }
+        }
+        __syncthreads();
+        if (t == 0) groupTot[g] = gsum;
+    }
+}
+
+// The vertex table: positions (may be nullptr), normals, colours (one RGBA word per vertex), each clipped
+// at `capacity` vertices.  The tile is the attributed kernel's; a block's vertices are contiguous.
+template <bool NORMALS, bool COLOURS>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(MeshScene s, const unsigned* __restrict__ rgb, const unsigned* __restrict__ mask,
+                                                               const unsigned* __restrict__ wpre, const long long* __restrict__ vcount,
+                                                               const long long* __restrict__ vbase, float* __restrict__ outPos,
+                                                               float* __restrict__ outNrm, unsigned* __restrict__ outCol, long long capacity,
+                                                               float voxelSize)
+{
+    __shared__ unsigned tile[TFM_ATILE3];
+    __shared__ int grad3[NORMALS ? 3 * TFM_TILE3 : 1];
+    __shared__ unsigned ctile[COLOURS ? TFM_TILE3 : 1];
+    __shared__ int nvoff[27];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ unsigned lm[TFM_EDGE_WORDS + 1], lpre[TFM_EDGE_WORDS];
+    const int t = threadIdx.x;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    if (t == 0) lm[TFM_EDGE_WORDS] = 0u;     // (the zero word behind the mask; published by the first list's barriers)
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasOutput{ vcount, vbase, capacity });
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            const TfHashEntry e = s.v.hash[ei];
+            mesh_stage_attr<NORMALS, COLOURS>(s, rgb, e, tile, ctile, nvoff);
+            if (t < TFM_EDGE_WORDS) {                // (vcount > 0: the entry is live and its block below n_blocks)
+                lm[t] = mask[(size_t)e.ptr * TFM_EDGE_WORDS + t];
+                lpre[t] = wpre[(size_t)e.ptr * TFM_EDGE_WORDS + t];
+            }
+            if (NORMALS) mesh_grad_fill(tile, grad3);
+            __syncthreads();         // the mask words, and the gradients
+            // this voxel's seven bits, t * 7 .. t * 7 + 6: in one word or across two (lm has a zero word behind)
+            const unsigned b0 = (unsigned)t * 7u, w0 = b0 >> 5;
+            const unsigned bits = (unsigned)((((unsigned long long)lm[w0 + 1] << 32 | lm[w0]) >> (b0 & 31u)) & 127u);
+            if (bits) {
+                const int x = t & 7, y = t >> 3 & 7, z = t >> 6;
+                const int c = (x + 1) + TFM_ATILE * (y + 1) + TFM_ATILE * TFM_ATILE * (z + 1);
+                const int sp = (int)(short)(tile[c] & 0xffffu);
+                const MeshAttrSrc<NORMALS, COLOURS> src = { grad3, ctile, x + TFM_TILE * y + TFM_TILE * TFM_TILE * z };
+                const long long base = vbase[ei];
+#pragma unroll
+                for (unsigned dc = 1; dc < 8; ++dc) {
+                    if (!(bits >> (dc - 1) & 1u)) continue;
+                    const unsigned bit = b0 + dc - 1;
+                    const long long vi = base + tfm_edge_rank(lm[bit >> 5], lpre[bit >> 5], bit);
+                    if (vi >= capacity) continue;
+                    const int sq = (int)(short)(tile[c + (int)(dc & 1) + TFM_ATILE * (int)(dc >> 1 & 1) + TFM_ATILE * TFM_ATILE * (int)(dc >> 2)] & 0xffffu);
+                    if (outPos) {
+                        float p[3];
+                        tfm_edge_vertex(dc, sp, sq, e.x * TF_BLK + x, e.y * TF_BLK + y, e.z * TF_BLK + z, voxelSize, p);
+                        mesh_store3(outPos + vi * 3, p);
+                    }
+                    const float et = tfm_edge_t(sp, sq);
+                    if (NORMALS) {
+                        int gp[3], gq[3];
+                        float nr[3];
+                        src.grad(0u, gp);
+                        src.grad(dc, gq);
+                        tfm_normal(et, gp, gq, nr);
+                        mesh_store3(outNrm + vi * 3, nr);
+                    }
+                    if (COLOURS) outCol[vi] = tfm_colour(et, src.colour(0u), src.colour(dc));
+                }
+            }
+        }
+    }
+}
+
+// the index of one triangle vertex: its edge's owner among the entry's eight blocks, the bit, the rank
+struct MeshIndexWriter {
+    const unsigned* lm;          // LDS: the entry's own mask words and prefixes
+    const unsigned* lpre;
+    const int* nvoff;            // LDS: the eight blocks' voxel offsets
+    const long long* nbase;      // LDS: ... and their entries' vertex bases
+    const unsigned* mask;
+    const unsigned* wpre;
+    unsigned* out;
+    int x, y, z;
+    long long idx;               // the next triangle's index
+    long long capacity;
+    __device__ __forceinline__ void operator()(const unsigned* lo, const unsigned* hi)
+    {
+        if (idx < capacity) {
+            tfm_u3 tri;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+                const TfmEdgeRef r = tfm_edge_ref(x + (int)(lo[v] & 1), y + (int)(lo[v] >> 1 & 1), z + (int)(lo[v] >> 2), hi[v] & ~lo[v]);
+                const unsigned w = r.bit >> 5;
+                unsigned m = 0u, pre = 0u;
+                if (r.owner == 0u) {
+                    m = lm[w]; pre = lpre[w];
+                } else if (nvoff[r.owner] >= 0) {        // (always: the owner holds a corner of this valid cube)
+                    const size_t at = (size_t)(nvoff[r.owner] >> 9) * TFM_EDGE_WORDS + w;
+                    m = mask[at]; pre = wpre[at];
+                }
+                tri[v] = (unsigned)(nbase[r.owner] + tfm_edge_rank(m, pre, r.bit));
+            }
+            *reinterpret_cast<tfm_u3*>(out + idx * 3) = tri;
+        }
+        ++idx;
+    }
+};
+
+// mesh_stage's hook of k_mesh_emit_indices: the eight blocks' entries give their vertex bases (a missing
+// block owns nothing), and threads 64 .. 175 bring the entry's own mask words and prefixes
+struct MeshIndexStage {
+    const long long* vbase;
+    const unsigned* mask;        // the entry's block's words
+    const unsigned* wpre;
+    long long* nbase;            // LDS
+    unsigned* lm;
+    unsigned* lpre;
+    __device__ __forceinline__ void operator()(int t, int2 b) const
+    {
+        if (t < 8) nbase[t] = b.y >= 0 ? vbase[b.x] : 0;
+        if (t >= 64 && t < 64 + TFM_EDGE_WORDS) {
+            lm[t - 64] = mask[t - 64];
+            lpre[t - 64] = wpre[t - 64];
+        }
+    }
+};
+
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_indices(MeshScene s, const unsigned* __restrict__ mask, const unsigned* __restrict__ wpre,
+                                                              const long long* __restrict__ count, const long long* __restrict__ base,
+                                                              const long long* __restrict__ vbase, unsigned* __restrict__ out, long long capacity)
+{
+    __shared__ unsigned tile[TFM_TILE3];
+    __shared__ int nvoff[8];
+    __shared__ long long nbase[8];
+    __shared__ int live[TFM_WG];
+    __shared__ int nlive;
+    __shared__ int wsum[TFM_WG / 64];
+    __shared__ unsigned lm[TFM_EDGE_WORDS], lpre[TFM_EDGE_WORDS];
+    const int t = threadIdx.x;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasOutput{ count, base, capacity });
+        for (int k = 0; k < n; ++k) {
+            const int ei = live[k];
+            const TfHashEntry e = s.v.hash[ei];
+            const size_t own = (size_t)e.ptr * TFM_EDGE_WORDS;
+            mesh_stage(s, ei, e, tile, nvoff, MeshIndexStage{ vbase, mask + own, wpre + own, nbase, lm, lpre });
+            const TfmCube q = mesh_cube<TFM_TILE, 0>(tile);
+            const int mine = tfm_cube_count(q);
+            const int off = mesh_scan(mine, wsum);
+            if (mine) {
+                MeshIndexWriter wr = { lm, lpre, nvoff, nbase, mask, wpre, out, t & 7, t >> 3 & 7, t >> 6, base[ei] + off, capacity };
+                tfm_cube_emit_edges(q, wr);
+            }
+        }
+    }
+}
+
+// ---- the host side ----------------------------------------------------------------------------------------
+static hipError_t mesh_prefix(tf_ctx* c, const long long* count, const long long* groupTot, long long* base)
+{
+    hipLaunchKernelGGL(k_mesh_prefix, dim3((mesh_groups(c) + TFM_SCAN_GROUPS - 1) / TFM_SCAN_GROUPS), dim3(256), 0, c->stream, count, groupTot,
+                       base, c->n_total);
+    return hipGetLastError();
+}
+
 // count + prefix; the scratch (counts, bases + total, group totals behind the counts) is the
 // context's from the first call on
 hipError_t tfk_mesh_count(tf_ctx* c)
 {
-    const int ng = mesh_groups(c);
     if (!c->meshCount) {
-        hipError_t e = hipMalloc((void**)&c->meshCount, sizeof(long long) * ((size_t)c->n_total + (size_t)ng));
+        hipError_t e = hipMalloc((void**)&c->meshCount, sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c)));
         if (e != hipSuccess) { c->meshCount = nullptr; return e; }
         e = hipMalloc((void**)&c->meshBase, sizeof(long long) * ((size_t)c->n_total + 1));
         if (e != hipSuccess) { (void)hipFree(c->meshCount); c->meshCount = nullptr; c->meshBase = nullptr; return e; }
     }
     long long* groupTot = c->meshCount + c->n_total;
-    hipLaunchKernelGGL(k_mesh_count, dim3(ng < TFM_GRID ? ng : TFM_GRID), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount,
-                       groupTot);
-    hipLaunchKernelGGL(k_mesh_prefix, dim3((ng + TFM_SCAN_GROUPS - 1) / TFM_SCAN_GROUPS), dim3(256), 0, c->stream, c->meshCount,
-                       groupTot, c->meshBase, c->n_total);
-    return hipGetLastError();
+    hipLaunchKernelGGL(k_mesh_count, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, groupTot);
+    return mesh_prefix(c, c->meshCount, groupTot, c->meshBase);
 }
 
 // after tfk_mesh_count on the same stream
 hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
 {
-    const int ng = mesh_groups(c);
-    hipLaunchKernelGGL(k_mesh_emit, dim3(ng < TFM_GRID ? ng : TFM_GRID), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount,
-                       c->meshBase, triangles, capacity, c->p.voxelSize);
+    hipLaunchKernelGGL(k_mesh_emit, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, c->meshBase, triangles, capacity,
+                       c->p.voxelSize);
     return hipGetLastError();
 }
 
@@ -307,26 +479,61 @@ hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
 // least one of the two; colours need the colour plane), all clipped at the same capacity
 hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity)
 {
-    const int ng = mesh_groups(c);
-    const dim3 grid(ng < TFM_GRID ? ng : TFM_GRID), wg(TFM_WG);
-    unsigned* col = reinterpret_cast<unsigned*>(colours);
-    if (normals && colours)
-        hipLaunchKernelGGL((k_mesh_emit_attr<true, true>), grid, wg, 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount, c->meshBase,
-                           triangles, normals, col, capacity, c->p.voxelSize);
-    else if (normals)
-        hipLaunchKernelGGL((k_mesh_emit_attr<true, false>), grid, wg, 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount, c->meshBase,
-                           triangles, normals, col, capacity, c->p.voxelSize);
-    else
-        hipLaunchKernelGGL((k_mesh_emit_attr<false, true>), grid, wg, 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount, c->meshBase,
-                           triangles, normals, col, capacity, c->p.voxelSize);
+    mesh_dispatch_attr(normals != nullptr, colours != nullptr, [&](auto N, auto C) {
+        if constexpr (N() || C())
+            hipLaunchKernelGGL((k_mesh_emit_attr<N(), C()>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount,
+                               c->meshBase, triangles, normals, reinterpret_cast<unsigned*>(colours), capacity, c->p.voxelSize);
+    });
     return hipGetLastError();
 }
 
-// the exclusive scan alone (tf_mesh_indexed.hip scans its vertex counts with it)
-hipError_t tfk_mesh_prefix(tf_ctx* c, const long long* count, const long long* groupTot, long long* base)
+// Triangle count + prefix (tfk_mesh_count), then the edge masks cleared (blocks are freed and reused: a
+// stale mask is a wrong mesh), marked and counted, and the vertex prefix: the totals land in
+// meshBase[n_total] and meshVBase[n_total].  The scratch is the context's from the first call on.
+hipError_t tfk_mesh_index_count(tf_ctx* c)
 {
-    const int ng = mesh_groups(c);
-    hipLaunchKernelGGL(k_mesh_prefix, dim3((ng + TFM_SCAN_GROUPS - 1) / TFM_SCAN_GROUPS), dim3(256), 0, c->stream, count, groupTot, base,
-                       c->n_total);
+    hipError_t e = tfk_mesh_count(c);
+    if (e != hipSuccess) return e;
+    const size_t words = (size_t)c->p.n_blocks * TFM_EDGE_WORDS;
+    if (!c->meshMask) {
+        void* b[4] = { nullptr, nullptr, nullptr, nullptr };
+        const size_t bytes[4] = { sizeof(unsigned) * words, sizeof(unsigned) * words,
+                                  sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c)), sizeof(long long) * ((size_t)c->n_total + 1) };
+        for (int i = 0; i < 4; ++i) {
+            e = hipMalloc(&b[i], bytes[i]);
+            if (e != hipSuccess) {
+                for (int j = 0; j < i; ++j) (void)hipFree(b[j]);
+                return e;
+            }
+        }
+        c->meshMask = (unsigned*)b[0]; c->meshWPre = (unsigned*)b[1]; c->meshVCount = (long long*)b[2]; c->meshVBase = (long long*)b[3];
+    }
+    e = hipMemsetAsync(c->meshMask, 0, sizeof(unsigned) * words, c->stream);
+    if (e != hipSuccess) return e;
+    long long* groupTot = c->meshVCount + c->n_total;
+    hipLaunchKernelGGL(k_mesh_mark, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->p.n_blocks);
+    hipLaunchKernelGGL(k_mesh_vcount, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->meshWPre, c->p.n_blocks,
+                       c->meshVCount, groupTot);
+    e = hipGetLastError();
+    return e == hipSuccess ? mesh_prefix(c, c->meshVCount, groupTot, c->meshVBase) : e;
+}
+
+// after tfk_mesh_index_count on the same stream: the vertex table's columns (each may be nullptr, one at
+// least is not; colours need the colour plane), clipped at the same capacity
+hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity)
+{
+    mesh_dispatch_attr(normals != nullptr, colours != nullptr, [&](auto N, auto C) {
+        hipLaunchKernelGGL((k_mesh_emit_vertices<N(), C()>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshMask,
+                           c->meshWPre, c->meshVCount, c->meshVBase, vertices, normals, reinterpret_cast<unsigned*>(colours), capacity,
+                           c->p.voxelSize);
+    });
+    return hipGetLastError();
+}
+
+// after tfk_mesh_index_count on the same stream: three vertex numbers per triangle, the first `capacity` triangles
+hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity)
+{
+    hipLaunchKernelGGL(k_mesh_emit_indices, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->meshWPre, c->meshCount,
+                       c->meshBase, c->meshVBase, indices, capacity);
     return hipGetLastError();
 }

@@ -1,7 +1,11 @@
-// tf_mesh_dev.h -- what the mesh extraction's translation units share on the device side (tf_mesh.hip: the
-// triangle soup; tf_mesh_indexed.hip: the indexed form): the scene view, the block look-ups and the LDS
-// tiles of a hash entry's cube corners.
+// tf_mesh_dev.h -- the workgroup skeleton of mesh extraction's kernels (tf_mesh.hip), each piece written
+// once: the scene view, the live list of a 512-entry group, the workgroup scan, the block look-up, the
+// LDS tiles of a hash entry's corner voxels with their gradient fill and cube read, the stores and the
+// <NORMALS, COLOURS> dispatch.  Every piece that holds a barrier says so, and says what its caller may
+// assume before and after.
 #pragma once
+
+#include <type_traits>
 
 #include "tf_internal.h"
 #include "tf_mesh.h"
@@ -17,25 +21,82 @@ struct MeshScene {
     int n_total;
 };
 
-// (hash entry, VBA voxel offset) of a neighbour block; a block coordinate outside the short range,
-// a block the hash does not hold, and a swapped-out entry (ptr -1) are all missing
-__device__ __forceinline__ int mesh_block_voff(const MeshScene& s, int bx, int by, int bz)
-{
-    if (tf_grid_in(bx, by, bz)) return s.v.grid[tf_grid_cell(bx, by, bz)].y;
-    if (bx > 32767 || by > 32767 || bz > 32767) return TF_VOFF_NONE;
-    return blk_walk(s.v, bx, by, bz).y;
-}
-
-// The entry's 729 corner voxels into LDS (sdf | w << 16 per voxel, index x + 9 y + 81 z).  All
-// threads of the workgroup call it; e is uniform.
-__device__ __forceinline__ void mesh_stage(const MeshScene& s, const TfHashEntry& e, unsigned* tile, int* nvoff)
+// The entries of group g that pred(idx) accepts, into live[] (any order); returns their number.  pred
+// runs once per entry below n_total and may leave a side effect for a rejected one (the count passes
+// write its 0).  Three barriers: the first ends the previous group's reads of live / nlive (and of
+// whatever thread 0 reset just before the call), the third publishes the list.
+template <class Pred>
+__device__ __forceinline__ int mesh_live_list(int g, int n_total, int* live, int* nlive, Pred pred)
 {
     const int t = threadIdx.x;
-    __syncthreads();             // the previous entry's reads of tile / nvoff are done
-    if (t < 8) {
-        const int dx = t & 1, dy = t >> 1 & 1, dz = t >> 2;
-        nvoff[t] = t == 0 ? e.ptr * TF_BLK3 : mesh_block_voff(s, e.x + dx, e.y + dy, e.z + dz);
+    __syncthreads();
+    if (t == 0) *nlive = 0;
+    __syncthreads();
+    const int idx = g * TFM_WG + t;
+    if (idx < n_total && pred(idx)) live[atomicAdd(nlive, 1)] = idx;
+    __syncthreads();
+    return *nlive;
+}
+
+// inclusive scan of one int per lane of the wave
+__device__ __forceinline__ int mesh_wave_scan(int v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
     }
+    return v;
+}
+
+// Exclusive scan of `mine` over the workgroup's 512 threads: inclusive within the wave, then the lower
+// waves' sums out of wsum[TFM_WG / 64].  One barrier, between wsum's writes and its reads: it also
+// publishes whatever the caller wrote to LDS before the call.  No barrier behind the reads: the caller
+// keeps one (the next entry's staging) between them and the next call.
+__device__ __forceinline__ int mesh_scan(int mine, int* wsum)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int inc = mesh_wave_scan(mine);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int off = inc - mine;
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    return off;
+}
+
+// (hash entry, VBA voxel offset) of a neighbour block, or (-1, TF_VOFF_NONE): a block coordinate
+// outside the short range (blk_walk compares shorts and would wrap), a block the hash does not hold
+// and a swapped-out entry (ptr -1) are all missing.  Both ends of the range are checked for every
+// caller; the 9-wide tile only ever steps up from a short, so the lower compare cannot change its result.
+__device__ __forceinline__ int2 mesh_block_look(const MeshScene& s, int bx, int by, int bz)
+{
+    if (tf_grid_in(bx, by, bz)) return s.v.grid[tf_grid_cell(bx, by, bz)];
+    if (bx > 32767 || by > 32767 || bz > 32767 || bx < -32768 || by < -32768 || bz < -32768) return make_int2(-1, TF_VOFF_NONE);
+    return blk_walk(s.v, bx, by, bz);
+}
+
+struct MeshNoHook {
+    __device__ __forceinline__ void operator()(int, int2) const {}
+};
+
+// Entry ei's 729 corner voxels into LDS (sdf | w << 16 per voxel, index x + 9 y + 81 z) and its eight
+// blocks' voxel offsets into nvoff.  All threads of the workgroup call it; ei and e are uniform.
+// Three barriers: the leading one ends the previous entry's reads of tile / nvoff and of any LDS of the
+// caller's; between it and the second every thread calls hook(t, b) -- for t < 8, b is block t's
+// (entry, voff) as found, so the caller can keep what belongs to the entry, and any thread may fill
+// LDS of the caller's there; the trailing one publishes the tile, nvoff and what the hook wrote.
+template <class Hook = MeshNoHook>
+__device__ __forceinline__ void mesh_stage(const MeshScene& s, int ei, const TfHashEntry& e, unsigned* tile, int* nvoff, Hook hook = Hook())
+{
+    const int t = threadIdx.x;
+    __syncthreads();
+    int2 b = make_int2(-1, TF_VOFF_NONE);
+    if (t < 8) {
+        b = t == 0 ? make_int2(ei, e.ptr * TF_BLK3) : mesh_block_look(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
+        nvoff[t] = b.y;
+    }
+    hook(t, b);
     __syncthreads();
     for (int i = t; i < TFM_TILE3; i += TFM_WG) {
         const int z = i / (TFM_TILE * TFM_TILE), r = i - z * (TFM_TILE * TFM_TILE), y = r / TFM_TILE, x = r - y * TFM_TILE;
@@ -46,16 +107,18 @@ __device__ __forceinline__ void mesh_stage(const MeshScene& s, const TfHashEntry
     __syncthreads();
 }
 
-// this thread's cube: voxel threadIdx.x = x + 8 y + 64 z
+// This thread's cube (voxel threadIdx.x = x + 8 y + 64 z) out of a tile STRIDE wide whose voxel (0, 0, 0)
+// sits at ORIGIN on each axis: <TFM_TILE, 0> for mesh_stage's, <TFM_ATILE, 1> for mesh_stage_attr's.
+template <int STRIDE, int ORIGIN>
 __device__ __forceinline__ TfmCube mesh_cube(const unsigned* tile)
 {
     const int t = threadIdx.x, x = t & 7, y = t >> 3 & 7, z = t >> 6;
-    const int b = x + TFM_TILE * y + TFM_TILE * TFM_TILE * z;
+    const int b = (x + ORIGIN) + STRIDE * (y + ORIGIN) + STRIDE * STRIDE * (z + ORIGIN);
     TfmCube q;
     unsigned wmin = 255u;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const unsigned v = tile[b + (c & 1) + TFM_TILE * (c >> 1 & 1) + TFM_TILE * TFM_TILE * (c >> 2)];
+        const unsigned v = tile[b + (c & 1) + STRIDE * (c >> 1 & 1) + STRIDE * STRIDE * (c >> 2)];
         q.sdf[c] = (int)(short)(v & 0xffffu);
         wmin = min(wmin, v >> 16);
     }
@@ -67,30 +130,23 @@ __device__ __forceinline__ TfmCube mesh_cube(const unsigned* tile)
 #define TFM_ATILE 11
 #define TFM_ATILE3 (TFM_ATILE * TFM_ATILE * TFM_ATILE)
 
-// mesh_block_voff for offsets that also step down: block -32769 does not exist either (blk_walk
-// compares shorts and would wrap)
-__device__ __forceinline__ int mesh_block_voff_attr(const MeshScene& s, int bx, int by, int bz)
-{
-    if (tf_grid_in(bx, by, bz)) return s.v.grid[tf_grid_cell(bx, by, bz)].y;
-    if (bx > 32767 || by > 32767 || bz > 32767 || bx < -32768 || by < -32768 || bz < -32768) return TF_VOFF_NONE;
-    return blk_walk(s.v, bx, by, bz).y;
-}
-
 // tile: sdf | w << 16 at (x + 1) + 11 (y + 1) + 121 (z + 1), x, y, z in -1 .. 9 (NORMALS; else 0 .. 8 only,
 // the rim reads as w = 0); ctile: colour words at x + 9 y + 81 z (COLOURS); nvoff: the 27 block offsets
-// (ox + 1) + 3 (oy + 1) + 9 (oz + 1), those with more than one -1 (without NORMALS: any -1) unused
+// (ox + 1) + 3 (oy + 1) + 9 (oz + 1), those with more than one -1 (without NORMALS: any -1) unused.
+// Three barriers, as mesh_stage's: the leading one ends the previous entry's reads of tile / gradients /
+// ctile / nvoff, the trailing one publishes the tiles.
 template <bool NORMALS, bool COLOURS>
 __device__ __forceinline__ void mesh_stage_attr(const MeshScene& s, const unsigned* __restrict__ rgb, const TfHashEntry& e, unsigned* tile,
                                                 unsigned* ctile, int* nvoff)
 {
     const int t = threadIdx.x;
-    __syncthreads();             // the previous entry's reads of tile / gradients / ctile / nvoff are done
+    __syncthreads();
     if (t < 27) {
         const int ox = t % 3 - 1, oy = t / 3 % 3 - 1, oz = t / 9 - 1;
         const int down = (ox < 0) + (oy < 0) + (oz < 0);
         int voff = TF_VOFF_NONE;
         if (t == 13) voff = e.ptr * TF_BLK3;
-        else if (down <= (NORMALS ? 1 : 0)) voff = mesh_block_voff_attr(s, e.x + ox, e.y + oy, e.z + oz);
+        else if (down <= (NORMALS ? 1 : 0)) voff = mesh_block_look(s, e.x + ox, e.y + oy, e.z + oz).y;
         nvoff[t] = voff;
     }
     __syncthreads();
@@ -111,21 +167,18 @@ __device__ __forceinline__ void mesh_stage_attr(const MeshScene& s, const unsign
     __syncthreads();
 }
 
-// this thread's cube from the 11-wide tile
-__device__ __forceinline__ TfmCube mesh_cube_attr(const unsigned* tile)
+// The 9^3 lattice gradients of a complete 11-wide tile into grad3[3][TFM_TILE3], once per entry.  No
+// barrier: the caller's next one (the scan's, or its own) publishes them.
+__device__ __forceinline__ void mesh_grad_fill(const unsigned* tile, int* grad3)
 {
-    const int t = threadIdx.x, x = t & 7, y = t >> 3 & 7, z = t >> 6;
-    const int b = (x + 1) + TFM_ATILE * (y + 1) + TFM_ATILE * TFM_ATILE * (z + 1);
-    TfmCube q;
-    unsigned wmin = 255u;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const unsigned v = tile[b + (c & 1) + TFM_ATILE * (c >> 1 & 1) + TFM_ATILE * TFM_ATILE * (c >> 2)];
-        q.sdf[c] = (int)(short)(v & 0xffffu);
-        wmin = min(wmin, v >> 16);
+    for (int i = threadIdx.x; i < TFM_TILE3; i += TFM_WG) {
+        const int z = i / (TFM_TILE * TFM_TILE), r = i - z * (TFM_TILE * TFM_TILE), y = r / TFM_TILE, x = r - y * TFM_TILE;
+        const int c = (x + 1) + TFM_ATILE * (y + 1) + TFM_ATILE * TFM_ATILE * (z + 1);
+        const unsigned v0 = tile[c];
+        grad3[i] = tfm_grad_axis_packed(tile[c - 1], v0, tile[c + 1]);
+        grad3[TFM_TILE3 + i] = tfm_grad_axis_packed(tile[c - TFM_ATILE], v0, tile[c + TFM_ATILE]);
+        grad3[2 * TFM_TILE3 + i] = tfm_grad_axis_packed(tile[c - TFM_ATILE * TFM_ATILE], v0, tile[c + TFM_ATILE * TFM_ATILE]);
     }
-    q.valid = wmin > 0;
-    return q;
 }
 
 // the lattice data of this thread's cube corners, out of LDS
@@ -144,6 +197,29 @@ struct MeshAttrSrc {
     __device__ __forceinline__ unsigned colour(unsigned c) const { return ctile[at(c)]; }
 };
 
+// ---- stores: dword-aligned vectors (a triangle is 36 bytes, a vertex 12) ----
+typedef float tfm_f4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef float tfm_f3 __attribute__((ext_vector_type(3), aligned(4)));
+typedef unsigned tfm_u3 __attribute__((ext_vector_type(3), aligned(4)));
+
+__device__ __forceinline__ void mesh_store9(float* p, const float* v)
+{
+    tfm_f4 a, b;
+    a.x = v[0]; a.y = v[1]; a.z = v[2]; a.w = v[3];
+    b.x = v[4]; b.y = v[5]; b.z = v[6]; b.w = v[7];
+    *reinterpret_cast<tfm_f4*>(p) = a;
+    *reinterpret_cast<tfm_f4*>(p + 4) = b;
+    p[8] = v[8];
+}
+
+__device__ __forceinline__ void mesh_store3(float* p, const float* v)
+{
+    tfm_f3 a;
+    a.x = v[0]; a.y = v[1]; a.z = v[2];
+    *reinterpret_cast<tfm_f3*>(p) = a;
+}
+
+// ---- the host side ----
 static inline MeshScene mesh_scene(const tf_ctx* c)
 {
     MeshScene s;
@@ -153,3 +229,14 @@ static inline MeshScene mesh_scene(const tf_ctx* c)
 }
 
 static inline int mesh_groups(const tf_ctx* c) { return (c->n_total + TFM_WG - 1) / TFM_WG; }
+static inline dim3 mesh_grid(const tf_ctx* c) { return dim3(mesh_groups(c) < TFM_GRID ? mesh_groups(c) : TFM_GRID); }
+
+// f(std::bool_constant<NORMALS>, std::bool_constant<COLOURS>) for the run-time pair
+template <class F>
+static inline void mesh_dispatch_attr(bool normals, bool colours, F f)
+{
+    if (normals && colours) f(std::true_type(), std::true_type());
+    else if (normals) f(std::true_type(), std::false_type());
+    else if (colours) f(std::false_type(), std::true_type());
+    else f(std::false_type(), std::false_type());
+}

@@ -15,7 +15,7 @@
 //   k_ckpt_apply   : hash[index], visType[index] from the records (the block grid is rebuilt after)
 //
 // The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of its
-// own over int2 group counts (8 B per 256 entries) rather than tfk_mesh_prefix over 64-bit per-entry
+// own over int2 group counts (8 B per 256 entries) rather than k_mesh_prefix over 64-bit per-entry
 // counts, and shares no scratch with a mesh extraction.  No workgroup waits on another inside a grid.
 #include "tf_internal.h"
 #include "tf_scene_file.h"
