@@ -124,29 +124,76 @@ def test_random_walk_synth():
     assert abs(n.mean()) < 0.01 and abs(n.std() - 1.0) < 0.01 and np.abs(n).max() <= 2 * synth._SQRT3
 
 
+def _csrc_sources(suffixes):
+    d = os.path.join(ROOT, "topfusion_amd", "csrc")
+    return {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.endswith(suffixes)}
+
+
 def test_entry_points_flush_deferred_frame():
-    """A per-call frame leaves its last two launches to the next call (tf_capi.hip flush_tail): every
+    """A per-call frame leaves its last two launches to the next call (tf_frame.hip flush_tail): every
     other C-ABI entry point that takes a context must enqueue them first (TF_FLUSH), so that it
-    sees the whole frame.  Static check of tf_capi.hip: the only entry points without it are the
-    per-call frame itself (it flushes with its own frame's lookahead) and the host-only ones."""
+    sees the whole frame.  Static check of every file under topfusion_amd/csrc that defines an
+    extern "C" function: the only entry points without it are the per-call frame itself (it flushes
+    with its own frame's lookahead) and the host-only ones."""
     import re
-    src = open(os.path.join(ROOT, "topfusion_amd", "csrc", "tf_capi.hip")).read()
     host_only = {"tf_destroy", "tf_get_params", "tf_get_stream", "tf_get_schedule", "tf_get_pose_algebra", "tf_profile_enable",
                  "tf_profile_stages", "tf_profile_sample", "tf_profile_reset", "tf_profile_read"}
     per_call = {"tf_process_frame", "tf_process_frame_host"}
     checked = 0
-    for m in re.finditer(r'extern "C" [^(]*\b(tf_\w+)\(([^)]*)\)\s*\{', src):
-        name, args = m.group(1), m.group(2)
-        if "tf_ctx* c" not in args or name in host_only:
-            continue
-        body = src[m.end():src.index("\n}", m.end()) if "\n}" in src[m.end():] else len(src)]
-        head = body[:400]
-        if name in per_call:
-            assert "process_frame_early" in head and "TF_FLUSH(c)" in head, name
-        else:
-            assert "TF_FLUSH(c)" in head, f"{name} does not flush a deferred per-call frame"
-        checked += 1
-    assert checked >= 40, checked
+    sources = _csrc_sources((".hip", ".cpp"))
+    for src in sources.values():
+        for m in re.finditer(r'extern "C" [^(]*\b(tf_\w+)\(([^)]*)\)\s*\{', src):
+            name, args = m.group(1), m.group(2)
+            if "tf_ctx* c" not in args or name in host_only:
+                continue
+            body = src[m.end():src.index("\n}", m.end()) if "\n}" in src[m.end():] else len(src)]
+            head = body[:400]
+            if name in per_call:
+                assert "process_frame_early" in head and "TF_FLUSH(c)" in head, name
+            else:
+                assert "TF_FLUSH(c)" in head, f"{name} does not flush a deferred per-call frame"
+            checked += 1
+    assert checked >= 57, checked
     # tf_get_stream hands the stream out: a caller synchronising it itself must see whole frames
+    src = sources["tf_capi.hip"]
     gs = src[src.index('extern "C" void* tf_get_stream'):]
     assert "flush_tail(c)" in gs[:300]
+
+
+def test_raw_allocators_named_once():
+    """A context's device and pinned memory has one owner (tf_ctx_mem.h), so HIP's four allocation and free
+    calls occur in topfusion_amd/csrc only where tf_capi.hip hands them to the registry: once each, inside the
+    initialiser of tf_hip_mem_fns."""
+    import re
+    call = re.compile(r"\bhip(Malloc|HostMalloc|Free|HostFree)\s*\(")
+    found = {}
+    for f, src in _csrc_sources((".hip", ".cpp", ".h")).items():
+        for m in call.finditer(src):
+            found.setdefault(f, []).append(m.group(1))
+    assert sorted(found) == ["tf_capi.hip"], found
+    assert sorted(found["tf_capi.hip"]) == ["Free", "HostFree", "HostMalloc", "Malloc"], found
+    src = _csrc_sources((".hip",))["tf_capi.hip"]
+    table = src[src.index("static const TfMemFns tf_hip_mem_fns = {"):]
+    table = table[:table.index("};")]
+    assert len(call.findall(table)) == 4
+
+
+def test_ctx_mem_and_env_under_asan_ubsan(tmp_path):
+    """tests/ctx_mem_main.cpp built for the CPU with -fsanitize=address,undefined and run: the registry of
+    tf_ctx_mem.h over a counting malloc that fails on its k-th call, for every k of a scripted sequence (single
+    buffers, a group of four, an early release and regrow, a second group, a scoped temporary) -- nothing live
+    after destruction, a failed group all null, nothing freed twice, 16 bytes at least, frees == allocations --
+    and the environment helpers of tf_env.h against tables written from the expressions tf_create used."""
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    exe = str(tmp_path / "ctx_mem_main")
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-o", exe, os.path.join(ROOT, "tests", "ctx_mem_main.cpp")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok 13 runs, 11 allocations") and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stdout + r.stderr

@@ -60,8 +60,8 @@ hipError_t tfk_fuse_frames(tf_ctx* c, const uint16_t* frames, size_t stride, siz
         // setToType3); the batch's first head alone before them.  c->dists alternates between the
         // two buffers and ends on the last frame's.
         if (!c->fuse_dists) {
-            const hipError_t e = hipMalloc((void**)&c->fuse_dists, sizeof(float) * (size_t)c->W * c->H);
-            if (e != hipSuccess) { c->fuse_dists = nullptr; return e; }
+            const hipError_t e = tf_mem_hip(c->mem.alloc(&c->fuse_dists, sizeof(float) * (size_t)c->W * c->H));
+            if (e != hipSuccess) return e;
         }
         hipError_t e = tfk_fuse_head(c, frames, pitch, c->dists, c->fuse_pose);
         for (int k = 0; k < n && e == hipSuccess; ++k) {

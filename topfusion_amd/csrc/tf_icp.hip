@@ -390,7 +390,7 @@ struct IcpFrameArgs {
     float2* snap;
     // per-call frames (tf_process_frame): the frame's verdict -- TopFu::operator()'s return value
     // and poses_.back() -- written to host memory as soon as it is known, so the host returns
-    // while the rest of the frame runs (tf_verdict_*, tf_capi.hip); nullptr: not requested
+    // while the rest of the frame runs (tf_verdict_*, tf_frame.hip); nullptr: not requested
     unsigned long long* verdict;
     unsigned verdict_gen;
     int fault_iter;                     // >= 0: report a lost peer at this iteration (fault injection, tests)

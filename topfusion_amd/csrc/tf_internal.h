@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/tfusion_hip.h"
+#include "tf_ctx_mem.h"
 
 #define TF_BLK 8        // SDF_BLOCK_SIZE (VoxelBlockHash.hpp:10)
 #define TF_BLK3 512     // SDF_BLOCK_SIZE3
@@ -319,6 +320,7 @@ static __device__ __forceinline__ void render_snapshot(TfDevState* st, const flo
 // host-side context
 // ---------------------------------------------------------------------------------------
 struct tf_ctx {
+    TfCtxMem mem;            // owns every device and pinned buffer below (first: tf_create constructs it, the rest is zero)
     tf_params p;
     int device;
     hipStream_t stream;
@@ -441,7 +443,7 @@ struct tf_ctx {
     // ... and a per-call frame leaves its last two launches (k_raycast_pair, k_icp_maps_end)
     // unenqueued: the next call enqueues them with its own frame's bilateral and pyramid passes in
     // their grid tails (the batch's lookahead), every other entry point first enqueues them as
-    // they are (flush_tail, tf_capi.hip)
+    // they are (flush_tail, tf_frame.hip)
     int tail_pending;
     int tail_fuse_ed;
     int percall_defer;                   // TFUSION_PERCALL_DEFER (default 1)
@@ -484,11 +486,13 @@ struct tf_ctx {
     double ckpt_ms[8];                   // the last save / load: see tf_scene_ckpt_times
     int ckpt_timing;                     // TFUSION_CKPT_TIMING=1: the kernels are timed by events (and waited for)
 };
+// the registry's status (tf_ctx_mem.h: the allocator's own code, unchanged) as the HIP error it is
+static inline hipError_t tf_mem_hip(int e) { return (hipError_t)e; }
 #define TF_CKPT_CHUNK_BLOCKS 4096        // 8 MiB of voxels (16 MiB with colour) per chunk, whatever n_blocks is
 #define TF_VERDICT_WORDS 16
 
 // the launch of a stage's single kernel: timed by the dispatch's own timestamps when the
-// stage is being timed (c->ev_start set by STAGE_ON, consumed here), plain otherwise
+// stage is being timed (c->ev_start set by STAGE_ON, tf_frame.hip, consumed here), plain otherwise
 template <typename... KArgs, typename... Args>
 inline void tf_launch(tf_ctx* c, void (*kern)(KArgs...), dim3 grid, dim3 block, unsigned shm, Args... args)
 {
@@ -583,31 +587,5 @@ hipError_t tfk_frame0_matrices(tf_ctx* c);
 // and IntegrateGlobalIntoLocal + SaveToGlobalMemory (after integration)
 hipError_t tfk_swap_realloc(tf_ctx* c);
 hipError_t tfk_swap(tf_ctx* c, int which = 3);   // 1 in, 2 out, 3 both
-
-// mesh extraction (tf_mesh.hip): count + prefix (the total lands in meshBase[n_total]), then the emit pass
-// of the first `capacity` triangles (9 floats each) in entry / voxel / tetrahedron order
-hipError_t tfk_mesh_count(tf_ctx* c);
-hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity);
-// the emit pass with per-vertex attributes: positions (may be nullptr), normals and / or colours (one of
-// the two at least; colours only with the colour plane), clipped at the same capacity
-hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity);
-// the indexed form: tfk_mesh_count plus the edge marks and the vertex count + prefix (the vertex total lands
-// in meshVBase[n_total]); then the vertex table's columns (positions, normals, RGBA; nullptr skips one)
-// clipped at `capacity` vertices, and three u32 vertex numbers per triangle clipped at `capacity` triangles
-hipError_t tfk_mesh_index_count(tf_ctx* c);
-hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity);
-hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity);
-
-// scene checkpoints (tf_scene_ckpt.hip): the scratch; count + prefix (totals: device address of {records,
-// blocks} and, behind it, the "a ptr lies outside the VBA" flag); the records and the stored blocks' ptr
-// list into caller device buffers; nb <= ckpt_chunk_blocks listed blocks VBA -> staging / staging -> VBA;
-// hash and visType from n records
-hipError_t tfk_ckpt_scratch(tf_ctx* c);
-size_t tfk_ckpt_stage_bytes(const tf_ctx* c);
-hipError_t tfk_ckpt_count(tf_ctx* c, const int2** totals);
-hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr);
-hipError_t tfk_ckpt_gather(tf_ctx* c, const int* blockPtr, int nb);
-hipError_t tfk_ckpt_scatter(tf_ctx* c, const int* blockPtr, int nb);
-hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_records);
 
 enum { TF_POSE_ALLOC = 1, TF_POSE_RAY = 2, TF_POSE_ALLOC_NOINV = 4 };

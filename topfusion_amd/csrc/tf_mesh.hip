@@ -29,6 +29,9 @@
 //
 // No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) is only read.
 #include "tf_mesh_dev.h"
+#include "tf_host.h"
+
+#include <stdlib.h>
 
 __device__ __forceinline__ int wave_sum(int v)
 {
@@ -454,13 +457,13 @@ static hipError_t mesh_prefix(tf_ctx* c, const long long* count, const long long
 
 // count + prefix; the scratch (counts, bases + total, group totals behind the counts) is the
 // context's from the first call on
-hipError_t tfk_mesh_count(tf_ctx* c)
+static hipError_t tfk_mesh_count(tf_ctx* c)
 {
     if (!c->meshCount) {
-        hipError_t e = hipMalloc((void**)&c->meshCount, sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c)));
-        if (e != hipSuccess) { c->meshCount = nullptr; return e; }
-        e = hipMalloc((void**)&c->meshBase, sizeof(long long) * ((size_t)c->n_total + 1));
-        if (e != hipSuccess) { (void)hipFree(c->meshCount); c->meshCount = nullptr; c->meshBase = nullptr; return e; }
+        const hipError_t e = tf_mem_hip(c->mem.alloc_group({
+            TfCtxMem::dev(&c->meshCount, sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c))),
+            TfCtxMem::dev(&c->meshBase, sizeof(long long) * ((size_t)c->n_total + 1)) }));
+        if (e != hipSuccess) return e;
     }
     long long* groupTot = c->meshCount + c->n_total;
     hipLaunchKernelGGL(k_mesh_count, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, groupTot);
@@ -468,7 +471,7 @@ hipError_t tfk_mesh_count(tf_ctx* c)
 }
 
 // after tfk_mesh_count on the same stream
-hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
+static hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
 {
     hipLaunchKernelGGL(k_mesh_emit, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, c->meshBase, triangles, capacity,
                        c->p.voxelSize);
@@ -477,7 +480,7 @@ hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
 
 // after tfk_mesh_count on the same stream: positions (may be nullptr), normals and / or colours (at
 // least one of the two; colours need the colour plane), all clipped at the same capacity
-hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity)
+static hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity)
 {
     mesh_dispatch_attr(normals != nullptr, colours != nullptr, [&](auto N, auto C) {
         if constexpr (N() || C())
@@ -490,23 +493,17 @@ hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsig
 // Triangle count + prefix (tfk_mesh_count), then the edge masks cleared (blocks are freed and reused: a
 // stale mask is a wrong mesh), marked and counted, and the vertex prefix: the totals land in
 // meshBase[n_total] and meshVBase[n_total].  The scratch is the context's from the first call on.
-hipError_t tfk_mesh_index_count(tf_ctx* c)
+static hipError_t tfk_mesh_index_count(tf_ctx* c)
 {
     hipError_t e = tfk_mesh_count(c);
     if (e != hipSuccess) return e;
     const size_t words = (size_t)c->p.n_blocks * TFM_EDGE_WORDS;
     if (!c->meshMask) {
-        void* b[4] = { nullptr, nullptr, nullptr, nullptr };
-        const size_t bytes[4] = { sizeof(unsigned) * words, sizeof(unsigned) * words,
-                                  sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c)), sizeof(long long) * ((size_t)c->n_total + 1) };
-        for (int i = 0; i < 4; ++i) {
-            e = hipMalloc(&b[i], bytes[i]);
-            if (e != hipSuccess) {
-                for (int j = 0; j < i; ++j) (void)hipFree(b[j]);
-                return e;
-            }
-        }
-        c->meshMask = (unsigned*)b[0]; c->meshWPre = (unsigned*)b[1]; c->meshVCount = (long long*)b[2]; c->meshVBase = (long long*)b[3];
+        const size_t counts = sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c));
+        e = tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->meshMask, sizeof(unsigned) * words), TfCtxMem::dev(&c->meshWPre, sizeof(unsigned) * words),
+                                            TfCtxMem::dev(&c->meshVCount, counts),
+                                            TfCtxMem::dev(&c->meshVBase, sizeof(long long) * ((size_t)c->n_total + 1)) }));
+        if (e != hipSuccess) return e;
     }
     e = hipMemsetAsync(c->meshMask, 0, sizeof(unsigned) * words, c->stream);
     if (e != hipSuccess) return e;
@@ -520,7 +517,7 @@ hipError_t tfk_mesh_index_count(tf_ctx* c)
 
 // after tfk_mesh_index_count on the same stream: the vertex table's columns (each may be nullptr, one at
 // least is not; colours need the colour plane), clipped at the same capacity
-hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity)
+static hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity)
 {
     mesh_dispatch_attr(normals != nullptr, colours != nullptr, [&](auto N, auto C) {
         hipLaunchKernelGGL((k_mesh_emit_vertices<N(), C()>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshMask,
@@ -531,9 +528,174 @@ hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, un
 }
 
 // after tfk_mesh_index_count on the same stream: three vertex numbers per triangle, the first `capacity` triangles
-hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity)
+static hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity)
 {
     hipLaunchKernelGGL(k_mesh_emit_indices, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->meshWPre, c->meshCount,
                        c->meshBase, c->meshVBase, indices, capacity);
     return hipGetLastError();
+}
+
+// ---- the entry points (additions: the reference has no mesher; DESIGN.md §Mesh extraction) -----------
+// The PLY writers (tf_mesh_write_ply*) are host code of their own in tf_mesh_ply.cpp.
+// count + prefix on the stream, then the total
+static tf_status mesh_count(tf_ctx* c, long long* n)
+{
+    TF_CHECK(tfk_mesh_count(c));
+    TF_CHECK(hipMemcpyAsync(n, c->meshBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    return sync_checked(c);
+}
+
+// tf_mesh_extract and tf_mesh_extract_attr, after the flush
+static tf_status mesh_extract(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity, long long* n_triangles)
+{
+    const bool any = dev_triangles || dev_normals || dev_colours;
+    if (!c || !n_triangles || capacity < 0 || (capacity > 0 && !any)) return TF_INVALID_ARG;
+    if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long n = 0;
+    tf_status s = mesh_count(c, &n);
+    if (s != TF_OK) return s;
+    *n_triangles = n;
+    if (capacity == 0 || !any || n == 0) return TF_OK;
+    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
+    if (dev_normals || dev_colours) {
+        TF_CHECK(tfk_mesh_emit_attr(c, dev_triangles, dev_normals, dev_colours, capacity));
+    } else {
+        TF_CHECK(tfk_mesh_emit(c, dev_triangles, capacity));
+    }
+    return sync_checked(c);
+}
+
+extern "C" tf_status tf_mesh_extract(tf_ctx* c, float* dev_triangles, long long capacity, long long* n_triangles)
+{
+    TF_FLUSH(c);
+    return mesh_extract(c, dev_triangles, nullptr, nullptr, capacity, n_triangles);
+}
+
+extern "C" tf_status tf_mesh_extract_attr(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity,
+                                          long long* n_triangles)
+{
+    TF_FLUSH(c);
+    return mesh_extract(c, dev_triangles, dev_normals, dev_colours, capacity, n_triangles);
+}
+
+// What the tf_mesh_save_ply* share: `bytes` of output, written by emit(dev) on the context stream into a
+// temporary device buffer, brought to *host (malloc'd, the caller frees; nullptr when bytes == 0)
+template <class Emit>
+static tf_status mesh_download(tf_ctx* c, size_t bytes, char** host, Emit emit)
+{
+    *host = nullptr;
+    if (bytes == 0) return TF_OK;
+    char* dev = nullptr;
+    TfCtxMem tmp(c->mem.fns());                         // the device buffer, freed when this returns
+    *host = (char*)malloc(bytes);
+    if (!*host) return TF_OOM;
+    if (tmp.alloc(&dev, bytes) != 0) { (void)hipGetLastError(); free(*host); *host = nullptr; return TF_OOM; }
+    hipError_t e = emit(dev);
+    if (e == hipSuccess) e = hipMemcpyAsync(*host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
+    tf_status s = tf_from_hip(e);
+    const tf_status s2 = sync_checked(c);              // (the stream is idle before the buffer goes)
+    if (s == TF_OK) s = s2;
+    return s;
+}
+
+// The attribute column at `off` of the downloaded buffer when `want`ed, else nullptr.  An empty mesh has no
+// buffer: its columns are still declared in the file (a non-null dummy, never read).
+template <class T>
+static const T* mesh_column(const char* host, size_t off, bool want)
+{
+    static const float none = 0.0f;
+    return !want ? nullptr : host ? (const T*)(host + off) : (const T*)&none;
+}
+
+// tf_mesh_save_ply (attrs 0) and tf_mesh_save_ply_attr, after the flush
+static tf_status mesh_save_ply(tf_ctx* c, const char* path, int attrs)
+{
+    if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS))) return TF_INVALID_ARG;
+    if ((attrs & TF_MESH_COLOURS) && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long n = 0;
+    tf_status s = mesh_count(c, &n);
+    if (s != TF_OK) return s;
+    const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
+    // one allocation each side: positions, then normals, then colours
+    const size_t bt = sizeof(float) * 9 * (size_t)n, bn = nrm ? bt : 0, bc = col ? 12 * (size_t)n : 0;
+    char* host = nullptr;
+    s = mesh_download(c, bt + bn + bc, &host, [&](char* dev) {
+        if (!nrm && !col) return tfk_mesh_emit(c, (float*)dev, n);
+        return tfk_mesh_emit_attr(c, (float*)dev, nrm ? (float*)(dev + bt) : nullptr, col ? (unsigned char*)(dev + bt + bn) : nullptr, n);
+    });
+    if (s == TF_OK)
+        s = tf_mesh_write_ply_attr(path, (const float*)host, mesh_column<float>(host, bt, nrm), mesh_column<uint8_t>(host, bt + bn, col), n);
+    free(host);
+    return s;
+}
+
+extern "C" tf_status tf_mesh_save_ply(tf_ctx* c, const char* path)
+{
+    TF_FLUSH(c);
+    return mesh_save_ply(c, path, 0);
+}
+
+extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attrs)
+{
+    TF_FLUSH(c);
+    return mesh_save_ply(c, path, attrs);
+}
+
+// ---- indexed mesh extraction (additions; DESIGN.md §Mesh extraction, indexed) ---------------------------
+// triangle and vertex totals after the count passes
+static tf_status mesh_index_count(tf_ctx* c, long long* nv, long long* nt)
+{
+    const hipError_t e = tfk_mesh_index_count(c);
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return TF_OOM; }
+    TF_CHECK(e);
+    TF_CHECK(hipMemcpyAsync(nt, c->meshBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipMemcpyAsync(nv, c->meshVBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    return sync_checked(c);
+}
+
+extern "C" tf_status tf_mesh_extract_indexed(tf_ctx* c, float* dev_vertices, float* dev_normals, uint8_t* dev_colours,
+                                             long long vertex_capacity, uint32_t* dev_indices, long long triangle_capacity,
+                                             long long* n_vertices, long long* n_triangles)
+{
+    TF_FLUSH(c);
+    const bool any = dev_vertices || dev_normals || dev_colours;
+    if (!c || !n_vertices || !n_triangles || vertex_capacity < 0 || triangle_capacity < 0) return TF_INVALID_ARG;
+    if ((vertex_capacity > 0 && !any) || (triangle_capacity > 0 && !dev_indices)) return TF_INVALID_ARG;
+    if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long nv = 0, nt = 0;
+    tf_status s = mesh_index_count(c, &nv, &nt);
+    if (s != TF_OK) return s;
+    *n_vertices = nv;
+    *n_triangles = nt;
+    if (nv > 0xffffffffLL) return TF_INDEX_RANGE;
+    const bool verts = any && vertex_capacity > 0 && nv > 0, tris = dev_indices && triangle_capacity > 0 && nt > 0;
+    if (!verts && !tris) return TF_OK;
+    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
+    if (verts) TF_CHECK(tfk_mesh_emit_vertices(c, dev_vertices, dev_normals, dev_colours, vertex_capacity));
+    if (tris) TF_CHECK(tfk_mesh_emit_indices(c, dev_indices, triangle_capacity));
+    return sync_checked(c);
+}
+
+extern "C" tf_status tf_mesh_save_ply_indexed(tf_ctx* c, const char* path, int attrs)
+{
+    TF_FLUSH(c);
+    if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS | TF_MESH_INDEXED))) return TF_INVALID_ARG;
+    if ((attrs & TF_MESH_COLOURS) && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long nv = 0, nt = 0;
+    tf_status s = mesh_index_count(c, &nv, &nt);
+    if (s != TF_OK) return s;
+    if (nv > 0x7fffffffLL) return TF_INDEX_RANGE;       // (the PLY's indices are int)
+    const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
+    // one allocation each side: positions, normals, colours, indices
+    const size_t bp = 12 * (size_t)nv, bn = nrm ? bp : 0, bc = col ? 4 * (size_t)nv : 0, bi = 12 * (size_t)nt;
+    char* host = nullptr;
+    s = mesh_download(c, nt > 0 ? bp + bn + bc + bi : 0, &host, [&](char* dev) {
+        const hipError_t e = tfk_mesh_emit_vertices(c, (float*)dev, nrm ? (float*)(dev + bp) : nullptr, col ? (unsigned char*)(dev + bp + bn) : nullptr, nv);
+        return e == hipSuccess ? tfk_mesh_emit_indices(c, (unsigned*)(dev + bp + bn + bc), nt) : e;
+    });
+    if (s == TF_OK)
+        s = tf_mesh_write_ply_indexed(path, (const float*)host, mesh_column<float>(host, bp, nrm), mesh_column<uint8_t>(host, bp + bn, col),
+                                      nt > 0 ? nv : 0, host ? (const uint32_t*)(host + bp + bn + bc) : nullptr, nt);
+    free(host);
+    return s;
 }

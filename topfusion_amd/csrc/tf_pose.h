@@ -1,6 +1,6 @@
 // tf_pose.h -- device-side pose algebra shared by several kernels (cv::Affine3f *, inv;
 // InfiniTAM Matrix4::inv) and the derived per-frame matrices; plus the frame-begin logic of
-// the device-driven TopFu::operator() (tf_capi.hip).
+// the device-driven TopFu::operator() (tf_frame.hip).
 #pragma once
 #include "tf_internal.h"
 

@@ -2,7 +2,7 @@
 // shared by its own kernels (tf_preproc.hip) and by the frame kernels that run later frames'
 // preprocessing in their grid's tail when a batch supplies them (k_raycast_pair: the next
 // frame's computeDists + pyramids + normals and the bilateral pass of the one after;
-// k_alloc_requests: a bilateral pass at the batch start; tf_capi.hip enqueue_frame).
+// k_alloc_requests: a bilateral pass at the batch start; tf_frame.hip enqueue_frame).
 #pragma once
 #include "tf_internal.h"
 #include "tf_pose.h"

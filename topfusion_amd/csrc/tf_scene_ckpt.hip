@@ -17,8 +17,13 @@
 // The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of its
 // own over int2 group counts (8 B per 256 entries) rather than k_mesh_prefix over 64-bit per-entry
 // counts, and shares no scratch with a mesh extraction.  No workgroup waits on another inside a grid.
-#include "tf_internal.h"
+#include "tf_host.h"
 #include "tf_scene_file.h"
+
+#include <chrono>
+#include <vector>
+#include <stdio.h>
+#include <stdlib.h>
 
 #define CK_WG 256
 typedef unsigned ck_u4 __attribute__((ext_vector_type(4)));
@@ -149,29 +154,22 @@ static int ck_grid(size_t items) { const size_t g = (items + CK_WG - 1) / CK_WG;
 
 // the context's checkpoint scratch, from the first call on: the group counts, their bases + totals and
 // the "not saveable" flag; the device staging buffer and its pinned twin, ckpt_chunk_blocks blocks each
-hipError_t tfk_ckpt_scratch(tf_ctx* c)
+static hipError_t tfk_ckpt_scratch(tf_ctx* c)
 {
     if (c->ckptGroup) return hipSuccess;
     const size_t ng = (size_t)ck_groups(c);
     const size_t stage = (size_t)c->ckpt_chunk_blocks * TF_SCENE_BLOCK_BYTES * (c->p.voxel_rgb ? 2 : 1);
-    hipError_t e = hipMalloc((void**)&c->ckptGroup, sizeof(int2) * (2 * ng + 2));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ckptStage, stage);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->ckptPinned, stage, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        if (c->ckptGroup) (void)hipFree(c->ckptGroup);
-        if (c->ckptStage) (void)hipFree(c->ckptStage);
-        c->ckptGroup = nullptr; c->ckptStage = nullptr; c->ckptPinned = nullptr;
-    }
-    return e;
+    return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->ckptGroup, sizeof(int2) * (2 * ng + 2)), TfCtxMem::dev(&c->ckptStage, stage),
+                                           TfCtxMem::pin(&c->ckptPinned, stage, hipHostMallocDefault) }));
 }
 
-size_t tfk_ckpt_stage_bytes(const tf_ctx* c)
+static size_t tfk_ckpt_stage_bytes(const tf_ctx* c)
 {
     return (size_t)c->ckpt_chunk_blocks * TF_SCENE_BLOCK_BYTES * (c->p.voxel_rgb ? 2 : 1);
 }
 
 // count + prefix; totals[0] = {records, blocks}, totals[1].x = the "not saveable" flag (device addresses)
-hipError_t tfk_ckpt_count(tf_ctx* c, const int2** totals)
+static hipError_t tfk_ckpt_count(tf_ctx* c, const int2** totals)
 {
     const int ng = ck_groups(c);
     int2* cnt = c->ckptGroup;
@@ -187,7 +185,7 @@ hipError_t tfk_ckpt_count(tf_ctx* c, const int2** totals)
 }
 
 // after tfk_ckpt_count: records (n_records x 24 B) and the stored blocks' ptr list, device buffers of the caller
-hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr)
+static hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr)
 {
     hipLaunchKernelGGL(k_ckpt_records, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->n_total,
                        c->ckptGroup + ck_groups(c), (ck_u2*)records, blockPtr);
@@ -195,24 +193,307 @@ hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr)
 }
 
 // nb <= ckpt_chunk_blocks blocks of the list into / out of the staging buffer
-hipError_t tfk_ckpt_gather(tf_ctx* c, const int* blockPtr, int nb)
+static hipError_t tfk_ckpt_gather(tf_ctx* c, const int* blockPtr, int nb)
 {
     hipLaunchKernelGGL(k_ckpt_gather, dim3(ck_grid((size_t)nb * 256)), dim3(CK_WG), 0, c->stream, c->vba,
                        c->p.voxel_rgb ? c->vba_rgb : nullptr, blockPtr, nb, (ck_u4*)c->ckptStage);
     return hipGetLastError();
 }
 
-hipError_t tfk_ckpt_scatter(tf_ctx* c, const int* blockPtr, int nb)
+static hipError_t tfk_ckpt_scatter(tf_ctx* c, const int* blockPtr, int nb)
 {
     hipLaunchKernelGGL(k_ckpt_scatter, dim3(ck_grid((size_t)nb * 256)), dim3(CK_WG), 0, c->stream, c->vba,
                        c->p.voxel_rgb ? c->vba_rgb : nullptr, blockPtr, nb, (const ck_u4*)c->ckptStage);
     return hipGetLastError();
 }
 
-hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_records)
+static hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_records)
 {
     if (n_records == 0) return hipSuccess;
     hipLaunchKernelGGL(k_ckpt_apply, dim3(ck_grid((size_t)n_records)), dim3(CK_WG), 0, c->stream, (const ck_u2*)records, n_records, c->hash,
                        c->visType);
     return hipGetLastError();
+}
+
+// ---- the entry points --------------------------------------------------------------------------------
+// what the last save / load spent (tf_scene_ckpt_times): the host clock around the synchronous steps, and,
+// on a context created with TFUSION_CKPT_TIMING=1, the kernels by HIP events on the stream
+enum { CK_T_INDEX = 0, CK_T_BLOCKS = 1, CK_T_COPY = 2, CK_T_FILE = 3, CK_T_CALL = 4, CK_T_BLOCK_BYTES = 5, CK_T_CHECK = 6 };
+static double ck_now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+// the kernels enqueued by `launch`; with ckpt_timing waited for and timed into slot `which`
+template <class F>
+static tf_status ck_timed_kernels(tf_ctx* c, int which, F launch)
+{
+    if (!c->ckpt_timing) {
+        TF_CHECK(launch());
+        return TF_OK;
+    }
+    if (!c->ckptEv[0]) {
+        TF_CHECK(hipEventCreate(&c->ckptEv[0]));
+        TF_CHECK(hipEventCreate(&c->ckptEv[1]));
+    }
+    TF_CHECK(hipEventRecord(c->ckptEv[0], c->stream));
+    TF_CHECK(launch());
+    TF_CHECK(hipEventRecord(c->ckptEv[1], c->stream));
+    TF_CHECK(hipEventSynchronize(c->ckptEv[1]));
+    float ms = 0;
+    TF_CHECK(hipEventElapsedTime(&ms, c->ckptEv[0], c->ckptEv[1]));
+    c->ckpt_ms[which] += ms;
+    return TF_OK;
+}
+
+// `bytes` of device memory to the file through the pinned buffer, a staging chunk at a time
+// (bound > 0: the bytes are a list of ints that must lie in [0, bound), as load will require)
+static tf_status ckpt_d2h_write(tf_ctx* c, FILE* f, const void* dev, size_t bytes, int bound = 0)
+{
+    const size_t cap = tfk_ckpt_stage_bytes(c);
+    for (size_t o = 0; o < bytes; o += cap) {
+        const size_t n = bytes - o < cap ? bytes - o : cap;
+        const double t0 = ck_now_ms();
+        TF_CHECK(hipMemcpyAsync(c->ckptPinned, (const char*)dev + o, n, hipMemcpyDeviceToHost, c->stream));
+        TF_CHECK(hipStreamSynchronize(c->stream));
+        const double t1 = ck_now_ms();
+        if (bound > 0 && !tf_scene_list_within(c->ckptPinned, n / 4, bound)) return TF_INVALID_ARG;
+        if (fwrite(c->ckptPinned, 1, n, f) != n) return TF_INVALID_ARG;
+        c->ckpt_ms[CK_T_COPY] += t1 - t0;
+        c->ckpt_ms[CK_T_FILE] += ck_now_ms() - t1;
+    }
+    return TF_OK;
+}
+
+// ... and host bytes to device memory the same way
+static tf_status ckpt_h2d(tf_ctx* c, void* dev, const unsigned char* host, size_t bytes)
+{
+    const size_t cap = tfk_ckpt_stage_bytes(c);
+    for (size_t o = 0; o < bytes; o += cap) {
+        const size_t n = bytes - o < cap ? bytes - o : cap;
+        const double t0 = ck_now_ms();
+        memcpy(c->ckptPinned, host + o, n);
+        TF_CHECK(hipMemcpyAsync((char*)dev + o, c->ckptPinned, n, hipMemcpyHostToDevice, c->stream));
+        TF_CHECK(hipStreamSynchronize(c->stream));
+        c->ckpt_ms[CK_T_COPY] += ck_now_ms() - t0;
+    }
+    return TF_OK;
+}
+
+static tf_status scene_save(tf_ctx* c, FILE* f)
+{
+    TfCtxMem tmp(c->mem.fns());                            // the record table and the ptr list, freed when this returns
+    unsigned char* rec_dev = nullptr;
+    int* ptr_dev = nullptr;
+    TF_CHECK(tfk_ckpt_scratch(c));
+    tf_status s = sync_state(c);                           // counters, pose; TF_HIP_ERROR on a context in error
+    if (s != TF_OK) return s;
+    const TfDevState* st = c->st_host;
+    struct tf_scene_file_info info;
+    memset(&info, 0, sizeof(info));
+    info.params = c->p;
+    info.pose_algebra = c->pose_alg;
+    info.frame_counter = st->frame_counter;
+    info.lastFreeBlockId = st->lastFreeBlockId;
+    info.lastFreeExcessListId = st->lastFreeExcessListId;
+    info.noVisibleEntries = st->noVisibleEntries;
+    memcpy(info.pose, st->pose, sizeof(info.pose));
+    const int2* totals_dev = nullptr;
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_count(c, &totals_dev); });
+    if (s != TF_OK) return s;
+    int2 totals[2];
+    TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    if (totals[1].x) return TF_INVALID_ARG;                // an entry's ptr lies outside the VBA (uploaded tables)
+    info.n_records = totals[0].x;
+    info.n_blocks_stored = totals[0].y;
+    TfSceneLayout lay;
+    if (!tf_scene_layout(&info, &lay)) return TF_INVALID_ARG;      // counters outside their lists (tf_set_counters)
+    info.file_bytes = (long long)lay.file_bytes;
+    unsigned char hdr[TF_SCENE_HEADER_BYTES];
+    uint32_t records_crc = 0;
+    tf_scene_header_encode(&info, records_crc, hdr);       // rewritten at the end with the records' checksum
+    if (fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) return TF_INVALID_ARG;
+    const size_t rec_bytes = (size_t)info.n_records * TF_SCENE_RECORD_BYTES;
+    TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_records(c, rec_dev, ptr_dev); });
+    if (s != TF_OK) return s;
+    {   // the record table: to the host whole (24 B per record), checked by load's own rule before any block
+        // moves -- chain offsets, duplicate ptr (tables that came through tf_upload) -- then summed and written
+        std::vector<unsigned char> rec(rec_bytes);
+        double t0 = ck_now_ms();
+        const size_t cap = tfk_ckpt_stage_bytes(c);
+        for (size_t o = 0; o < rec_bytes; o += cap) {
+            const size_t n = rec_bytes - o < cap ? rec_bytes - o : cap;
+            TF_CHECK(hipMemcpyAsync(c->ckptPinned, (const char*)rec_dev + o, n, hipMemcpyDeviceToHost, c->stream));
+            TF_CHECK(hipStreamSynchronize(c->stream));
+            memcpy(rec.data() + o, c->ckptPinned, n);
+        }
+        double t1 = ck_now_ms();
+        c->ckpt_ms[CK_T_COPY] += t1 - t0;
+        s = tf_scene_records_check(rec.data(), info.n_records, &info.params, info.n_blocks_stored);
+        if (s != TF_OK) return s;
+        records_crc = tf_scene_crc32(0u, rec.data(), rec_bytes);
+        t0 = ck_now_ms();
+        c->ckpt_ms[CK_T_CHECK] += t0 - t1;
+        if (fwrite(rec.data(), 1, rec_bytes, f) != rec_bytes) return TF_INVALID_ARG;
+        c->ckpt_ms[CK_T_FILE] += ck_now_ms() - t0;
+    }
+    for (long long b0 = 0; b0 < info.n_blocks_stored && s == TF_OK; b0 += c->ckpt_chunk_blocks) {
+        const int nb = (int)(info.n_blocks_stored - b0 < c->ckpt_chunk_blocks ? info.n_blocks_stored - b0 : c->ckpt_chunk_blocks);
+        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_ckpt_gather(c, ptr_dev + b0, nb); });
+        if (s == TF_OK) s = ckpt_d2h_write(c, f, c->ckptStage, (size_t)nb * lay.block_bytes);
+        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)lay.block_bytes;     // read + written
+    }
+    if (s == TF_OK) s = ckpt_d2h_write(c, f, c->visibleIds, 4 * lay.n_vis, c->n_total);
+    if (s == TF_OK) s = ckpt_d2h_write(c, f, c->allocList, 4 * lay.n_alloc, c->p.n_blocks);
+    if (s == TF_OK) s = ckpt_d2h_write(c, f, c->excessList, 4 * lay.n_excess, c->p.n_excess);
+    for (int l = 0; l < TF_LEVELS && s == TF_OK; ++l) {
+        s = ckpt_d2h_write(c, f, c->prev_pts[l], lay.map_bytes[l]);
+        if (s == TF_OK) s = ckpt_d2h_write(c, f, c->prev_nrm[l], lay.map_bytes[l]);
+    }
+    if (s != TF_OK) return s;
+    tf_scene_header_encode(&info, records_crc, hdr);
+    if (fseeko(f, 0, SEEK_SET) != 0 || fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) return TF_INVALID_ARG;
+    return TF_OK;
+}
+
+extern "C" tf_status tf_scene_save(tf_ctx* c, const char* path)
+{
+    TF_FLUSH(c);
+    if (!c || !path || c->p.use_swapping) return TF_INVALID_ARG;
+    static_assert(TF_LEVELS == TF_SCENE_LEVELS, "the file stores the tracker's pyramid");
+    {   // a context in error saves nothing (checked before the file is created)
+        const tf_status s0 = sync_checked(c);
+        if (s0 != TF_OK) return s0;
+    }
+    FILE* f = fopen(path, "wb");
+    if (!f) return TF_INVALID_ARG;
+    const double t_call = ck_now_ms();
+    memset(c->ckpt_ms, 0, sizeof(c->ckpt_ms));
+    tf_status s = scene_save(c, f);
+    if (fclose(f) != 0 && s == TF_OK) s = TF_INVALID_ARG;
+    if (s != TF_OK) remove(path);                          // no half-written checkpoint
+    c->ckpt_ms[CK_T_CALL] = ck_now_ms() - t_call;
+    return s;
+}
+
+static bool bits_equal(float a, float b) { return memcmp(&a, &b, sizeof(float)) == 0; }
+
+// the validated file into the context (nothing here fails on the file's contents)
+static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct tf_scene_file_info& info, const TfSceneLayout& lay)
+{
+    TfCtxMem tmp(c->mem.fns());                            // the record table and the ptr list, freed when this returns
+    unsigned char* rec_dev = nullptr;
+    int* ptr_dev = nullptr;
+    TF_CHECK(tfk_ckpt_scratch(c));
+    TF_CHECK(tfk_reset_scene(c));                          // full: hash, VBA, colour, both lists (identity), block grid cells
+    TF_CHECK(hipMemsetAsync(c->visType, 0, (size_t)c->n_total, c->stream));
+    const size_t rec_bytes = (size_t)info.n_records * TF_SCENE_RECORD_BYTES;
+    TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
+    tf_status s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
+    if (s != TF_OK) return s;
+    {   // the stored blocks' ptr, in record order
+        std::vector<int> ptrs;
+        ptrs.reserve((size_t)info.n_blocks_stored);
+        const unsigned char* r = data + lay.records_off;
+        for (long long k = 0; k < info.n_records; ++k, r += TF_SCENE_RECORD_BYTES) {
+            int ptr;
+            memcpy(&ptr, r + 16, sizeof(int));
+            if (ptr >= 0) ptrs.push_back(ptr);
+        }
+        s = ckpt_h2d(c, ptr_dev, (const unsigned char*)ptrs.data(), sizeof(int) * ptrs.size());
+        if (s != TF_OK) return s;
+    }
+    for (long long b0 = 0; b0 < info.n_blocks_stored; b0 += c->ckpt_chunk_blocks) {
+        const int nb = (int)(info.n_blocks_stored - b0 < c->ckpt_chunk_blocks ? info.n_blocks_stored - b0 : c->ckpt_chunk_blocks);
+        s = ckpt_h2d(c, c->ckptStage, data + lay.blocks_off + (size_t)b0 * lay.block_bytes, (size_t)nb * lay.block_bytes);
+        if (s != TF_OK) return s;
+        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_ckpt_scatter(c, ptr_dev + b0, nb); });   // (waited for: the
+        if (s != TF_OK) return s;                                                                          // staging buffer is free again)
+        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)lay.block_bytes;
+    }
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {              // the block grid from the hash, as after a hash upload
+        const hipError_t e = tfk_ckpt_apply(c, rec_dev, info.n_records);
+        return e == hipSuccess ? tfk_grid_rebuild(c) : e;
+    });
+    if (s != TF_OK) return s;
+    s = ckpt_h2d(c, c->visibleIds, data + lay.vis_off, 4 * lay.n_vis);
+    if (s == TF_OK) s = ckpt_h2d(c, c->allocList, data + lay.alloc_off, 4 * lay.n_alloc);
+    if (s == TF_OK) s = ckpt_h2d(c, c->excessList, data + lay.excess_off, 4 * lay.n_excess);
+    size_t o = lay.maps_off;
+    for (int l = 0; l < TF_LEVELS && s == TF_OK; ++l) {
+        s = ckpt_h2d(c, c->prev_pts[l], data + o, lay.map_bytes[l]);
+        if (s == TF_OK) s = ckpt_h2d(c, c->prev_nrm[l], data + o + lay.map_bytes[l], lay.map_bytes[l]);
+        o += 2 * lay.map_bytes[l];
+    }
+    if (s != TF_OK) return s;
+    // what is not stored must not be seen stale: the next CreateExpectedDepths clears the whole range
+    // image, the raycast pair starts from the default tile order with zero costs (mesh scratch is
+    // recomputed by every extraction)
+    TF_CHECK(ed_spill_all(c));
+    TF_CHECK(tfk_tile_order_init(c));
+    s = sync_state(c);
+    if (s != TF_OK) return s;
+    TfDevState* st = c->st_host;
+    memcpy(st->pose, info.pose, sizeof(info.pose));
+    st->lastFreeBlockId = info.lastFreeBlockId;
+    st->lastFreeExcessListId = info.lastFreeExcessListId;
+    st->noVisibleEntries = info.noVisibleEntries;
+    st->frame_counter = info.frame_counter;
+    // the free lists and the blocks in use need not be what frames alone leave (a scene that came
+    // through tf_upload): every later reset clears everything (tf_reset.h)
+    st->scene_external = 1;
+    TF_CHECK(hipMemcpyAsync(c->st, c->st_host, sizeof(TfDevState), hipMemcpyHostToDevice, c->stream));
+    s = sync_checked(c);
+    if (s == TF_OK) c->frame_counter = info.frame_counter;
+    return s;
+}
+
+extern "C" tf_status tf_scene_load(tf_ctx* c, const char* path)
+{
+    TF_FLUSH(c);
+    if (!c || !path || c->p.use_swapping) return TF_INVALID_ARG;
+    {
+        const tf_status s0 = sync_checked(c);
+        if (s0 != TF_OK) return s0;
+    }
+    const double t_call = ck_now_ms();
+    FILE* f = fopen(path, "rb");
+    if (!f) return TF_INVALID_ARG;
+    long long size = -1;
+    if (fseeko(f, 0, SEEK_END) == 0) size = (long long)ftello(f);
+    if (size < TF_SCENE_HEADER_BYTES || fseeko(f, 0, SEEK_SET) != 0) { fclose(f); return TF_INVALID_ARG; }
+    memset(c->ckpt_ms, 0, sizeof(c->ckpt_ms));
+    unsigned char* data = (unsigned char*)malloc((size_t)size);
+    if (!data) { fclose(f); return TF_OOM; }
+    const size_t got = fread(data, 1, (size_t)size, f);
+    fclose(f);
+    c->ckpt_ms[CK_T_FILE] = ck_now_ms() - t_call;
+    struct tf_scene_file_info info;
+    TfSceneLayout lay;
+    const double t_check = ck_now_ms();
+    tf_status s = got == (size_t)size ? tf_scene_file_validate(data, got, &info, &lay) : TF_INVALID_ARG;
+    c->ckpt_ms[CK_T_CHECK] = ck_now_ms() - t_check;
+    if (s == TF_OK) {
+        const tf_params& a = info.params;
+        const tf_params& b = c->p;
+        if (a.cols != b.cols || a.rows != b.rows || a.n_buckets != b.n_buckets || a.n_excess != b.n_excess || a.n_blocks != b.n_blocks ||
+            a.voxel_rgb != b.voxel_rgb || a.use_swapping != 0 || !bits_equal(a.voxelSize, b.voxelSize) || !bits_equal(a.mu, b.mu) ||
+            a.maxW != b.maxW || info.noVisibleEntries > b.vis_capacity)
+            s = TF_INVALID_ARG;
+    }
+    if (s == TF_OK) s = scene_load(c, data, info, lay);
+    free(data);
+    c->ckpt_ms[CK_T_CALL] = ck_now_ms() - t_call;
+    return s;
+}
+
+extern "C" tf_status tf_scene_ckpt_times(tf_ctx* c, double ms[8])
+{
+    TF_FLUSH(c);
+    if (!c || !ms) return TF_INVALID_ARG;
+    memcpy(ms, c->ckpt_ms, sizeof(c->ckpt_ms));
+    return TF_OK;
 }
