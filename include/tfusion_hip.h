@@ -220,6 +220,12 @@ tf_status tf_get_pose_algebra(tf_ctx* ctx, int* algebra);
  * the lane-parallel Jacobi SVD).  Device buffers: sums 27 n floats, x 6 n floats, det n doubles
  * (may be NULL); asynchronous on `stream` (NULL: the null stream). */
 tf_status tf_icp_solve_systems(int algebra, const float* dev_sums, int n, float* dev_x, double* dev_det, void* stream);
+/* The record of the context's last estimateTransform (a frame's or a stage call's), as the device
+ * left it: the working affine (row-major 3x4; on a failed det check the last composition taken),
+ * the 27 sums of the last iteration run (the failing one's on failure), ok (1, 0 = det check
+ * failed, -1 = the launch reported a lost peer) and the iterations run.  Any pointer may be NULL.
+ * Synchronous. */
+tf_status tf_icp_get_result(tf_ctx* ctx, float affine_rt[12], float sums[27], int* ok, int* iterations);
 
 /* ---- stage entry points (operate on context state; parity tests) ------------- */
 /* computeDists + depthBilateralFilter + depthTruncation + depthBuildPyramid +

@@ -17,7 +17,7 @@ tf = TopFu(default_params(cols=W, rows=H, fx=fx, fy=fy, cx=cx, cy=cy), device=0)
 tf.process_frames(dev.ptr, 3)
 bench.device_sync()
 NW = 256
-S = 2 * NW + 10
+S = 2 * NW + 11
 buf = (ctypes.c_ulonglong * (64 * S))()
 _lib.load().tf_debug_icp_timeline(buf)
 tl = np.frombuffer(buf, dtype=np.uint64).reshape(64, S).astype(np.int64)
@@ -35,6 +35,8 @@ for i in range(its):
             f"pub {pub.min():5.2f}/{np.median(pub):5.2f}/{pub.max():5.2f} (max wg {int(pub.argmax())}) "
             f"wg0 pub {pub[0]:5.2f} gathered {g:5.2f} [tree+readlane {ph[0]:5.2f} unpack {ph[1]:5.2f} solve {ph[2]:5.2f} "
             f"rodrigues {ph[3]:5.2f} compose {ph[4]:5.2f} det {ph[5]:5.2f}] tail {tail:5.2f}")
+    if tl[i, 2 * NW + 10] > t0:                     # the det check in the window (wave IP_DETW's stamps)
+        line += f" [window: det issued {(tl[i, 2 * NW + 10] - t0) / 100.0:5.2f} done {ph[5]:5.2f}, solve end {ph[2]:5.2f}]"
     if nxt is not None:
         line += f" next-start {nxt.min():5.2f}/{np.median(nxt):5.2f}/{nxt.max():5.2f}"
         if tl[i + 1, 2 * NW + 8] > 0:               # the next iteration starts a level: its set-up

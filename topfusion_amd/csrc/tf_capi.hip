@@ -466,6 +466,19 @@ extern "C" tf_status tf_get_pose(tf_ctx* c, float rt[12])
     return TF_OK;
 }
 
+extern "C" tf_status tf_icp_get_result(tf_ctx* c, float affine_rt[12], float sums[27], int* ok, int* iterations)
+{
+    TF_FLUSH(c);
+    if (!c) return TF_INVALID_ARG;
+    tf_status s = sync_state(c);
+    if (s != TF_OK) return s;
+    if (affine_rt) memcpy(affine_rt, c->st_host->affine, sizeof(float) * 12);
+    if (sums) memcpy(sums, c->st_host->sums, sizeof(float) * 27);
+    if (ok) *ok = c->st_host->icp_ok;
+    if (iterations) *iterations = c->st_host->icp_iters;
+    return TF_OK;
+}
+
 extern "C" tf_status tf_get_stats(tf_ctx* c, tf_stats* stats)
 {
     TF_FLUSH(c);

@@ -34,8 +34,8 @@ extern "C" int tf_debug_icp_ts(unsigned long long* out)
 }
 #define IPT_NOW() __builtin_amdgcn_s_memrealtime()
 #define IPT_ADD(k, v) do { } while (0)
-// timeline of the last persistent launch: per iteration [256 starts][256 publishes][8 WG0 events]
-#define IPT_STRIDE (2 * ICP_NWG + 10)
+// timeline of the last persistent launch: per iteration [256 starts][256 publishes][11 WG0 events]
+#define IPT_STRIDE (2 * ICP_NWG + 11)
 __device__ unsigned long long g_icp_tl[64 * IPT_STRIDE];
 #define IPT_REC(it, slot) IPT_REC_T(it, slot, 0)
 // a stamp after a value: the value is an operand of a volatile asm placed before the stamp, so
@@ -52,6 +52,10 @@ __device__ unsigned long long g_icp_tl[64 * IPT_STRIDE];
 // between two stamps is that segment's issue time
 #define IPT_REC_T(it, slot, t) do { __builtin_amdgcn_sched_barrier(0); \
     if (threadIdx.x == (t) && (it) < 64) g_icp_tl[(it) * IPT_STRIDE + (slot)] = IPT_NOW(); \
+    __builtin_amdgcn_sched_barrier(0); } while (0)
+// the same by workgroup 0 alone (the window work's stamps)
+#define IPT_REC_T0(it, slot, t) do { __builtin_amdgcn_sched_barrier(0); \
+    if (blockIdx.x == 0 && threadIdx.x == (t) && (it) < 64) g_icp_tl[(it) * IPT_STRIDE + (slot)] = IPT_NOW(); \
     __builtin_amdgcn_sched_barrier(0); } while (0)
 extern "C" int tf_debug_icp_timeline(unsigned long long* out)
 {
@@ -83,6 +87,7 @@ extern "C" int tf_debug_icp_clock(unsigned long long* out)
 #define IPT_ADD(k, v) do { } while (0)
 #define IPT_REC(it, slot) do { } while (0)
 #define IPT_REC_T(it, slot, t) do { } while (0)
+#define IPT_REC_T0(it, slot, t) do { } while (0)
 #define IPT_REC_DEP(it, slot, val_) do { } while (0)
 #define IPT_CLK(it) do { } while (0)
 #endif
@@ -257,7 +262,8 @@ k_icp_iter(IcpLevel L, TfDevState* __restrict__ st, float* __restrict__ T, unsig
     float sm[27];
 #pragma unroll
     for (int q = 0; q < 27; ++q) sm[q] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tot), 2 * q));
-    if (lane < 27) st->sums[lane] = __shfl(tot, 2 * lane, 64);
+    const float sum_l = __shfl(tot, 2 * (lane & 31), 64);     // (by every lane: a disabled source lane reads as 0)
+    if (lane < 27) st->sums[lane] = sum_l;
     if (lane == 0) st->icp_iters += 1;
     // StreamHelper::get unpacking (projective_icp.cpp:51-61)
     float Am[6][6], bv[6];
@@ -340,6 +346,12 @@ k_icp_iter(IcpLevel L, TfDevState* __restrict__ st, float* __restrict__ T, unsig
 #define IP_NPART 8                               // residue classes of the final tree's first five steps
 #define IP_LDS_PAD (56 * 1024)
 #define IP_DETW (IP_WAVES - 1)                   // the wave that runs the det check off the critical path
+// The window: under the OpenCV algebras an iteration's solve (wave 0) takes about 8 us, during
+// which the workgroup's other waves are parked at a barrier with no hand-off poll in flight -- from
+// the __syncthreads_or that ends the hop-2 gather to the __syncthreads() after the compose.
+#ifndef IP_DET_WINDOW
+#define IP_DET_WINDOW 1                          // the det check of iteration k beside solve k (A/B: 0 = deferred
+#endif                                           // into iteration k + 1's rows, as the canonical instance keeps it)
 // Column sums go to the residue-class leader (workgroup wg % 8).  Each leader publishes its XCD
 // (HW_REG_XCC_ID) at launch; a workgroup that finds its leader on its own XCD publishes its
 // columns with plain stores (kept in the shared L2), any other with write-through sc1 stores.
@@ -634,10 +646,13 @@ __device__ __forceinline__ float ip_residue_tree(const float* c)
 // (ip_residue_tree) and publishes 27 partials; every workgroup then gathers the 8 x 27
 // partials, runs the last three tree steps and the solve / Rodrigues / compose itself,
 // redundantly and bit-identically -- two small hops per iteration, no broadcast.  The det check
-// of iteration k (cv::determinant, projective_icp.cpp:197-203) runs on wave IP_DETW while
-// iteration k+1 computes its rows and is settled before anything of k+1 is published: on
-// failure the affine of k-1 is restored and the loop ends exactly where the serial order ends
-// it.  The solve (wave 0) is the only serial work between two iterations.
+// of iteration k (cv::determinant, projective_icp.cpp:197-203) runs on wave IP_DETW.  Under the
+// OpenCV algebras it runs beside solve k, in the window (IP_DET_WINDOW), and is settled at the
+// iteration's closing barrier: on failure the composed affine is not taken and the loop ends.
+// The canonical instance, whose solve leaves no window, runs it while iteration k+1 computes its
+// rows and settles it before anything of k+1 is published: on failure the affine of k-1 is
+// restored.  Either way the loop ends exactly where the serial order ends it.  The solve
+// (wave 0) is the only serial work between two iterations.
 template <int ALG>
 __global__ void __launch_bounds__(64 * IP_WAVES)
 k_icp_frame(IcpFrameArgs a)
@@ -705,6 +720,9 @@ k_icp_frame(IcpFrameArgs a)
     for (int i = 0; i < 12; ++i) aff[i] = (i % 5 == 0) ? 1.0f : 0.0f;     // affine = Identity
     int status = 1, done = 0;
     float last_sums = 0.f;
+    // det check in the window (the OpenCV algebras): settled at the iteration's closing barrier,
+    // nothing is deferred; the canonical instance has no window (its solve takes 0.5 us)
+    constexpr bool DET_WIN = IP_DET_WINDOW && ALG != 0;
 
     bool det_pending = false;
 
@@ -744,7 +762,7 @@ k_icp_frame(IcpFrameArgs a)
             ++gen;
             IPT_REC(done, wg);
             IPT_CLK(done);
-            if (det_pending && wave == IP_DETW) {
+            if (!DET_WIN && det_pending && wave == IP_DETW) {
                 float Am[6][6], bv[6], det_sm[27];
 #pragma unroll
                 for (int q = 0; q < 27; ++q) det_sm[q] = det_sm_s[q];
@@ -789,7 +807,7 @@ k_icp_frame(IcpFrameArgs a)
                 if (!(lane & 1) && (lane >> 1) < 27) red[sl][lane >> 1] = tot;
             }
             __syncthreads();
-            if (det_pending) {                                    // settle iteration k's det check
+            if (!DET_WIN && det_pending) {                        // settle iteration k's det check
                 det_pending = false;
                 if (!det_ok_s) {
                     status = 0;
@@ -889,8 +907,15 @@ k_icp_frame(IcpFrameArgs a)
                     IPT_REC_DEP(done, 2 * ICP_NWG + 6, sm[26] + sm[0]);
                     ip_unpack(sm, Am, bv);
                     IPT_REC(done, 2 * ICP_NWG + 2);
-                    if (wave == IP_DETW) {                             // det after the barrier
-                        if (lane < 27) det_sm_s[lane] = tot;
+                    if (wave == IP_DETW) {
+                        if constexpr (DET_WIN) {                       // det beside the solve
+                            IPT_REC_T0(done, 2 * ICP_NWG + 10, 64 * IP_DETW);
+                            const double det = icp_det6<ALG>(Am);
+                            if (lane == 0) det_ok_s = !(fabs(det) < 1e-15 || isnan(det));
+                            IPT_REC_T0(done, 2 * ICP_NWG + 5, 64 * IP_DETW);
+                        } else if (lane < 27) {                        // det after the barrier
+                            det_sm_s[lane] = tot;
+                        }
                     } else {                                           // solve -> Rodrigues -> compose
 #if IP_TAIL_ROWS
                       if constexpr (ALG == 0) {                          // row layout (tf_icp_tail.h)
@@ -976,10 +1001,15 @@ k_icp_frame(IcpFrameArgs a)
                 __syncthreads();
                 IPT_REC(done, 2 * ICP_NWG + 1);
                 status = any_timeout ? 2 : 1;
-                det_pending = !any_timeout;
-                if (wave == 0 && lane == 0) {
+                if constexpr (DET_WIN) {
+                    // projective_icp.cpp:197-203: the iteration counts, its composed affine is not taken
+                    if (!any_timeout && !det_ok_s) status = 0;
+                } else {
+                    det_pending = !any_timeout;
+                    if (wave == 0 && lane == 0) {
 #pragma unroll
-                    for (int i = 0; i < 12; ++i) aff_prev_s[i] = aff[i];
+                        for (int i = 0; i < 12; ++i) aff_prev_s[i] = aff[i];
+                    }
                 }
                 if (status == 1) {
 #pragma unroll
@@ -991,7 +1021,7 @@ k_icp_frame(IcpFrameArgs a)
             __syncthreads();                       // red[] / aff_s reuse in the next iteration
         }
     }
-    if (det_pending) {                                            // the last iteration's det check
+    if (!DET_WIN && det_pending) {                                // the last iteration's det check
         if (wave == IP_DETW) {
             float Am[6][6], bv[6], det_sm[27];
 #pragma unroll
