@@ -159,6 +159,34 @@ namespace tfusion
             return s;
         }
 
+        // Mesh extraction over the scene's context (additions, as TopFu::extractMesh / saveMesh; the class a
+        // swapping caller holds, so this is where the whole map leaves the device).  flags: 0 = the resident
+        // blocks, TF_MESH_WHOLE = every block of either tier (tf_mesh_extract_whole).  Triangles as 9 floats
+        // each, resized to fit, normals (9 floats per triangle) beside them when the pointer is not null;
+        // returns the triangle count.
+        long long extractMesh(cuda::DeviceArray<float>& triangles, cuda::DeviceArray<float>* normals = nullptr, int flags = 0)
+        {
+            if (flags & ~TF_MESH_WHOLE) tf_engine_check(TF_INVALID_ARG, "Scene::extractMesh");
+            const bool whole = (flags & TF_MESH_WHOLE) != 0;
+            auto call = [&](float* t, float* n, long long cap, long long* count) {
+                return whole ? tf_mesh_extract_whole(ctx_, t, n, cap, count) : tf_mesh_extract_attr(ctx_, t, n, nullptr, cap, count);
+            };
+            long long n = 0, m = 0;
+            tf_engine_check(call(nullptr, nullptr, 0, &n), "Scene::extractMesh");
+            triangles.create((size_t)n * 9);
+            if (normals) normals->create((size_t)n * 9);
+            if (n > 0) tf_engine_check(call(triangles.ptr(), normals ? normals->ptr() : nullptr, n, &m), "Scene::extractMesh");
+            return n;
+        }
+        // the mesh as a binary PLY with welded vertices; attrs = TF_MESH_NORMALS and / or TF_MESH_WHOLE (the
+        // whole mesh is downloaded and welded in one piece: the host's memory bounds it), TF_MESH_COLOURS on a
+        // Voxel_s_rgb scene, TF_MESH_INDEXED for the resident vertex table as it leaves the GPU
+        void saveMesh(const std::string& path, int attrs = 0)
+        {
+            if (attrs & TF_MESH_INDEXED) tf_engine_check(tf_mesh_save_ply_indexed(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_indexed");
+            else tf_engine_check(tf_mesh_save_ply_attr(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_attr");
+        }
+
     private:
         tf_ctx* ctx_ = nullptr;
         Intr intr_;

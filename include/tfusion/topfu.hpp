@@ -279,7 +279,24 @@ namespace tfusion
             }
             return n;
         }
-        // the mesh as a PLY with nx ny nz (TF_MESH_NORMALS) and / or red green blue alpha (TF_MESH_COLOURS)
+        // extractMesh by flags: TF_MESH_WHOLE = the reading over both tiers of a swapping scene
+        // (tf_mesh_extract_whole; TopFu itself runs without swapping, where it is the resident mesh byte for
+        // byte -- a swapping caller holds a Scene, engines.hpp, which has the same pair), 0 = as above
+        long long extractMesh(cuda::DeviceArray<float>& triangles, cuda::DeviceArray<float>* normals, int flags)
+        {
+            if (!(flags & TF_MESH_WHOLE)) return extractMesh(triangles, normals, (cuda::DeviceArray<unsigned char>*)nullptr);
+            long long n = 0;
+            check(tf_mesh_extract_whole(ctx_, nullptr, nullptr, 0, &n), "tf_mesh_extract_whole");
+            triangles.create((size_t)n * 9);
+            if (normals) normals->create((size_t)n * 9);
+            if (n > 0) {
+                long long m = 0;
+                check(tf_mesh_extract_whole(ctx_, triangles.ptr(), normals ? normals->ptr() : nullptr, n, &m), "tf_mesh_extract_whole");
+            }
+            return n;
+        }
+        // the mesh as a PLY with nx ny nz (TF_MESH_NORMALS) and / or red green blue alpha (TF_MESH_COLOURS);
+        // TF_MESH_WHOLE passes through to tf_mesh_save_ply_attr (not with colours, not indexed);
         // with TF_MESH_INDEXED: the indexed vertex table as it leaves the GPU, no host weld (tf_mesh_save_ply_indexed)
         void saveMesh(const std::string& path, int attrs)
         {

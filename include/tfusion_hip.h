@@ -443,9 +443,20 @@ tf_status tf_time_stage(tf_ctx* ctx, int stage, const float pose_rt[12], int ite
  * Marching tetrahedra on the Kuhn split of every voxel cube of every allocated block (hash entries
  * with ptr >= 0), specified to the bit in DESIGN.md (Mesh extraction): a cube is meshed when all
  * eight corner voxels exist with w > 0, a corner is inside when its sdf short is < 0, vertices are
- * world positions (voxel coordinate * voxelSize, as integration and raycast place them).  Blocks
- * swapped out to the GlobalCache (ptr == -1) are not meshed and count as missing for their
- * neighbours' cubes.  The scene is only read. */
+ * world positions (voxel coordinate * voxelSize, as integration and raycast place them).  The scene
+ * is only read.
+ * Two readings of a swapping scene.  The resident one (every entry point without TF_MESH_WHOLE): blocks
+ * swapped out to the GlobalCache (ptr == -1) are not meshed and count as missing for their neighbours'
+ * cubes, and a block is read as it lies in the VBA.  The whole one (tf_mesh_extract_whole, TF_MESH_WHOLE in
+ * tf_mesh_save_ply_attr's attrs): every hash entry that holds voxel data in either tier is meshed, and every
+ * block -- own, cube neighbour, gradient neighbour -- is resolved the same way: the active block; the stored
+ * block as it is where the entry is swapped out; CombineVoxelInformation(stored, active, maxW) per voxel
+ * where a stored block still awaits its merge, i.e. what the engine's next IntegrateGlobalIntoLocal would
+ * write (Mesh extraction, the whole map).  The GlobalCache is read where it lies; nothing is
+ * swapped in and neither tier is written.  On a context with no stored data -- any context without
+ * use_swapping, a swapping one before its first eviction -- the whole mesh is byte-identical to the
+ * resident one.  The indexed form is resident-only: its vertex numbering is keyed by VBA block, which a
+ * stored block does not have. */
 /* addition (no reference counterpart): triangles in a fixed order (ascending hash entry, voxel
  * x + 8y + 64z, tetrahedron, triangle of the case) as float[n][9] -- three xyz vertices, right-hand
  * normal towards sdf >= 0 -- into the device buffer: the first min(n, capacity) of them;
@@ -484,8 +495,20 @@ tf_status tf_mesh_write_ply_attr(const char* path, const float* host_triangles, 
                                  const uint8_t* host_colours, long long n);
 /* addition (no reference counterpart): count, extract into temporary device buffers, download,
  * tf_mesh_write_ply_attr; attrs = TF_MESH_NORMALS | TF_MESH_COLOURS or either or 0; TF_OOM when the
- * buffers cannot be had, TF_INVALID_ARG for TF_MESH_COLOURS without voxel_rgb */
+ * buffers cannot be had, TF_INVALID_ARG for TF_MESH_COLOURS without voxel_rgb.  With TF_MESH_WHOLE the file
+ * holds the whole reading's mesh (normals too when asked for; TF_MESH_COLOURS with it is TF_INVALID_ARG: a
+ * swapping scene has no colour plane).  The writer is the same: one device buffer, one host copy, one weld,
+ * so the caller's memory bounds the mesh that can be saved in one piece. */
 tf_status tf_mesh_save_ply_attr(tf_ctx* ctx, const char* path, int attrs);
+
+#define TF_MESH_WHOLE 8
+/* addition (no reference counterpart): tf_mesh_extract_attr's positions and normals in the whole reading
+ * (above): the same order (ascending hash entry over the entries that resolve, then voxel, tetrahedron,
+ * triangle), the same capacity, count-only and NULL rules (either pointer may be NULL; with both NULL
+ * capacity must be 0), *n_triangles = the full count.  A normal's "usable voxel" is one whose block resolves
+ * and whose resolved w > 0.  Synchronous; the scene and the GlobalCache are only read. */
+tf_status tf_mesh_extract_whole(tf_ctx* ctx, float* dev_triangles, float* dev_normals, long long capacity,
+                                long long* n_triangles);
 
 /* The indexed form (Mesh extraction, indexed): the same triangles with shared vertices.  A vertex
  * is the cube edge it lies on -- (p, d), p the edge's lower voxel, d in {0,1}^3 \ {0} -- and exists when a
@@ -515,7 +538,9 @@ tf_status tf_mesh_write_ply_indexed(const char* path, const float* host_vertices
                                     const uint8_t* host_colours, long long nv, const uint32_t* host_indices, long long nt);
 /* addition (no reference counterpart): count, extract the indexed buffers into a temporary device buffer,
  * download them (and nothing else), tf_mesh_write_ply_indexed; attrs as tf_mesh_save_ply_attr's
- * (TF_MESH_INDEXED may be set and changes nothing); TF_INDEX_RANGE beyond 2^31 - 1 vertices */
+ * (TF_MESH_INDEXED may be set and changes nothing); TF_INDEX_RANGE beyond 2^31 - 1 vertices.  Resident
+ * only: TF_MESH_WHOLE in attrs is TF_INVALID_ARG (see DESIGN.md §10 for what rekeying the edge bits by hash
+ * entry would take) */
 tf_status tf_mesh_save_ply_indexed(tf_ctx* ctx, const char* path, int attrs);
 
 /* ---- scene checkpoints (additions: the reference cannot save its map; DESIGN.md §5 Scene checkpoints) --

@@ -17,6 +17,7 @@ TF_OK, TF_ICP_FAIL, TF_INVALID_ARG, TF_OOM, TF_HIP_ERROR, TF_NO_DEVICE = range(6
 TF_INDEX_RANGE = 6                             # tf_mesh_extract_indexed: more vertices than a u32 numbers
 TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2        # tf_mesh_save_ply_attr's attrs
 TF_MESH_INDEXED = 4
+TF_MESH_WHOLE = 8                              # the reading over both tiers of a swapping scene (tf_mesh_extract_whole)
 
 STAGE_NAMES = ("preprocess", "icp", "alloc", "integrate", "raycast_render", "grey", "expected_depths",
                "raycast_icp", "icp_maps")
@@ -188,6 +189,7 @@ def load():
         "tf_mesh_extract_attr": ([P, P, P, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)], I),
         "tf_mesh_write_ply_attr": ([ctypes.c_char_p, P, P, P, ctypes.c_longlong], I),
         "tf_mesh_save_ply_attr": ([P, ctypes.c_char_p, I], I),
+        "tf_mesh_extract_whole": ([P, P, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)], I),
         "tf_mesh_extract_indexed": ([P, P, P, P, ctypes.c_longlong, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong),
                                      ctypes.POINTER(ctypes.c_longlong)], I),
         "tf_mesh_write_ply_indexed": ([ctypes.c_char_p, P, P, P, ctypes.c_longlong, P, ctypes.c_longlong], I),

@@ -14,6 +14,12 @@
 //                   workgroup, triangles written at base + offset while below the caller's capacity
 //   k_mesh_emit_attr<NORMALS, COLOURS> : k_mesh_emit with per-vertex normals (TSDF gradient) and / or colours
 //                   (colour plane) beside the positions, from the larger tile (mesh_stage_attr)
+// k_mesh_count, k_mesh_emit and k_mesh_emit_attr<true, false> exist in two readings of the scene, chosen by the
+// scene type they are instantiated with (tf_mesh_dev.h): MeshScene, the resident blocks as above, and
+// MeshSceneWhole (TF_MESH_WHOLE, tf_mesh_extract_whole), where an entry is live when it holds voxel data in
+// either tier and every block -- own, cube neighbour, gradient neighbour -- is resolved over the VBA and the
+// GlobalCache: active, stored, or CombineVoxelInformation of both where a merge is pending.  Counts and bases
+// are per hash entry in both, so the scratch and k_mesh_prefix are shared.
 //
 // The indexed form (shared vertices, u32 indices; DESIGN.md §Mesh extraction, indexed).  A vertex is its
 // Kuhn edge (tf_mesh.h): per VBA block a mask of 512 x 7 edge bits (TFM_EDGE_WORDS words, indexed by the
@@ -27,7 +33,9 @@
 //                          the vertex base + prefix + popcount below
 //   k_mesh_emit_indices  : k_mesh_emit's structure; a triangle vertex (lo, hi) -> owner block, bit, index
 //
-// No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) is only read.
+// The indexed form keys its edge bits by VBA block, which a stored block does not have: it stays resident-only.
+//
+// No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) and the GlobalCache are only read.
 #include "tf_mesh_dev.h"
 #include "tf_host.h"
 
@@ -52,6 +60,19 @@ struct MeshHasBlock {
         return false;
     }
 };
+// ... the whole reading's: entries whose block resolves in either tier (mesh_entry_resolves)
+struct MeshHasData {
+    MeshSceneWhole s;
+    long long* count;
+    __device__ __forceinline__ bool operator()(int idx) const
+    {
+        if (mesh_entry_resolves(s, idx)) return true;
+        if (count) count[idx] = 0;
+        return false;
+    }
+};
+__device__ __forceinline__ MeshHasBlock mesh_has_block(const MeshScene& s, long long* count) { return MeshHasBlock{ s.v.hash, count }; }
+__device__ __forceinline__ MeshHasData mesh_has_block(const MeshSceneWhole& s, long long* count) { return MeshHasData{ s, count }; }
 struct MeshHasOutput {
     const long long* count;
     const long long* base;
@@ -59,17 +80,18 @@ struct MeshHasOutput {
     __device__ __forceinline__ bool operator()(int idx) const { return count[idx] > 0 && base[idx] < capacity; }
 };
 
-__global__ __launch_bounds__(TFM_WG) void k_mesh_count(MeshScene s, long long* __restrict__ count, long long* __restrict__ groupTot)
+template <class Scene>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_count(Scene s, long long* __restrict__ count, long long* __restrict__ groupTot)
 {
     __shared__ unsigned tile[TFM_TILE3];
-    __shared__ int nvoff[8];
+    __shared__ int nvoff[TFM_NVOFF(Scene, 8)];
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
     __shared__ int wsum[TFM_WG / 64];
     const int t = threadIdx.x;
     const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasBlock{ s.v.hash, count });      // (any order: each entry's count stands alone)
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, mesh_has_block(s, count));      // (any order: each entry's count stands alone)
         long long tot = 0;
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
@@ -154,11 +176,12 @@ struct MeshAttrWriter {
     }
 };
 
-__global__ __launch_bounds__(TFM_WG) void k_mesh_emit(MeshScene s, const long long* __restrict__ count, const long long* __restrict__ base,
+template <class Scene>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit(Scene s, const long long* __restrict__ count, const long long* __restrict__ base,
                                                       float* __restrict__ out, long long capacity, float voxelSize)
 {
     __shared__ unsigned tile[TFM_TILE3];
-    __shared__ int nvoff[8];
+    __shared__ int nvoff[TFM_NVOFF(Scene, 8)];
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
     __shared__ int wsum[TFM_WG / 64];
@@ -186,8 +209,8 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit(MeshScene s, const long lo
 // up to 19 neighbours, the 9 x 9 x 9 integer gradients formed once from it, the colour words of the same
 // 9 x 9 x 9 corners; then k_mesh_emit's classification and scan, and per triangle vertex two LDS gradient /
 // colour reads per end.
-template <bool NORMALS, bool COLOURS>
-__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const unsigned* __restrict__ rgb, const long long* __restrict__ count,
+template <bool NORMALS, bool COLOURS, class Scene>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(Scene s, const unsigned* __restrict__ rgb, const long long* __restrict__ count,
                                                            const long long* __restrict__ base, float* __restrict__ outTri,
                                                            float* __restrict__ outNrm, unsigned* __restrict__ outCol, long long capacity,
                                                            float voxelSize)
@@ -195,7 +218,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const un
     __shared__ unsigned tile[TFM_ATILE3];
     __shared__ int grad3[NORMALS ? 3 * TFM_TILE3 : 1];
     __shared__ unsigned ctile[COLOURS ? TFM_TILE3 : 1];
-    __shared__ int nvoff[27];
+    __shared__ int nvoff[TFM_NVOFF(Scene, 27)];
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
     __shared__ int wsum[TFM_WG / 64];
@@ -206,7 +229,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(MeshScene s, const un
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
             const TfHashEntry e = s.v.hash[ei];
-            mesh_stage_attr<NORMALS, COLOURS>(s, rgb, e, tile, ctile, nvoff);
+            mesh_stage_attr<NORMALS, COLOURS>(s, rgb, ei, e, tile, ctile, nvoff);
             if (NORMALS) mesh_grad_fill(tile, grad3);
             const TfmCube q = mesh_cube<TFM_ATILE, 1>(tile);
             const int mine = tfm_cube_count(q);
@@ -318,7 +341,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(MeshScene s, cons
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
             const TfHashEntry e = s.v.hash[ei];
-            mesh_stage_attr<NORMALS, COLOURS>(s, rgb, e, tile, ctile, nvoff);
+            mesh_stage_attr<NORMALS, COLOURS>(s, rgb, ei, e, tile, ctile, nvoff);
             if (t < TFM_EDGE_WORDS) {                // (vcount > 0: the entry is live and its block below n_blocks)
                 lm[t] = mask[(size_t)e.ptr * TFM_EDGE_WORDS + t];
                 lpre[t] = wpre[(size_t)e.ptr * TFM_EDGE_WORDS + t];
@@ -455,9 +478,13 @@ static hipError_t mesh_prefix(tf_ctx* c, const long long* count, const long long
     return hipGetLastError();
 }
 
+// Does this extraction read the GlobalCache?  Only a swapping context has one: on any other, every entry is in
+// the first or the last row of the resolution table and the whole reading IS the resident one (the same kernels).
+static inline bool mesh_reads_store(const tf_ctx* c, bool whole) { return whole && c->p.use_swapping && c->swapStore; }
+
 // count + prefix; the scratch (counts, bases + total, group totals behind the counts) is the
-// context's from the first call on
-static hipError_t tfk_mesh_count(tf_ctx* c)
+// context's from the first call on.  whole: the reading over both tiers (here and in the emit passes).
+static hipError_t tfk_mesh_count(tf_ctx* c, bool whole = false)
 {
     if (!c->meshCount) {
         const hipError_t e = tf_mem_hip(c->mem.alloc_group({
@@ -466,25 +493,38 @@ static hipError_t tfk_mesh_count(tf_ctx* c)
         if (e != hipSuccess) return e;
     }
     long long* groupTot = c->meshCount + c->n_total;
-    hipLaunchKernelGGL(k_mesh_count, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, groupTot);
+    if (mesh_reads_store(c, whole))
+        hipLaunchKernelGGL(k_mesh_count<MeshSceneWhole>, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene_whole(c), c->meshCount, groupTot);
+    else
+        hipLaunchKernelGGL(k_mesh_count<MeshScene>, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, groupTot);
     return mesh_prefix(c, c->meshCount, groupTot, c->meshBase);
 }
 
 // after tfk_mesh_count on the same stream
-static hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity)
+static hipError_t tfk_mesh_emit(tf_ctx* c, float* triangles, long long capacity, bool whole = false)
 {
-    hipLaunchKernelGGL(k_mesh_emit, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, c->meshBase, triangles, capacity,
-                       c->p.voxelSize);
+    if (mesh_reads_store(c, whole))
+        hipLaunchKernelGGL(k_mesh_emit<MeshSceneWhole>, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene_whole(c), c->meshCount, c->meshBase,
+                           triangles, capacity, c->p.voxelSize);
+    else
+        hipLaunchKernelGGL(k_mesh_emit<MeshScene>, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshCount, c->meshBase, triangles,
+                           capacity, c->p.voxelSize);
     return hipGetLastError();
 }
 
 // after tfk_mesh_count on the same stream: positions (may be nullptr), normals and / or colours (at
-// least one of the two; colours need the colour plane), all clipped at the same capacity
-static hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity)
+// least one of the two; colours need the colour plane), all clipped at the same capacity.  whole: normals
+// only (a swapping scene has no colour plane; the callers refuse the pair).
+static hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals, unsigned char* colours, long long capacity, bool whole = false)
 {
+    if (mesh_reads_store(c, whole)) {
+        hipLaunchKernelGGL((k_mesh_emit_attr<true, false, MeshSceneWhole>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene_whole(c), nullptr,
+                           c->meshCount, c->meshBase, triangles, normals, nullptr, capacity, c->p.voxelSize);
+        return hipGetLastError();
+    }
     mesh_dispatch_attr(normals != nullptr, colours != nullptr, [&](auto N, auto C) {
         if constexpr (N() || C())
-            hipLaunchKernelGGL((k_mesh_emit_attr<N(), C()>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount,
+            hipLaunchKernelGGL((k_mesh_emit_attr<N(), C(), MeshScene>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshCount,
                                c->meshBase, triangles, normals, reinterpret_cast<unsigned*>(colours), capacity, c->p.voxelSize);
     });
     return hipGetLastError();
@@ -538,29 +578,30 @@ static hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long 
 // ---- the entry points (additions: the reference has no mesher; DESIGN.md §Mesh extraction) -----------
 // The PLY writers (tf_mesh_write_ply*) are host code of their own in tf_mesh_ply.cpp.
 // count + prefix on the stream, then the total
-static tf_status mesh_count(tf_ctx* c, long long* n)
+static tf_status mesh_count(tf_ctx* c, long long* n, bool whole = false)
 {
-    TF_CHECK(tfk_mesh_count(c));
+    TF_CHECK(tfk_mesh_count(c, whole));
     TF_CHECK(hipMemcpyAsync(n, c->meshBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     return sync_checked(c);
 }
 
-// tf_mesh_extract and tf_mesh_extract_attr, after the flush
-static tf_status mesh_extract(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity, long long* n_triangles)
+// tf_mesh_extract, tf_mesh_extract_attr and tf_mesh_extract_whole (no colours), after the flush
+static tf_status mesh_extract(tf_ctx* c, float* dev_triangles, float* dev_normals, uint8_t* dev_colours, long long capacity, long long* n_triangles,
+                              bool whole = false)
 {
     const bool any = dev_triangles || dev_normals || dev_colours;
     if (!c || !n_triangles || capacity < 0 || (capacity > 0 && !any)) return TF_INVALID_ARG;
     if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
     long long n = 0;
-    tf_status s = mesh_count(c, &n);
+    tf_status s = mesh_count(c, &n, whole);
     if (s != TF_OK) return s;
     *n_triangles = n;
     if (capacity == 0 || !any || n == 0) return TF_OK;
     TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
     if (dev_normals || dev_colours) {
-        TF_CHECK(tfk_mesh_emit_attr(c, dev_triangles, dev_normals, dev_colours, capacity));
+        TF_CHECK(tfk_mesh_emit_attr(c, dev_triangles, dev_normals, dev_colours, capacity, whole));
     } else {
-        TF_CHECK(tfk_mesh_emit(c, dev_triangles, capacity));
+        TF_CHECK(tfk_mesh_emit(c, dev_triangles, capacity, whole));
     }
     return sync_checked(c);
 }
@@ -576,6 +617,12 @@ extern "C" tf_status tf_mesh_extract_attr(tf_ctx* c, float* dev_triangles, float
 {
     TF_FLUSH(c);
     return mesh_extract(c, dev_triangles, dev_normals, dev_colours, capacity, n_triangles);
+}
+
+extern "C" tf_status tf_mesh_extract_whole(tf_ctx* c, float* dev_triangles, float* dev_normals, long long capacity, long long* n_triangles)
+{
+    TF_FLUSH(c);
+    return mesh_extract(c, dev_triangles, dev_normals, nullptr, capacity, n_triangles, true);
 }
 
 // What the tf_mesh_save_ply* share: `bytes` of output, written by emit(dev) on the context stream into a
@@ -607,21 +654,23 @@ static const T* mesh_column(const char* host, size_t off, bool want)
     return !want ? nullptr : host ? (const T*)(host + off) : (const T*)&none;
 }
 
-// tf_mesh_save_ply (attrs 0) and tf_mesh_save_ply_attr, after the flush
+// tf_mesh_save_ply (attrs 0) and tf_mesh_save_ply_attr, after the flush.  TF_MESH_WHOLE: the whole map through
+// the same writer -- one device buffer, one host buffer, one weld, so the caller's memory bounds the mesh.
 static tf_status mesh_save_ply(tf_ctx* c, const char* path, int attrs)
 {
-    if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS))) return TF_INVALID_ARG;
-    if ((attrs & TF_MESH_COLOURS) && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    if (!c || !path || (attrs & ~(TF_MESH_NORMALS | TF_MESH_COLOURS | TF_MESH_WHOLE))) return TF_INVALID_ARG;
+    if ((attrs & TF_MESH_COLOURS) && (!c->p.voxel_rgb || (attrs & TF_MESH_WHOLE))) return TF_INVALID_ARG;
+    const bool whole = attrs & TF_MESH_WHOLE;
     long long n = 0;
-    tf_status s = mesh_count(c, &n);
+    tf_status s = mesh_count(c, &n, whole);
     if (s != TF_OK) return s;
     const bool nrm = attrs & TF_MESH_NORMALS, col = attrs & TF_MESH_COLOURS;
     // one allocation each side: positions, then normals, then colours
     const size_t bt = sizeof(float) * 9 * (size_t)n, bn = nrm ? bt : 0, bc = col ? 12 * (size_t)n : 0;
     char* host = nullptr;
     s = mesh_download(c, bt + bn + bc, &host, [&](char* dev) {
-        if (!nrm && !col) return tfk_mesh_emit(c, (float*)dev, n);
-        return tfk_mesh_emit_attr(c, (float*)dev, nrm ? (float*)(dev + bt) : nullptr, col ? (unsigned char*)(dev + bt + bn) : nullptr, n);
+        if (!nrm && !col) return tfk_mesh_emit(c, (float*)dev, n, whole);
+        return tfk_mesh_emit_attr(c, (float*)dev, nrm ? (float*)(dev + bt) : nullptr, col ? (unsigned char*)(dev + bt + bn) : nullptr, n, whole);
     });
     if (s == TF_OK)
         s = tf_mesh_write_ply_attr(path, (const float*)host, mesh_column<float>(host, bt, nrm), mesh_column<uint8_t>(host, bt + bn, col), n);

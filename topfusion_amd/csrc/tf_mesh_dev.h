@@ -2,13 +2,16 @@
 // once: the scene view, the live list of a 512-entry group, the workgroup scan, the block look-up, the
 // LDS tiles of a hash entry's corner voxels with their gradient fill and cube read, the stores and the
 // <NORMALS, COLOURS> dispatch.  Every piece that holds a barrier says so, and says what its caller may
-// assume before and after.
+// assume before and after.  The pieces that look at a block take the reading of the scene -- resident, or
+// whole: both tiers of a swapping scene -- as the scene's type; the whole reading's resolution of a block
+// (mesh_resolve_entry, mesh_block_resolve, mesh_voxel_whole) stands once, beside mesh_block_look.
 #pragma once
 
 #include <type_traits>
 
 #include "tf_internal.h"
 #include "tf_mesh.h"
+#include "tf_swap_combine.h"
 
 #define TFM_WG 512               // threads per workgroup = voxels per block = entries per group
 #define TFM_TILE 9
@@ -16,9 +19,30 @@
 #define TFM_GRID 2048            // workgroups of the count / emit passes (groups are taken round robin)
 #define TFM_SCAN_GROUPS 4        // groups (of TFM_WG entries) per k_mesh_prefix workgroup
 
+// The two readings of the scene (DESIGN.md §Mesh extraction, the whole map).  Every piece below that looks
+// at a block takes the scene's type as a template parameter: MeshScene is the resident reading (blocks with
+// ptr >= 0, as they lie in the VBA), MeshSceneWhole adds the GlobalCache (blocks resolved over both tiers).
 struct MeshScene {
+    static constexpr bool whole = false;
     SceneView v;                 // v.vba: the guard block of Voxel_s() (sdf 32767, w 0), then the VBA -- a missing block reads it
     int n_total;
+};
+struct MeshSceneWhole {
+    static constexpr bool whole = true;
+    SceneView v;
+    int n_total;
+    int maxW;                    // CombineVoxelInformation's clamp (tf_params::maxW)
+    const unsigned char* state;  // HashSwapState::state per entry
+    const unsigned char* flags;  // hasStoredData per entry
+    const TfVoxel* store;        // storedVoxelBlocks: 512 voxels per entry
+};
+
+// A resolved block: where its voxels lie.  act = the VBA voxel offset (ptr * 512) or TF_VOFF_NONE, sto = the
+// GlobalCache voxel offset (entry * 512; tf_create bounds the table so it fits an int) or TFM_STO_NONE.
+// Both: the voxel is CombineVoxelInformation(stored, active); neither: the block is missing.
+#define TFM_STO_NONE (-1)
+struct MeshBlk {
+    int act, sto;
 };
 
 // The entries of group g that pred(idx) accepts, into live[] (any order); returns their number.  pred
@@ -76,6 +100,71 @@ __device__ __forceinline__ int2 mesh_block_look(const MeshScene& s, int bx, int 
     return blk_walk(s.v, bx, by, bz);
 }
 
+// ---- the whole reading's resolution (DESIGN.md §Mesh extraction, the whole map), written once ----
+// Entry ei with the block pointer ptr, by the table: a block and no store, or a store left behind by a
+// finished merge (state 2: k_swap_in never clears the flag) -> the active block; a block and a store not
+// yet merged -> both; swapped out with a store -> the store; anything else is missing.
+__device__ __forceinline__ MeshBlk mesh_resolve_entry(const MeshSceneWhole& s, int ei, int ptr)
+{
+    const bool stored = s.flags[ei] != 0;
+    MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE };
+    if (ptr >= 0) {
+        d.act = ptr * TF_BLK3;
+        if (stored && s.state[ei] != 2) d.sto = ei * TF_BLK3;
+    } else if (ptr == -1 && stored) {
+        d.sto = ei * TF_BLK3;
+    }
+    return d;
+}
+
+// does entry idx hold voxel data in either tier
+__device__ __forceinline__ bool mesh_entry_resolves(const MeshSceneWhole& s, int idx)
+{
+    const int ptr = s.v.hash[idx].ptr;
+    return ptr >= 0 || (ptr == -1 && s.flags[idx] != 0);
+}
+
+// blk_walk over both tiers: the first entry at the block that resolves (ptr >= 0, or swapped out -- ptr -1 --
+// with stored data), or -1
+__device__ __forceinline__ int mesh_walk_whole(const MeshSceneWhole& s, int bx, int by, int bz)
+{
+    int hi = tf_hash_index(bx, by, bz, s.v.mask);
+    while (true) {
+        const TfHashEntry e = s.v.hash[hi];
+        if (e.x == (short)bx && e.y == (short)by && e.z == (short)bz && (e.ptr >= 0 || (e.ptr == -1 && s.flags[hi] != 0))) return hi;
+        if (e.offset < 1) return -1;
+        hi = s.v.n_buckets + e.offset - 1;
+    }
+}
+
+// mesh_block_look for the whole reading.  The block grid first: a hit is a block in the VBA, whose entry's
+// flag and state say whether a merge is pending.  A miss inside the grid is not the end -- swap-out clears
+// the cell, so a stored block is never in the grid -- and takes the hash walk, as a block outside the grid does.
+__device__ __forceinline__ MeshBlk mesh_block_resolve(const MeshSceneWhole& s, int bx, int by, int bz)
+{
+    const MeshBlk none = { TF_VOFF_NONE, TFM_STO_NONE };
+    if (tf_grid_in(bx, by, bz)) {
+        const int2 b = s.v.grid[tf_grid_cell(bx, by, bz)];
+        if (b.x >= 0) return mesh_resolve_entry(s, b.x, b.y >> 9);
+    } else if (bx > 32767 || by > 32767 || bz > 32767 || bx < -32768 || by < -32768 || bz < -32768) {
+        return none;
+    }
+    const int hi = mesh_walk_whole(s, bx, by, bz);
+    return hi < 0 ? none : mesh_resolve_entry(s, hi, s.v.hash[hi].ptr);
+}
+
+// one voxel of a resolved block as the tiles hold it (sdf | w << 16): the active voxel (the guard's
+// (32767, 0) where there is none), the stored one as it is, or CombineVoxelInformation of the two
+__device__ __forceinline__ unsigned mesh_voxel_whole(const MeshSceneWhole& s, int act, int sto, int lin)
+{
+    unsigned a = reinterpret_cast<const unsigned*>(s.v.vba)[TF_BLK3 + act + lin] & 0xffffffu;
+    if (sto >= 0) {                  // (per block: the lanes of a tile row share it but for the row's last voxel)
+        const unsigned st = reinterpret_cast<const unsigned*>(s.store)[sto + lin] & 0xffffffu;
+        a = act == TF_VOFF_NONE ? st : sw_combine(st, a, s.maxW);
+    }
+    return a;
+}
+
 struct MeshNoHook {
     __device__ __forceinline__ void operator()(int, int2) const {}
 };
@@ -86,23 +175,37 @@ struct MeshNoHook {
 // caller's; between it and the second every thread calls hook(t, b) -- for t < 8, b is block t's
 // (entry, voff) as found, so the caller can keep what belongs to the entry, and any thread may fill
 // LDS of the caller's there; the trailing one publishes the tile, nvoff and what the hook wrote.
-template <class Hook = MeshNoHook>
-__device__ __forceinline__ void mesh_stage(const MeshScene& s, int ei, const TfHashEntry& e, unsigned* tile, int* nvoff, Hook hook = Hook())
+// The whole reading: nvoff holds TFM_NVOFF(Scene, 8) ints, the blocks' store offsets behind their active
+// ones, each voxel comes from where its block's descriptor says, and the hook sees (-1, active offset).
+#define TFM_NVOFF(Scene, n) ((Scene::whole ? 2 : 1) * (n))
+template <class Scene, class Hook = MeshNoHook>
+__device__ __forceinline__ void mesh_stage(const Scene& s, int ei, const TfHashEntry& e, unsigned* tile, int* nvoff, Hook hook = Hook())
 {
     const int t = threadIdx.x;
     __syncthreads();
     int2 b = make_int2(-1, TF_VOFF_NONE);
     if (t < 8) {
-        b = t == 0 ? make_int2(ei, e.ptr * TF_BLK3) : mesh_block_look(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
+        if constexpr (Scene::whole) {
+            const MeshBlk d = t == 0 ? mesh_resolve_entry(s, ei, e.ptr) : mesh_block_resolve(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
+            b.y = d.act;
+            nvoff[8 + t] = d.sto;
+        } else {
+            b = t == 0 ? make_int2(ei, e.ptr * TF_BLK3) : mesh_block_look(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
+        }
         nvoff[t] = b.y;
     }
     hook(t, b);
     __syncthreads();
     for (int i = t; i < TFM_TILE3; i += TFM_WG) {
         const int z = i / (TFM_TILE * TFM_TILE), r = i - z * (TFM_TILE * TFM_TILE), y = r / TFM_TILE, x = r - y * TFM_TILE;
-        const int voff = nvoff[(x >> 3) | (y >> 3) << 1 | (z >> 3) << 2];
-        const TfVoxel v = s.v.vba[TF_BLK3 + voff + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6)];
-        tile[i] = (unsigned)(unsigned short)v.sdf | (unsigned)v.w << 16;
+        const int bi = (x >> 3) | (y >> 3) << 1 | (z >> 3) << 2;
+        const int voff = nvoff[bi];
+        if constexpr (Scene::whole) {
+            tile[i] = mesh_voxel_whole(s, voff, nvoff[8 + bi], (x & 7) + ((y & 7) << 3) + ((z & 7) << 6));
+        } else {
+            const TfVoxel v = s.v.vba[TF_BLK3 + voff + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6)];
+            tile[i] = (unsigned)(unsigned short)v.sdf | (unsigned)v.w << 16;
+        }
     }
     __syncthreads();
 }
@@ -135,18 +238,29 @@ __device__ __forceinline__ TfmCube mesh_cube(const unsigned* tile)
 // (ox + 1) + 3 (oy + 1) + 9 (oz + 1), those with more than one -1 (without NORMALS: any -1) unused.
 // Three barriers, as mesh_stage's: the leading one ends the previous entry's reads of tile / gradients /
 // ctile / nvoff, the trailing one publishes the tiles.
-template <bool NORMALS, bool COLOURS>
-__device__ __forceinline__ void mesh_stage_attr(const MeshScene& s, const unsigned* __restrict__ rgb, const TfHashEntry& e, unsigned* tile,
+// The whole reading (never with COLOURS: a swapping scene has no colour plane): ei is the entry's index,
+// nvoff holds TFM_NVOFF(Scene, 27) ints, the store offsets behind the active ones, as mesh_stage's.
+template <bool NORMALS, bool COLOURS, class Scene>
+__device__ __forceinline__ void mesh_stage_attr(const Scene& s, const unsigned* __restrict__ rgb, int ei, const TfHashEntry& e, unsigned* tile,
                                                 unsigned* ctile, int* nvoff)
 {
+    static_assert(!(Scene::whole && COLOURS), "the whole reading has no colours");
     const int t = threadIdx.x;
     __syncthreads();
     if (t < 27) {
         const int ox = t % 3 - 1, oy = t / 3 % 3 - 1, oz = t / 9 - 1;
         const int down = (ox < 0) + (oy < 0) + (oz < 0);
         int voff = TF_VOFF_NONE;
-        if (t == 13) voff = e.ptr * TF_BLK3;
-        else if (down <= (NORMALS ? 1 : 0)) voff = mesh_block_look(s, e.x + ox, e.y + oy, e.z + oz).y;
+        if constexpr (Scene::whole) {
+            MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE };
+            if (t == 13) d = mesh_resolve_entry(s, ei, e.ptr);
+            else if (down <= (NORMALS ? 1 : 0)) d = mesh_block_resolve(s, e.x + ox, e.y + oy, e.z + oz);
+            voff = d.act;
+            nvoff[27 + t] = d.sto;
+        } else {
+            if (t == 13) voff = e.ptr * TF_BLK3;
+            else if (down <= (NORMALS ? 1 : 0)) voff = mesh_block_look(s, e.x + ox, e.y + oy, e.z + oz).y;
+        }
         nvoff[t] = voff;
     }
     __syncthreads();
@@ -156,11 +270,16 @@ __device__ __forceinline__ void mesh_stage_attr(const MeshScene& s, const unsign
         const int rim = ((unsigned)x > 8u) + ((unsigned)y > 8u) + ((unsigned)z > 8u);
         unsigned packed = 0u;
         if (rim <= (NORMALS ? 1 : 0)) {
-            const int voff = nvoff[((x >> 3) + 1) + 3 * ((y >> 3) + 1) + 9 * ((z >> 3) + 1)];
-            const int at = TF_BLK3 + voff + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6);
-            const TfVoxel v = s.v.vba[at];
-            packed = (unsigned)(unsigned short)v.sdf | (unsigned)v.w << 16;
-            if (COLOURS && rim == 0) ctile[x + TFM_TILE * y + TFM_TILE * TFM_TILE * z] = rgb[at];
+            const int bi = ((x >> 3) + 1) + 3 * ((y >> 3) + 1) + 9 * ((z >> 3) + 1);
+            const int voff = nvoff[bi];
+            if constexpr (Scene::whole) {
+                packed = mesh_voxel_whole(s, voff, nvoff[27 + bi], (x & 7) + ((y & 7) << 3) + ((z & 7) << 6));
+            } else {
+                const int at = TF_BLK3 + voff + (x & 7) + ((y & 7) << 3) + ((z & 7) << 6);
+                const TfVoxel v = s.v.vba[at];
+                packed = (unsigned)(unsigned short)v.sdf | (unsigned)v.w << 16;
+                if (COLOURS && rim == 0) ctile[x + TFM_TILE * y + TFM_TILE * TFM_TILE * z] = rgb[at];
+            }
         }
         tile[i] = packed;
     }
@@ -225,6 +344,16 @@ static inline MeshScene mesh_scene(const tf_ctx* c)
     MeshScene s;
     s.v.hash = c->hash; s.v.vba = c->vba_guard; s.v.grid = c->bgrid;
     s.v.mask = (unsigned)c->p.n_buckets - 1u; s.v.n_buckets = c->p.n_buckets; s.n_total = c->n_total;
+    return s;
+}
+
+// ... of a swapping context (the others have no GlobalCache: their whole reading is the resident one)
+static inline MeshSceneWhole mesh_scene_whole(const tf_ctx* c)
+{
+    MeshSceneWhole s;
+    s.v = mesh_scene(c).v;
+    s.n_total = c->n_total; s.maxW = c->p.maxW;
+    s.state = c->swapState; s.flags = c->swapFlags; s.store = c->swapStore;
     return s;
 }
 

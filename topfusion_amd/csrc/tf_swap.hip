@@ -26,6 +26,7 @@
 // swap out.  The reallocation of listed swapped-out entries is the same count + prefix pattern
 // over the visible list (ascending, so its serial free-list order is a prefix sum).
 #include "tf_internal.h"
+#include "tf_swap_combine.h"
 
 #define SW_CHUNK 4096          // entries per workgroup (256 threads x 16)
 
@@ -173,21 +174,7 @@ k_swap_count_in(TfDevState* __restrict__ st, const unsigned char* __restrict__ s
     if (blockIdx.x == 0 && threadIdx.x == 0) st->swap_merged = 0;   // (k_swap_in counts this pass's merges)
 }
 
-// CombineVoxelInformation (depth part): src = stored, dst = active; canonical arithmetic
-__device__ __forceinline__ unsigned sw_combine(unsigned src, unsigned dst, int maxW)
-{
-    const int oldW = (src >> 16) & 0xff, newW0 = (dst >> 16) & 0xff;
-    if (oldW == 0) return dst;
-    const float oldF = tf_short_to_float((short)(src & 0xffff)), newF0 = tf_short_to_float((short)(dst & 0xffff));
-    float newF = (float)oldW * oldF + (float)newW0 * newF0;
-    int newW = oldW + newW0;
-    newF = newF / (float)newW;
-    newW = newW < maxW ? newW : maxW;
-    const short sdf = (short)(newF * 32767.0f);
-    return (unsigned)(unsigned short)sdf | ((unsigned)(newW & 0xff) << 16) | (dst & 0xff000000u);
-}
-
-// IntegrateGlobalIntoLocal for this chunk's candidates of rank < T, then the chunk's swap-out
+// IntegrateGlobalIntoLocal (the merge is sw_combine, tf_swap_combine.h) for this chunk's candidates of rank < T, then the chunk's swap-out
 // candidates (its states are final once its own swap-ins are done: no other workgroup touches
 // this chunk's entries)
 __global__ void __launch_bounds__(256)

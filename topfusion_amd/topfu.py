@@ -370,17 +370,23 @@ class TopFu:
         return t
 
     # -- mesh extraction (additions: tf_mesh_*; the reference has no mesher) ------------------------
-    def mesh_count(self):
+    # whole=True: the reading over both tiers of a swapping scene (tf_mesh_extract_whole, TF_MESH_WHOLE) -- every
+    # entry with voxel data in the VBA or the GlobalCache, stored blocks read where they lie, pending merges
+    # combined on the fly; without stored data it is the resident mesh byte for byte.  No colours, not indexed.
+    def mesh_count(self, whole=False):
         """Triangles the scene's mesh has (the count pass alone)."""
         n = ctypes.c_longlong()
-        L.check(L.load().tf_mesh_extract(self._h, None, 0, ctypes.byref(n)), "tf_mesh_extract")
+        if whole:
+            L.check(L.load().tf_mesh_extract_whole(self._h, None, None, 0, ctypes.byref(n)), "tf_mesh_extract_whole")
+        else:
+            L.check(L.load().tf_mesh_extract(self._h, None, 0, ctypes.byref(n)), "tf_mesh_extract")
         return n.value
 
-    def mesh(self):
+    def mesh(self, whole=False):
         """The scene's surface as (n, 3, 3) float32 triangles -- marching tetrahedra over the voxel
         block hash, in the fixed order of tf_mesh_extract, right-hand normals towards free space.
         Counts, allocates a device buffer through the library's HIP runtime, extracts, downloads."""
-        n = self.mesh_count()
+        n = self.mesh_count(whole)
         out = np.empty((n, 3, 3), np.float32)
         if n == 0:
             return out
@@ -390,7 +396,10 @@ class TopFu:
             raise L.TfError(L.TF_OOM, "hipMalloc (mesh)")
         try:
             m = ctypes.c_longlong()
-            L.check(L.load().tf_mesh_extract(self._h, dev, n, ctypes.byref(m)), "tf_mesh_extract")
+            if whole:
+                L.check(L.load().tf_mesh_extract_whole(self._h, dev, None, n, ctypes.byref(m)), "tf_mesh_extract_whole")
+            else:
+                L.check(L.load().tf_mesh_extract(self._h, dev, n, ctypes.byref(m)), "tf_mesh_extract")
             assert m.value == n, (m.value, n)
             if hip.hipMemcpy(_ptr(out), dev, ctypes.c_size_t(out.nbytes), 2) != 0:      # hipMemcpyDeviceToHost
                 raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (mesh)")
@@ -398,12 +407,14 @@ class TopFu:
             hip.hipFree(dev)
         return out
 
-    def mesh_attr(self, normals=True, colours=False):
+    def mesh_attr(self, normals=True, colours=False, whole=False):
         """mesh() with per-vertex attributes (tf_mesh_extract_attr): (triangles (n, 3, 3) float32,
         normals (n, 3, 3) float32 or None, colours (n, 3, 4) uint8 RGBA or None), the same triangles
         in the same order.  Normals are the normalised TSDF gradient (towards free space), colours
-        come from the colour plane (voxel_rgb contexts only)."""
-        n = self.mesh_count()
+        come from the colour plane (voxel_rgb contexts only; never with whole=True)."""
+        if whole and colours:
+            raise L.TfError(L.TF_INVALID_ARG, "mesh_attr (whole with colours)")
+        n = self.mesh_count(whole)
         outs = [np.empty((n, 3, 3), np.float32), np.empty((n, 3, 3), np.float32) if normals else None,
                 np.empty((n, 3, 4), np.uint8) if colours else None]
         if n == 0 and not (colours and not self.params_.voxel_rgb):     # (that one is the library's TF_INVALID_ARG)
@@ -417,7 +428,10 @@ class TopFu:
                     raise L.TfError(L.TF_OOM, "hipMalloc (mesh)")
                 devs.append(d)
             m = ctypes.c_longlong()
-            L.check(L.load().tf_mesh_extract_attr(self._h, devs[0], devs[1], devs[2], n, ctypes.byref(m)), "tf_mesh_extract_attr")
+            if whole:
+                L.check(L.load().tf_mesh_extract_whole(self._h, devs[0], devs[1], n, ctypes.byref(m)), "tf_mesh_extract_whole")
+            else:
+                L.check(L.load().tf_mesh_extract_attr(self._h, devs[0], devs[1], devs[2], n, ctypes.byref(m)), "tf_mesh_extract_attr")
             assert m.value == n, (m.value, n)
             for o, d in zip(outs, devs):
                 if o is not None and n and hip.hipMemcpy(_ptr(o), d, ctypes.c_size_t(o.nbytes), 2) != 0:   # hipMemcpyDeviceToHost
@@ -468,15 +482,16 @@ class TopFu:
                     hip.hipFree(d)
         return outs[0], outs[3], outs[1], outs[2]
 
-    def save_mesh(self, path, normals=False, colours=False, indexed=False):
+    def save_mesh(self, path, normals=False, colours=False, indexed=False, whole=False):
         """The mesh as a binary PLY with welded vertices (tf_mesh_save_ply); with normals / colours,
         nx ny nz / red green blue alpha per vertex (tf_mesh_save_ply_attr).  indexed: the vertex table of
-        mesh_indexed() as it is, no host weld (tf_mesh_save_ply_indexed)."""
-        attrs = (L.TF_MESH_NORMALS if normals else 0) | (L.TF_MESH_COLOURS if colours else 0)
+        mesh_indexed() as it is, no host weld (tf_mesh_save_ply_indexed).  whole: the whole map's mesh through
+        the same writer (one download, one weld: the caller's memory bounds it); not with indexed or colours."""
+        attrs = (L.TF_MESH_NORMALS if normals else 0) | (L.TF_MESH_COLOURS if colours else 0) | (L.TF_MESH_WHOLE if whole else 0)
         if indexed:
             L.check(L.load().tf_mesh_save_ply_indexed(self._h, str(path).encode(), attrs), "tf_mesh_save_ply_indexed")
             return
-        if not normals and not colours:
+        if not normals and not colours and not whole:
             L.check(L.load().tf_mesh_save_ply(self._h, str(path).encode()), "tf_mesh_save_ply")
             return
         L.check(L.load().tf_mesh_save_ply_attr(self._h, str(path).encode(), attrs), "tf_mesh_save_ply_attr")
