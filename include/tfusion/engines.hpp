@@ -187,6 +187,15 @@ namespace tfusion
             else tf_engine_check(tf_mesh_save_ply_attr(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_attr");
         }
 
+        // Map checkpoints (additions: tf_map_save / tf_map_load).  saveMap writes the state the scene resumes
+        // from, sized by what is live: of a swapping scene both tiers -- the hash, the active blocks, the
+        // GlobalCache's swap states, stored flags and stored blocks, the lists and counters (version 2 of the
+        // checkpoint file); of a scene without swapping the scene checkpoint (version 1).  loadMap replaces this
+        // scene's state by the file's: a scene with the file's capacities, image size, scene parameters and
+        // useSwapping is from then on the one that saved, bit for bit, through any further engine calls.
+        void saveMap(const std::string& path) { tf_engine_check(tf_map_save(ctx_, path.c_str()), "tf_map_save"); }
+        void loadMap(const std::string& path) { tf_engine_check(tf_map_load(ctx_, path.c_str()), "tf_map_load"); }
+
     private:
         tf_ctx* ctx_ = nullptr;
         Intr intr_;

@@ -345,6 +345,26 @@ namespace tfusion
             return info;
         }
 
+        // Map checkpoints (additions: tf_map_save / tf_map_load / tf_map_file_info): saveScene's file on this
+        // TopFu (it runs without swapping, so version 1, byte for byte); loadMap takes what saveMap wrote.  A
+        // swapping caller holds a Scene (engines.hpp: Scene::saveMap / loadMap, the version-2 file).
+        void saveMap(const std::string& path) { check(tf_map_save(ctx_, path.c_str()), "tf_map_save"); }
+        void loadMap(const std::string& path)
+        {
+            check(tf_map_load(ctx_, path.c_str()), "tf_map_load");
+            float rt[12];
+            check(tf_get_pose(ctx_, rt), "tf_get_pose");
+            frame_counter_ = stats().frame_counter;
+            poses_.clear();
+            poses_.push_back(affine_from_rt(rt));
+        }
+        static struct tf_map_file_info mapFileInfo(const std::string& path)
+        {
+            struct tf_map_file_info info;
+            check(tf_map_file_info(path.c_str(), &info), "tf_map_file_info");
+            return info;
+        }
+
         tf_ctx* handle() { return ctx_; }
         hipStream_t stream() const { return (hipStream_t)tf_get_stream(ctx_); }
 

@@ -548,8 +548,8 @@ tf_status tf_mesh_save_ply_indexed(tf_ctx* ctx, const char* path, int attrs);
  * from ResetScene's, their voxel (and colour) blocks, visType where non-zero, visibleIds[0, noVisibleEntries),
  * the live parts of the two free lists, the counters, frame_counter, the pose and the previous points /
  * normals pyramid.  A context that loads a checkpoint is indistinguishable, bit for bit, from the one that
- * saved it, now and after any further frames.  Contexts with use_swapping are refused (TF_INVALID_ARG): the
- * GlobalCache has its own tf_swap_save / tf_swap_load, and a file that combines the two is not built. */
+ * saved it, now and after any further frames.  Contexts with use_swapping are refused (TF_INVALID_ARG) by
+ * these two calls: their checkpoint, GlobalCache included, is tf_map_save / tf_map_load's (below). */
 /* addition (no reference counterpart): writes the checkpoint of the current state to path.  Synchronous, the
  * scene is only read; two saves of one state are byte-identical, and a save straight after tf_scene_load of
  * file F is byte-identical to F.  TF_INVALID_ARG: NULL arguments, use_swapping, a path that cannot be
@@ -585,6 +585,41 @@ tf_status tf_scene_file_info(const char* path, struct tf_scene_file_info* info);
  * load: records -> hash, visType, block grid), ms[1] the block kernels (gather / scatter, summed over the
  * chunks).  ms[5] is not a time: the bytes the block kernels read + wrote.  ms[7] is 0. */
 tf_status tf_scene_ckpt_times(tf_ctx* ctx, double ms[8]);
+
+/* ---- map checkpoints (additions; DESIGN.md §5 Map checkpoints) ------------------------------------------
+ * The checkpoint of a context with or without use_swapping.  A swapping context's state is the scene
+ * checkpoint's state plus the GlobalCache: swapState and hasStoredData per entry and the stored block of
+ * every entry whose flag is 1 (a stored block whose flag is 0 is read by nobody and is not state).  It is
+ * written as version 2 of the checkpoint file: the records carry the two bytes, and the stored blocks follow
+ * the active ones as a second payload in record order.  A swapping context that loads a map checkpoint is
+ * indistinguishable, bit for bit, from the one that saved it, now and after any further frames or engine
+ * calls.  Not stored: the last call's tf_swap_counts (zero after a load) and the totals. */
+/* addition (no reference counterpart): on a context without use_swapping tf_scene_save's file, byte for byte
+ * (version 1); on a swapping context the version-2 file.  tf_scene_save's guarantees: synchronous, the scene
+ * and the cache are only read; two saves of one state are byte-identical, a save straight after tf_map_load
+ * of file F is byte-identical to F; a state that tf_map_load would refuse (also: a swap state > 2, a stored
+ * flag > 1) is TF_INVALID_ARG with no file left; every block travels through the same bounded staging buffer
+ * (TFUSION_CKPT_CHUNK_BLOCKS). */
+tf_status tf_map_save(tf_ctx* ctx, const char* path);
+/* addition (no reference counterpart): a version-1 file into a context without use_swapping (exactly
+ * tf_scene_load), a version-2 file into a swapping context: the file's use_swapping must equal the context's,
+ * the other agreement rules are tf_scene_load's (swap_transfer_blocks stays the context's own, as the tracker
+ * parameters do).  The whole file is validated on the host before the context is touched: TF_INVALID_ARG
+ * leaves it exactly as it was, the three GlobalCache buffers included.  Stored blocks of entries the file does
+ * not flag are left as they are (no clear of the store); states and flags are the file's over the whole table. */
+tf_status tf_map_load(tf_ctx* ctx, const char* path);
+/* what a map checkpoint file holds, from its header: version 1 or 2; n_cache_blocks is 0 for version 1 */
+struct tf_map_file_info {
+    struct tf_scene_file_info scene;
+    int version;
+    long long n_cache_blocks;
+};
+/* addition (no reference counterpart): host only, no context, no GPU call -- the header of a version-1 or
+ * version-2 file, checked against its checksum and the file's length.  (tf_scene_file_info and tf_scene_load
+ * refuse a version-2 file, as any unknown version.) */
+tf_status tf_map_file_info(const char* path, struct tf_map_file_info* info);
+/* tf_scene_ckpt_times reports the last tf_map_save / tf_map_load too: the cache blocks' kernel time is part
+ * of ms[1], their bytes of ms[5]. */
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,11 @@ class TfSceneFileInfo(ctypes.Structure):
                 ("n_blocks_stored", ctypes.c_longlong), ("file_bytes", ctypes.c_longlong), ("pose", ctypes.c_float * 12)]
 
 
+class TfMapFileInfo(ctypes.Structure):
+    """struct tf_map_file_info: a map checkpoint's header (version 1 or 2)."""
+    _fields_ = [("scene", TfSceneFileInfo), ("version", ctypes.c_int), ("n_cache_blocks", ctypes.c_longlong)]
+
+
 class TfTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_longlong) for n in ("frames", "frames_tracked", "resets", "visible_sum", "tiles_sum",
                                                  "swapped_in", "swapped_out", "integrate_lanes_read",
@@ -198,6 +203,9 @@ def load():
         "tf_scene_load": ([P, ctypes.c_char_p], I),
         "tf_scene_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfSceneFileInfo)], I),
         "tf_scene_ckpt_times": ([P, P], I),
+        "tf_map_save": ([P, ctypes.c_char_p], I),
+        "tf_map_load": ([P, ctypes.c_char_p], I),
+        "tf_map_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfMapFileInfo)], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():
@@ -269,16 +277,32 @@ def default_params(**kw):
     return p
 
 
-def scene_file_info(path):
-    """The header of a scene checkpoint (tf_scene_file_info; host only, no context): a dict with the
-    saving context's `params` (TfParams), pose_algebra, frame_counter, the three counters, n_records,
-    n_blocks_stored, file_bytes and the 3 x 4 `pose`."""
-    info = TfSceneFileInfo()
-    check(load().tf_scene_file_info(str(path).encode(), ctypes.byref(info)), "tf_scene_file_info")
+def _scene_info_dict(info):
     out = {n: getattr(info, n) for n in ("pose_algebra", "frame_counter", "lastFreeBlockId", "lastFreeExcessListId",
                                          "noVisibleEntries", "n_records", "n_blocks_stored", "file_bytes")}
     p = TfParams()
     ctypes.memmove(ctypes.byref(p), ctypes.byref(info.params), ctypes.sizeof(TfParams))
     out["params"] = p
     out["pose"] = np.array(list(info.pose), np.float32).reshape(3, 4)
+    return out
+
+
+def scene_file_info(path):
+    """The header of a scene checkpoint (tf_scene_file_info; host only, no context): a dict with the
+    saving context's `params` (TfParams), pose_algebra, frame_counter, the three counters, n_records,
+    n_blocks_stored, file_bytes and the 3 x 4 `pose`."""
+    info = TfSceneFileInfo()
+    check(load().tf_scene_file_info(str(path).encode(), ctypes.byref(info)), "tf_scene_file_info")
+    return _scene_info_dict(info)
+
+
+def map_file_info(path):
+    """The header of a map checkpoint of either version (tf_map_file_info; host only, no context):
+    scene_file_info's dict plus `version` (1, or 2: a swapping context's) and `n_cache_blocks` (the
+    GlobalCache blocks the file holds; 0 in version 1)."""
+    info = TfMapFileInfo()
+    check(load().tf_map_file_info(str(path).encode(), ctypes.byref(info)), "tf_map_file_info")
+    out = _scene_info_dict(info.scene)
+    out["version"] = info.version
+    out["n_cache_blocks"] = info.n_cache_blocks
     return out

@@ -17,6 +17,10 @@
 // The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of its
 // own over int2 group counts (8 B per 256 entries) rather than k_mesh_prefix over 64-bit per-entry
 // counts, and shares no scratch with a mesh extraction.  No workgroup waits on another inside a grid.
+//
+// Map checkpoints (tf_map_save / tf_map_load, DESIGN.md §5 Map checkpoints) are the same calls; on a swapping
+// context they write version 2 of the file with the k_map_* forms further down: the GlobalCache's swap state
+// and stored flag in every record, the stored blocks gathered from store + index * 512 as a second payload.
 #include "tf_host.h"
 #include "tf_scene_file.h"
 
@@ -149,6 +153,137 @@ __global__ __launch_bounds__(CK_WG) void k_ckpt_apply(const ck_u2* __restrict__ 
     }
 }
 
+// ---- the swapping forms (map checkpoints, version 2 of the file): the same passes with the GlobalCache's two
+// bytes per entry in the record predicate and in the record, a third tally (entries with hasStoredData) from
+// the same ballots, and a second list -- the entry indices of flagged records, in record order -- that the
+// store's gather walks.  The version-1 kernels above are launched as they were.
+// cache: swapState | hasStoredData << 8; sto: the entry's stored block is state
+__device__ __forceinline__ void ck_classify_map(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
+                                                const unsigned char* __restrict__ swapState, const unsigned char* __restrict__ swapFlags,
+                                                int idx, int n_total, ck_u4& e, unsigned& vis, unsigned& cache, bool& rec, bool& blk,
+                                                bool& sto)
+{
+    ck_classify(hash, visType, idx, n_total, e, vis, rec, blk);
+    cache = 0;
+    if (idx < n_total) cache = (unsigned)swapState[idx] | (unsigned)swapFlags[idx] << 8;
+    rec = rec || cache != 0u;                              // (blk implies rec already: ptr >= 0 is not ResetScene's)
+    sto = (cache >> 8) != 0u;
+}
+
+__global__ __launch_bounds__(CK_WG) void k_map_count(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
+                                                     const unsigned char* __restrict__ swapState,
+                                                     const unsigned char* __restrict__ swapFlags, int n_total, int n_blocks,
+                                                     int4* __restrict__ groupCnt, int* __restrict__ bad)
+{
+    __shared__ int4 wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        ck_u4 e; unsigned vis, cache; bool rec, blk, sto;
+        ck_classify_map(hash, visType, swapState, swapFlags, g * CK_WG + t, n_total, e, vis, cache, rec, blk, sto);
+        if (blk && (int)e.w >= n_blocks) *bad = 1;
+        const int nr = __popcll(__ballot(rec)), nb = __popcll(__ballot(blk)), ns = __popcll(__ballot(sto));
+        __syncthreads();
+        if ((t & 63) == 0) wcnt[t >> 6] = make_int4(nr, nb, ns, 0);
+        __syncthreads();
+        if (t == 0) {
+            int4 s = make_int4(0, 0, 0, 0);
+            for (int w = 0; w < CK_WG / 64; ++w) { s.x += wcnt[w].x; s.y += wcnt[w].y; s.z += wcnt[w].z; }
+            groupCnt[g] = s;
+        }
+    }
+}
+
+// k_ckpt_prefix over three counts (.w unused)
+__global__ __launch_bounds__(CK_WG) void k_map_prefix(const int4* __restrict__ cnt, int ng, int4* __restrict__ base)
+{
+    __shared__ int4 part[CK_WG];
+    const int t = threadIdx.x, per = (ng + CK_WG - 1) / CK_WG;
+    const int first = min(t * per, ng), last = min(first + per, ng);
+    int4 s = make_int4(0, 0, 0, 0);
+    for (int g = first; g < last; ++g) { s.x += cnt[g].x; s.y += cnt[g].y; s.z += cnt[g].z; }
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int4 run = make_int4(0, 0, 0, 0);
+        for (int k = 0; k < CK_WG; ++k) { const int4 v = part[k]; part[k] = run; run.x += v.x; run.y += v.y; run.z += v.z; }
+        base[ng] = run;
+    }
+    __syncthreads();
+    s = part[t];
+    for (int g = first; g < last; ++g) { base[g] = s; s.x += cnt[g].x; s.y += cnt[g].y; s.z += cnt[g].z; }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_map_records(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
+                                                       const unsigned char* __restrict__ swapState,
+                                                       const unsigned char* __restrict__ swapFlags, int n_total,
+                                                       const int4* __restrict__ base, ck_u2* __restrict__ records,
+                                                       int* __restrict__ blockPtr, int* __restrict__ storedIdx)
+{
+    __shared__ int4 wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int idx = g * CK_WG + t;
+        ck_u4 e; unsigned vis, cache; bool rec, blk, sto;
+        ck_classify_map(hash, visType, swapState, swapFlags, idx, n_total, e, vis, cache, rec, blk, sto);
+        const unsigned long long mr = __ballot(rec), mb = __ballot(blk), ms = __ballot(sto), below = (1ull << lane) - 1ull;
+        __syncthreads();
+        if (lane == 0) wcnt[w] = make_int4(__popcll(mr), __popcll(mb), __popcll(ms), 0);
+        __syncthreads();
+        int4 b = base[g];
+        for (int k = 0; k < w; ++k) { b.x += wcnt[k].x; b.y += wcnt[k].y; b.z += wcnt[k].z; }
+        if (rec) {
+            ck_u2* r = records + 3 * (size_t)(b.x + __popcll(mr & below));
+            r[0] = ck_u2{ (unsigned)idx, e.x };
+            r[1] = ck_u2{ e.y, e.z };
+            r[2] = ck_u2{ e.w, vis | cache << 8 };         // visType, swapState, hasStoredData, 0
+        }
+        if (blk) blockPtr[b.y + __popcll(mb & below)] = (int)e.w;
+        if (sto) storedIdx[b.z + __popcll(ms & below)] = idx;
+    }
+}
+
+// blocks [0, nb) of the entry-index list between the GlobalCache's store and the staging buffer: ck_copy's
+// shape (16 B per lane, a wave instruction per KiB, contiguous inside a block).  The store is indexed by hash
+// entry, 2 KiB each, so the offset is formed in 64 bits (it passes 4 GiB above 2^21 entries); it is touched
+// once, so its side is nontemporal too.
+template <bool GATHER>
+__device__ __forceinline__ void ck_copy_store(ck_u4* __restrict__ store, const int* __restrict__ storedIdx, int nb,
+                                              ck_u4* __restrict__ stage)
+{
+    const size_t n = (size_t)nb << 7;
+    for (size_t u = (size_t)blockIdx.x * CK_WG + threadIdx.x; u < n; u += (size_t)gridDim.x * CK_WG) {
+        ck_u4* p = store + (size_t)storedIdx[u >> 7] * 128u + ((unsigned)u & 127u);
+        if (GATHER) __builtin_nontemporal_store(__builtin_nontemporal_load(p), stage + u);
+        else __builtin_nontemporal_store(__builtin_nontemporal_load(stage + u), p);
+    }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_map_gather(const TfVoxel* store, const int* __restrict__ storedIdx, int nb,
+                                                      ck_u4* __restrict__ stage)
+{
+    ck_copy_store<true>((ck_u4*)store, storedIdx, nb, stage);
+}
+
+__global__ __launch_bounds__(CK_WG) void k_map_scatter(TfVoxel* store, const int* __restrict__ storedIdx, int nb,
+                                                       const ck_u4* __restrict__ stage)
+{
+    ck_copy_store<false>((ck_u4*)store, storedIdx, nb, (ck_u4*)stage);
+}
+
+// k_ckpt_apply with the two cache bytes (swapState / swapFlags were cleared over the whole table before)
+__global__ __launch_bounds__(CK_WG) void k_map_apply(const ck_u2* __restrict__ records, long long n_records, TfHashEntry* __restrict__ hash,
+                                                     unsigned char* __restrict__ visType, unsigned char* __restrict__ swapState,
+                                                     unsigned char* __restrict__ swapFlags)
+{
+    for (long long k = (long long)blockIdx.x * CK_WG + threadIdx.x; k < n_records; k += (long long)gridDim.x * CK_WG) {
+        const ck_u2 a = records[3 * k], b = records[3 * k + 1], c = records[3 * k + 2];
+        *reinterpret_cast<ck_u4*>(hash + a.x) = ck_u4{ a.y, b.x, b.y, c.x };
+        visType[a.x] = (unsigned char)c.y;
+        swapState[a.x] = (unsigned char)(c.y >> 8);
+        swapFlags[a.x] = (unsigned char)(c.y >> 16);
+    }
+}
+
 static int ck_groups(const tf_ctx* c) { return (c->n_total + CK_WG - 1) / CK_WG; }
 static int ck_grid(size_t items) { const size_t g = (items + CK_WG - 1) / CK_WG; return (int)(g < 1 ? 1 : g > 2048 ? 2048 : g); }
 
@@ -159,7 +294,8 @@ static hipError_t tfk_ckpt_scratch(tf_ctx* c)
     if (c->ckptGroup) return hipSuccess;
     const size_t ng = (size_t)ck_groups(c);
     const size_t stage = (size_t)c->ckpt_chunk_blocks * TF_SCENE_BLOCK_BYTES * (c->p.voxel_rgb ? 2 : 1);
-    return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->ckptGroup, sizeof(int2) * (2 * ng + 2)), TfCtxMem::dev(&c->ckptStage, stage),
+    const size_t cnt = c->p.use_swapping ? sizeof(int4) : sizeof(int2);      // three tallies per group with the GlobalCache
+    return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->ckptGroup, cnt * (2 * ng + 2)), TfCtxMem::dev(&c->ckptStage, stage),
                                            TfCtxMem::pin(&c->ckptPinned, stage, hipHostMallocDefault) }));
 }
 
@@ -212,6 +348,52 @@ static hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_rec
     if (n_records == 0) return hipSuccess;
     hipLaunchKernelGGL(k_ckpt_apply, dim3(ck_grid((size_t)n_records)), dim3(CK_WG), 0, c->stream, (const ck_u2*)records, n_records, c->hash,
                        c->visType);
+    return hipGetLastError();
+}
+
+// the swapping forms: totals[0] = {records, blocks, flagged, -}, totals[1].x = the "not saveable" flag
+static hipError_t tfk_map_count(tf_ctx* c, const int4** totals)
+{
+    const int ng = ck_groups(c);
+    int4* cnt = (int4*)c->ckptGroup;
+    int4* base = cnt + ng;
+    int* bad = (int*)(base + ng + 1);
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int4), c->stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_map_count, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->swapState,
+                       c->swapFlags, c->n_total, c->p.n_blocks, cnt, bad);
+    hipLaunchKernelGGL(k_map_prefix, dim3(1), dim3(CK_WG), 0, c->stream, cnt, ng, base);
+    *totals = base + ng;
+    return hipGetLastError();
+}
+
+static hipError_t tfk_map_records(tf_ctx* c, void* records, int* blockPtr, int* storedIdx)
+{
+    hipLaunchKernelGGL(k_map_records, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->swapState,
+                       c->swapFlags, c->n_total, (const int4*)c->ckptGroup + ck_groups(c), (ck_u2*)records, blockPtr, storedIdx);
+    return hipGetLastError();
+}
+
+// nb <= ckpt_chunk_blocks stored blocks of the entry list into / out of the staging buffer
+static hipError_t tfk_map_gather(tf_ctx* c, const int* storedIdx, int nb)
+{
+    hipLaunchKernelGGL(k_map_gather, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, c->swapStore, storedIdx, nb,
+                       (ck_u4*)c->ckptStage);
+    return hipGetLastError();
+}
+
+static hipError_t tfk_map_scatter(tf_ctx* c, const int* storedIdx, int nb)
+{
+    hipLaunchKernelGGL(k_map_scatter, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, c->swapStore, storedIdx, nb,
+                       (const ck_u4*)c->ckptStage);
+    return hipGetLastError();
+}
+
+static hipError_t tfk_map_apply(tf_ctx* c, const void* records, long long n_records)
+{
+    if (n_records == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_map_apply, dim3(ck_grid((size_t)n_records)), dim3(CK_WG), 0, c->stream, (const ck_u2*)records, n_records, c->hash,
+                       c->visType, c->swapState, c->swapFlags);
     return hipGetLastError();
 }
 
@@ -279,44 +461,70 @@ static tf_status ckpt_h2d(tf_ctx* c, void* dev, const unsigned char* host, size_
     return TF_OK;
 }
 
+// version 1, or on a swapping context version 2 (tf_map_save): the cache's bytes in the records, the stored
+// blocks as a second payload
 static tf_status scene_save(tf_ctx* c, FILE* f)
 {
-    TfCtxMem tmp(c->mem.fns());                            // the record table and the ptr list, freed when this returns
+    TfCtxMem tmp(c->mem.fns());                            // the record table and the lists, freed when this returns
     unsigned char* rec_dev = nullptr;
     int* ptr_dev = nullptr;
+    int* sto_dev = nullptr;                                // swapping: the entries with a stored block, in record order
+    const bool sw = c->p.use_swapping != 0;
     TF_CHECK(tfk_ckpt_scratch(c));
     tf_status s = sync_state(c);                           // counters, pose; TF_HIP_ERROR on a context in error
     if (s != TF_OK) return s;
     const TfDevState* st = c->st_host;
-    struct tf_scene_file_info info;
-    memset(&info, 0, sizeof(info));
+    struct tf_map_file_info minfo;
+    memset(&minfo, 0, sizeof(minfo));
+    minfo.version = sw ? (int)TF_MAP_VERSION : (int)TF_SCENE_VERSION;
+    struct tf_scene_file_info& info = minfo.scene;
     info.params = c->p;
+    if (sw) info.params.use_swapping = 1;                  // (tf_create takes any non-zero value; the file holds 1)
     info.pose_algebra = c->pose_alg;
     info.frame_counter = st->frame_counter;
     info.lastFreeBlockId = st->lastFreeBlockId;
     info.lastFreeExcessListId = st->lastFreeExcessListId;
     info.noVisibleEntries = st->noVisibleEntries;
     memcpy(info.pose, st->pose, sizeof(info.pose));
-    const int2* totals_dev = nullptr;
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_count(c, &totals_dev); });
-    if (s != TF_OK) return s;
-    int2 totals[2];
-    TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
-    TF_CHECK(hipStreamSynchronize(c->stream));
-    if (totals[1].x) return TF_INVALID_ARG;                // an entry's ptr lies outside the VBA (uploaded tables)
-    info.n_records = totals[0].x;
-    info.n_blocks_stored = totals[0].y;
+    if (sw) {
+        const int4* totals_dev = nullptr;
+        s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_map_count(c, &totals_dev); });
+        if (s != TF_OK) return s;
+        int4 totals[2];
+        TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+        TF_CHECK(hipStreamSynchronize(c->stream));
+        if (totals[1].x) return TF_INVALID_ARG;
+        info.n_records = totals[0].x;
+        info.n_blocks_stored = totals[0].y;
+        minfo.n_cache_blocks = totals[0].z;
+    } else {
+        const int2* totals_dev = nullptr;
+        s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_count(c, &totals_dev); });
+        if (s != TF_OK) return s;
+        int2 totals[2];
+        TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+        TF_CHECK(hipStreamSynchronize(c->stream));
+        if (totals[1].x) return TF_INVALID_ARG;            // an entry's ptr lies outside the VBA (uploaded tables)
+        info.n_records = totals[0].x;
+        info.n_blocks_stored = totals[0].y;
+    }
     TfSceneLayout lay;
-    if (!tf_scene_layout(&info, &lay)) return TF_INVALID_ARG;      // counters outside their lists (tf_set_counters)
+    if (!tf_map_layout(&minfo, &lay)) return TF_INVALID_ARG;       // counters outside their lists (tf_set_counters)
     info.file_bytes = (long long)lay.file_bytes;
-    unsigned char hdr[TF_SCENE_HEADER_BYTES];
+    unsigned char hdr[TF_MAP_HEADER_BYTES];
+    const size_t hdr_bytes = lay.records_off;
     uint32_t records_crc = 0;
-    tf_scene_header_encode(&info, records_crc, hdr);       // rewritten at the end with the records' checksum
-    if (fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) return TF_INVALID_ARG;
+    const auto encode = [&] {                              // (rewritten at the end with the records' checksum)
+        if (sw) tf_map_header_encode(&minfo, records_crc, hdr);
+        else tf_scene_header_encode(&info, records_crc, hdr);
+    };
+    encode();
+    if (fwrite(hdr, 1, hdr_bytes, f) != hdr_bytes) return TF_INVALID_ARG;
     const size_t rec_bytes = (size_t)info.n_records * TF_SCENE_RECORD_BYTES;
     TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
     TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_records(c, rec_dev, ptr_dev); });
+    if (sw) TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * (size_t)minfo.n_cache_blocks)));
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return sw ? tfk_map_records(c, rec_dev, ptr_dev, sto_dev) : tfk_ckpt_records(c, rec_dev, ptr_dev); });
     if (s != TF_OK) return s;
     {   // the record table: to the host whole (24 B per record), checked by load's own rule before any block
         // moves -- chain offsets, duplicate ptr (tables that came through tf_upload) -- then summed and written
@@ -331,7 +539,8 @@ static tf_status scene_save(tf_ctx* c, FILE* f)
         }
         double t1 = ck_now_ms();
         c->ckpt_ms[CK_T_COPY] += t1 - t0;
-        s = tf_scene_records_check(rec.data(), info.n_records, &info.params, info.n_blocks_stored);
+        s = sw ? tf_map_records_check(rec.data(), info.n_records, &info.params, info.n_blocks_stored, minfo.n_cache_blocks)
+               : tf_scene_records_check(rec.data(), info.n_records, &info.params, info.n_blocks_stored);
         if (s != TF_OK) return s;
         records_crc = tf_scene_crc32(0u, rec.data(), rec_bytes);
         t0 = ck_now_ms();
@@ -345,6 +554,12 @@ static tf_status scene_save(tf_ctx* c, FILE* f)
         if (s == TF_OK) s = ckpt_d2h_write(c, f, c->ckptStage, (size_t)nb * lay.block_bytes);
         c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)lay.block_bytes;     // read + written
     }
+    for (long long b0 = 0; b0 < minfo.n_cache_blocks && s == TF_OK; b0 += c->ckpt_chunk_blocks) {      // the GlobalCache's
+        const int nb = (int)(minfo.n_cache_blocks - b0 < c->ckpt_chunk_blocks ? minfo.n_cache_blocks - b0 : c->ckpt_chunk_blocks);
+        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_map_gather(c, sto_dev + b0, nb); });
+        if (s == TF_OK) s = ckpt_d2h_write(c, f, c->ckptStage, (size_t)nb * TF_SCENE_BLOCK_BYTES);
+        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)TF_SCENE_BLOCK_BYTES;
+    }
     if (s == TF_OK) s = ckpt_d2h_write(c, f, c->visibleIds, 4 * lay.n_vis, c->n_total);
     if (s == TF_OK) s = ckpt_d2h_write(c, f, c->allocList, 4 * lay.n_alloc, c->p.n_blocks);
     if (s == TF_OK) s = ckpt_d2h_write(c, f, c->excessList, 4 * lay.n_excess, c->p.n_excess);
@@ -353,15 +568,15 @@ static tf_status scene_save(tf_ctx* c, FILE* f)
         if (s == TF_OK) s = ckpt_d2h_write(c, f, c->prev_nrm[l], lay.map_bytes[l]);
     }
     if (s != TF_OK) return s;
-    tf_scene_header_encode(&info, records_crc, hdr);
-    if (fseeko(f, 0, SEEK_SET) != 0 || fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) return TF_INVALID_ARG;
+    encode();
+    if (fseeko(f, 0, SEEK_SET) != 0 || fwrite(hdr, 1, hdr_bytes, f) != hdr_bytes) return TF_INVALID_ARG;
     return TF_OK;
 }
 
-extern "C" tf_status tf_scene_save(tf_ctx* c, const char* path)
+extern "C" tf_status tf_map_save(tf_ctx* c, const char* path)
 {
     TF_FLUSH(c);
-    if (!c || !path || c->p.use_swapping) return TF_INVALID_ARG;
+    if (!c || !path) return TF_INVALID_ARG;
     static_assert(TF_LEVELS == TF_SCENE_LEVELS, "the file stores the tracker's pyramid");
     {   // a context in error saves nothing (checked before the file is created)
         const tf_status s0 = sync_checked(c);
@@ -378,33 +593,58 @@ extern "C" tf_status tf_scene_save(tf_ctx* c, const char* path)
     return s;
 }
 
+extern "C" tf_status tf_scene_save(tf_ctx* c, const char* path)
+{
+    if (c && c->p.use_swapping) {                          // (after the deferred frame's tail, as every entry point)
+        TF_FLUSH(c);
+        return TF_INVALID_ARG;
+    }
+    return tf_map_save(c, path);
+}
+
 static bool bits_equal(float a, float b) { return memcmp(&a, &b, sizeof(float)) == 0; }
 
 // the validated file into the context (nothing here fails on the file's contents)
-static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct tf_scene_file_info& info, const TfSceneLayout& lay)
+static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay)
 {
-    TfCtxMem tmp(c->mem.fns());                            // the record table and the ptr list, freed when this returns
+    TfCtxMem tmp(c->mem.fns());                            // the record table and the lists, freed when this returns
     unsigned char* rec_dev = nullptr;
     int* ptr_dev = nullptr;
+    int* sto_dev = nullptr;
+    const struct tf_scene_file_info& info = minfo.scene;
+    const bool sw = minfo.version == (int)TF_MAP_VERSION;
     TF_CHECK(tfk_ckpt_scratch(c));
     TF_CHECK(tfk_reset_scene(c));                          // full: hash, VBA, colour, both lists (identity), block grid cells
     TF_CHECK(hipMemsetAsync(c->visType, 0, (size_t)c->n_total, c->stream));
+    if (sw) {   // the loader's own states and flags of entries the file does not name must not survive; the store
+                // itself is not cleared: a stored block whose flag is 0 is read by nobody
+        TF_CHECK(hipMemsetAsync(c->swapState, 0, (size_t)c->n_total, c->stream));
+        TF_CHECK(hipMemsetAsync(c->swapFlags, 0, (size_t)c->n_total, c->stream));
+    }
     const size_t rec_bytes = (size_t)info.n_records * TF_SCENE_RECORD_BYTES;
     TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
     TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
     tf_status s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
     if (s != TF_OK) return s;
-    {   // the stored blocks' ptr, in record order
-        std::vector<int> ptrs;
+    {   // the stored blocks' ptr, in record order; version 2: and the entries with a block in the GlobalCache
+        std::vector<int> ptrs, stored;
         ptrs.reserve((size_t)info.n_blocks_stored);
+        stored.reserve((size_t)minfo.n_cache_blocks);
         const unsigned char* r = data + lay.records_off;
         for (long long k = 0; k < info.n_records; ++k, r += TF_SCENE_RECORD_BYTES) {
-            int ptr;
+            int idx, ptr;
+            memcpy(&idx, r, sizeof(int));
             memcpy(&ptr, r + 16, sizeof(int));
             if (ptr >= 0) ptrs.push_back(ptr);
+            if (sw && r[22]) stored.push_back(idx);
         }
         s = ckpt_h2d(c, ptr_dev, (const unsigned char*)ptrs.data(), sizeof(int) * ptrs.size());
         if (s != TF_OK) return s;
+        if (sw) {
+            TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * stored.size())));
+            s = ckpt_h2d(c, sto_dev, (const unsigned char*)stored.data(), sizeof(int) * stored.size());
+            if (s != TF_OK) return s;
+        }
     }
     for (long long b0 = 0; b0 < info.n_blocks_stored; b0 += c->ckpt_chunk_blocks) {
         const int nb = (int)(info.n_blocks_stored - b0 < c->ckpt_chunk_blocks ? info.n_blocks_stored - b0 : c->ckpt_chunk_blocks);
@@ -414,8 +654,16 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
         if (s != TF_OK) return s;                                                                          // staging buffer is free again)
         c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)lay.block_bytes;
     }
+    for (long long b0 = 0; b0 < minfo.n_cache_blocks; b0 += c->ckpt_chunk_blocks) {        // the GlobalCache's, to store + index * 512
+        const int nb = (int)(minfo.n_cache_blocks - b0 < c->ckpt_chunk_blocks ? minfo.n_cache_blocks - b0 : c->ckpt_chunk_blocks);
+        s = ckpt_h2d(c, c->ckptStage, data + lay.stored_off + (size_t)b0 * TF_SCENE_BLOCK_BYTES, (size_t)nb * TF_SCENE_BLOCK_BYTES);
+        if (s != TF_OK) return s;
+        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_map_scatter(c, sto_dev + b0, nb); });
+        if (s != TF_OK) return s;
+        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)TF_SCENE_BLOCK_BYTES;
+    }
     s = ck_timed_kernels(c, CK_T_INDEX, [&] {              // the block grid from the hash, as after a hash upload
-        const hipError_t e = tfk_ckpt_apply(c, rec_dev, info.n_records);
+        const hipError_t e = sw ? tfk_map_apply(c, rec_dev, info.n_records) : tfk_ckpt_apply(c, rec_dev, info.n_records);
         return e == hipSuccess ? tfk_grid_rebuild(c) : e;
     });
     if (s != TF_OK) return s;
@@ -451,10 +699,10 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
     return s;
 }
 
-extern "C" tf_status tf_scene_load(tf_ctx* c, const char* path)
+extern "C" tf_status tf_map_load(tf_ctx* c, const char* path)
 {
     TF_FLUSH(c);
-    if (!c || !path || c->p.use_swapping) return TF_INVALID_ARG;
+    if (!c || !path) return TF_INVALID_ARG;
     {
         const tf_status s0 = sync_checked(c);
         if (s0 != TF_OK) return s0;
@@ -464,30 +712,40 @@ extern "C" tf_status tf_scene_load(tf_ctx* c, const char* path)
     if (!f) return TF_INVALID_ARG;
     long long size = -1;
     if (fseeko(f, 0, SEEK_END) == 0) size = (long long)ftello(f);
-    if (size < TF_SCENE_HEADER_BYTES || fseeko(f, 0, SEEK_SET) != 0) { fclose(f); return TF_INVALID_ARG; }
+    if (size < TF_SCENE_HEADER_BYTES || fseeko(f, 0, SEEK_SET) != 0) { fclose(f); return TF_INVALID_ARG; }    // (shorter than either header)
     memset(c->ckpt_ms, 0, sizeof(c->ckpt_ms));
     unsigned char* data = (unsigned char*)malloc((size_t)size);
     if (!data) { fclose(f); return TF_OOM; }
     const size_t got = fread(data, 1, (size_t)size, f);
     fclose(f);
     c->ckpt_ms[CK_T_FILE] = ck_now_ms() - t_call;
-    struct tf_scene_file_info info;
+    struct tf_map_file_info minfo;
     TfSceneLayout lay;
     const double t_check = ck_now_ms();
-    tf_status s = got == (size_t)size ? tf_scene_file_validate(data, got, &info, &lay) : TF_INVALID_ARG;
+    tf_status s = got == (size_t)size ? tf_map_file_validate(data, got, &minfo, &lay) : TF_INVALID_ARG;
     c->ckpt_ms[CK_T_CHECK] = ck_now_ms() - t_check;
     if (s == TF_OK) {
-        const tf_params& a = info.params;
+        const tf_params& a = minfo.scene.params;
         const tf_params& b = c->p;
+        // (a version-2 file has use_swapping == 1, a version-1 file 0: the layout's rule; the context's may be any non-zero value)
         if (a.cols != b.cols || a.rows != b.rows || a.n_buckets != b.n_buckets || a.n_excess != b.n_excess || a.n_blocks != b.n_blocks ||
-            a.voxel_rgb != b.voxel_rgb || a.use_swapping != 0 || !bits_equal(a.voxelSize, b.voxelSize) || !bits_equal(a.mu, b.mu) ||
-            a.maxW != b.maxW || info.noVisibleEntries > b.vis_capacity)
+            a.voxel_rgb != b.voxel_rgb || (a.use_swapping != 0) != (b.use_swapping != 0) || !bits_equal(a.voxelSize, b.voxelSize) ||
+            !bits_equal(a.mu, b.mu) || a.maxW != b.maxW || minfo.scene.noVisibleEntries > b.vis_capacity)
             s = TF_INVALID_ARG;
     }
-    if (s == TF_OK) s = scene_load(c, data, info, lay);
+    if (s == TF_OK) s = scene_load(c, data, minfo, lay);
     free(data);
     c->ckpt_ms[CK_T_CALL] = ck_now_ms() - t_call;
     return s;
+}
+
+extern "C" tf_status tf_scene_load(tf_ctx* c, const char* path)
+{
+    if (c && c->p.use_swapping) {                          // (after the deferred frame's tail, as every entry point)
+        TF_FLUSH(c);
+        return TF_INVALID_ARG;
+    }
+    return tf_map_load(c, path);
 }
 
 extern "C" tf_status tf_scene_ckpt_times(tf_ctx* c, double ms[8])

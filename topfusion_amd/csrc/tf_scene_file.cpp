@@ -47,7 +47,8 @@ static void put64(unsigned char* p, uint64_t v) { memcpy(p, &v, 8); }
 static uint32_t get32(const unsigned char* p) { uint32_t v; memcpy(&v, p, 4); return v; }
 static int64_t get64(const unsigned char* p) { int64_t v; memcpy(&v, p, 8); return v; }
 
-bool tf_scene_layout(const struct tf_scene_file_info* info, TfSceneLayout* lay)
+// the layout of either version: version 2 is a swapping context's (no colour plane), with n_cache stored blocks
+static bool layout_of(const struct tf_scene_file_info* info, unsigned version, long long n_cache, TfSceneLayout* lay)
 {
     const tf_params& p = info->params;
     // the bounds tf_create puts on a context's tables (params_valid, tf_capi.hip), so that every
@@ -57,7 +58,9 @@ bool tf_scene_layout(const struct tf_scene_file_info* info, TfSceneLayout* lay)
     if (p.n_excess <= 0 || p.n_excess > (1 << 30) || ((p.n_buckets + p.n_excess) % 16)) return false;
     if (p.n_blocks <= 0 || p.n_blocks > (1 << 21) - 1) return false;
     if (p.vis_capacity <= 0) return false;
-    if (p.use_swapping != 0) return false;                 // (voxel_rgb: any non-zero value is a colour context, as tf_create takes it)
+    if (version == TF_SCENE_VERSION) {
+        if (p.use_swapping != 0 || n_cache != 0) return false;     // (voxel_rgb: any non-zero value is a colour context, as tf_create takes it)
+    } else if (p.use_swapping != 1 || p.voxel_rgb != 0) return false;
     const long long n_total = (long long)p.n_buckets + p.n_excess;
     if (info->lastFreeBlockId < -1 || info->lastFreeBlockId >= p.n_blocks) return false;
     if (info->lastFreeExcessListId < -1 || info->lastFreeExcessListId >= p.n_excess) return false;
@@ -65,13 +68,16 @@ bool tf_scene_layout(const struct tf_scene_file_info* info, TfSceneLayout* lay)
     if (info->frame_counter < 0) return false;
     if (info->n_records < 0 || info->n_records > n_total) return false;
     if (info->n_blocks_stored < 0 || info->n_blocks_stored > info->n_records || info->n_blocks_stored > p.n_blocks) return false;
+    if (n_cache < 0 || n_cache > info->n_records) return false;
     lay->block_bytes = (size_t)TF_SCENE_BLOCK_BYTES * (p.voxel_rgb ? 2 : 1);
     lay->n_vis = (size_t)info->noVisibleEntries;
     lay->n_alloc = (size_t)(info->lastFreeBlockId + 1);
     lay->n_excess = (size_t)(info->lastFreeExcessListId + 1);
-    lay->records_off = TF_SCENE_HEADER_BYTES;
+    lay->records_off = version == TF_SCENE_VERSION ? TF_SCENE_HEADER_BYTES : TF_MAP_HEADER_BYTES;
     lay->blocks_off = lay->records_off + (size_t)info->n_records * TF_SCENE_RECORD_BYTES;
-    lay->vis_off = lay->blocks_off + (size_t)info->n_blocks_stored * lay->block_bytes;
+    lay->stored_off = lay->blocks_off + (size_t)info->n_blocks_stored * lay->block_bytes;
+    lay->n_stored = (size_t)n_cache;
+    lay->vis_off = lay->stored_off + lay->n_stored * TF_SCENE_BLOCK_BYTES;
     lay->alloc_off = lay->vis_off + 4 * lay->n_vis;
     lay->excess_off = lay->alloc_off + 4 * lay->n_alloc;
     lay->maps_off = lay->excess_off + 4 * lay->n_excess;
@@ -84,12 +90,24 @@ bool tf_scene_layout(const struct tf_scene_file_info* info, TfSceneLayout* lay)
     return true;
 }
 
-void tf_scene_header_encode(const struct tf_scene_file_info* info, uint32_t records_crc, unsigned char hdr[TF_SCENE_HEADER_BYTES])
+bool tf_scene_layout(const struct tf_scene_file_info* info, TfSceneLayout* lay)
+{
+    return layout_of(info, TF_SCENE_VERSION, 0, lay);
+}
+
+bool tf_map_layout(const struct tf_map_file_info* info, TfSceneLayout* lay)
+{
+    if (info->version != (int)TF_SCENE_VERSION && info->version != (int)TF_MAP_VERSION) return false;
+    return layout_of(&info->scene, (unsigned)info->version, info->n_cache_blocks, lay);
+}
+
+// bytes [0, 288) of either version's header
+static void header_fields_encode(const struct tf_scene_file_info* info, uint32_t version, unsigned char* hdr)
 {
     static_assert(sizeof(tf_params) == 180, "the header stores tf_params as it is laid out");
-    memset(hdr, 0, TF_SCENE_HEADER_BYTES);
+    memset(hdr, 0, TF_SCENE_OFF_CRC);
     memcpy(hdr + TF_SCENE_OFF_MAGIC, k_magic, 8);
-    put32(hdr + TF_SCENE_OFF_VERSION, TF_SCENE_VERSION);
+    put32(hdr + TF_SCENE_OFF_VERSION, version);
     put32(hdr + TF_SCENE_OFF_PARAMS_BYTES, (uint32_t)sizeof(tf_params));
     memcpy(hdr + TF_SCENE_OFF_PARAMS, &info->params, sizeof(tf_params));
     const int32_t ints[5] = { info->pose_algebra, info->frame_counter, info->lastFreeBlockId, info->lastFreeExcessListId,
@@ -99,17 +117,35 @@ void tf_scene_header_encode(const struct tf_scene_file_info* info, uint32_t reco
     put64(hdr + TF_SCENE_OFF_COUNTS + 8, (uint64_t)info->n_blocks_stored);
     put64(hdr + TF_SCENE_OFF_COUNTS + 16, (uint64_t)info->file_bytes);
     memcpy(hdr + TF_SCENE_OFF_POSE, info->pose, sizeof(float) * 12);
+}
+
+void tf_scene_header_encode(const struct tf_scene_file_info* info, uint32_t records_crc, unsigned char hdr[TF_SCENE_HEADER_BYTES])
+{
+    header_fields_encode(info, TF_SCENE_VERSION, hdr);
     put32(hdr + TF_SCENE_OFF_CRC, tf_scene_crc32(0u, hdr, TF_SCENE_OFF_CRC));
     put32(hdr + TF_SCENE_OFF_RECORDS_CRC, records_crc);
 }
 
-tf_status tf_scene_header_decode(const unsigned char* hdr, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay)
+void tf_map_header_encode(const struct tf_map_file_info* info, uint32_t records_crc, unsigned char hdr[TF_MAP_HEADER_BYTES])
 {
-    if (!hdr || !info || !lay || len < TF_SCENE_HEADER_BYTES) return TF_INVALID_ARG;
+    header_fields_encode(&info->scene, TF_MAP_VERSION, hdr);
+    put64(hdr + TF_MAP_OFF_CACHE_BLOCKS, (uint64_t)info->n_cache_blocks);
+    put32(hdr + TF_MAP_OFF_CRC, tf_scene_crc32(0u, hdr, TF_MAP_OFF_CRC));
+    put32(hdr + TF_MAP_OFF_RECORDS_CRC, records_crc);
+}
+
+// a header of `version` (1 or 2): magic, version, sizes, checksum, the fields, the layout, file_bytes
+static tf_status header_decode(const unsigned char* hdr, size_t len, uint32_t version, struct tf_scene_file_info* info,
+                               long long* n_cache, TfSceneLayout* lay)
+{
+    const bool v1 = version == TF_SCENE_VERSION;
+    const size_t hdr_bytes = v1 ? TF_SCENE_HEADER_BYTES : TF_MAP_HEADER_BYTES, crc_off = v1 ? TF_SCENE_OFF_CRC : TF_MAP_OFF_CRC;
+    if (!hdr || !info || !lay || len < hdr_bytes) return TF_INVALID_ARG;
     if (memcmp(hdr + TF_SCENE_OFF_MAGIC, k_magic, 8) != 0) return TF_INVALID_ARG;
-    if (get32(hdr + TF_SCENE_OFF_VERSION) != TF_SCENE_VERSION) return TF_INVALID_ARG;
+    if (get32(hdr + TF_SCENE_OFF_VERSION) != version) return TF_INVALID_ARG;
     if (get32(hdr + TF_SCENE_OFF_PARAMS_BYTES) != (uint32_t)sizeof(tf_params)) return TF_INVALID_ARG;
-    if (get32(hdr + TF_SCENE_OFF_CRC) != tf_scene_crc32(0u, hdr, TF_SCENE_OFF_CRC)) return TF_INVALID_ARG;
+    if (get32(hdr + crc_off) != tf_scene_crc32(0u, hdr, crc_off)) return TF_INVALID_ARG;
+    *n_cache = v1 ? 0 : get64(hdr + TF_MAP_OFF_CACHE_BLOCKS);
     memset(info, 0, sizeof(*info));
     memcpy(&info->params, hdr + TF_SCENE_OFF_PARAMS, sizeof(tf_params));
     int32_t ints[5];
@@ -120,8 +156,28 @@ tf_status tf_scene_header_decode(const unsigned char* hdr, size_t len, struct tf
     info->n_blocks_stored = get64(hdr + TF_SCENE_OFF_COUNTS + 8);
     info->file_bytes = get64(hdr + TF_SCENE_OFF_COUNTS + 16);
     memcpy(info->pose, hdr + TF_SCENE_OFF_POSE, sizeof(float) * 12);
-    if (!tf_scene_layout(info, lay)) return TF_INVALID_ARG;
+    if (!layout_of(info, version, *n_cache, lay)) return TF_INVALID_ARG;
     if (info->file_bytes < 0 || (unsigned long long)info->file_bytes != (unsigned long long)lay->file_bytes) return TF_INVALID_ARG;
+    return TF_OK;
+}
+
+tf_status tf_scene_header_decode(const unsigned char* hdr, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay)
+{
+    long long n_cache;
+    return header_decode(hdr, len, TF_SCENE_VERSION, info, &n_cache, lay);
+}
+
+tf_status tf_map_header_decode(const unsigned char* hdr, size_t len, struct tf_map_file_info* info, TfSceneLayout* lay)
+{
+    if (!hdr || !info || !lay || len < TF_SCENE_OFF_VERSION + 4) return TF_INVALID_ARG;
+    const uint32_t version = get32(hdr + TF_SCENE_OFF_VERSION);
+    if (version != TF_SCENE_VERSION && version != TF_MAP_VERSION) return TF_INVALID_ARG;
+    struct tf_map_file_info tmp;
+    memset(&tmp, 0, sizeof(tmp));
+    const tf_status s = header_decode(hdr, len, version, &tmp.scene, &tmp.n_cache_blocks, lay);
+    if (s != TF_OK) return s;
+    tmp.version = (int)version;
+    *info = tmp;
     return TF_OK;
 }
 
@@ -134,14 +190,16 @@ bool tf_scene_list_within(const unsigned char* p, size_t n, int32_t bound)
     return true;
 }
 
-tf_status tf_scene_records_check(const unsigned char* r, long long n_records, const tf_params* pp, long long n_blocks_stored)
+// version 1: bytes 21..23 are padding; version 2: swapState, hasStoredData, one padding byte
+static tf_status records_check(const unsigned char* r, long long n_records, const tf_params* pp, long long n_blocks_stored, bool v2,
+                               long long n_cache_blocks)
 {
     const tf_params& p = *pp;
     const int64_t n_total = (int64_t)p.n_buckets + p.n_excess;
     unsigned char* used = (unsigned char*)calloc(((size_t)p.n_blocks + 7) / 8, 1);     // ptr seen
     if (!used) return TF_OOM;
     tf_status s = TF_OK;
-    int64_t prev = -1, stored = 0;
+    int64_t prev = -1, stored = 0, cached = 0;
     for (long long k = 0; k < n_records && s == TF_OK; ++k, r += TF_SCENE_RECORD_BYTES) {
         const int64_t idx = (int64_t)get32(r);
         int16_t xyzp[4];
@@ -149,39 +207,63 @@ tf_status tf_scene_records_check(const unsigned char* r, long long n_records, co
         const int32_t offset = (int32_t)get32(r + 12), ptr = (int32_t)get32(r + 16);
         const unsigned char vis = r[20];
         if (idx <= prev || idx >= n_total) s = TF_INVALID_ARG;                 // strictly ascending, in the table
-        else if (r[21] | r[22] | r[23]) s = TF_INVALID_ARG;                    // padding
+        else if (v2 ? (r[21] > 2 || r[22] > 1 || r[23]) : (r[21] | r[22] | r[23])) s = TF_INVALID_ARG;   // padding; state, flag
         else if (offset > p.n_excess) s = TF_INVALID_ARG;                      // the chain's next entry: n_buckets + offset - 1
         else if (ptr >= p.n_blocks) s = TF_INVALID_ARG;
-        else if (!(xyzp[0] | xyzp[1] | xyzp[2] | xyzp[3]) && offset == 0 && ptr == -2 && vis == 0)
+        else if (!(xyzp[0] | xyzp[1] | xyzp[2] | xyzp[3]) && offset == 0 && ptr == -2 && vis == 0 && !(r[21] | r[22]))
             s = TF_INVALID_ARG;                                                // ResetScene's entry has no record
         else if (ptr >= 0) {
             if (used[ptr >> 3] >> (ptr & 7) & 1) s = TF_INVALID_ARG;           // two entries, one block
             used[ptr >> 3] |= (unsigned char)(1u << (ptr & 7));
             ++stored;
         }
+        if (s == TF_OK && v2) cached += r[22];
         prev = idx;
     }
     free(used);
     if (s != TF_OK) return s;
-    return stored == n_blocks_stored ? TF_OK : TF_INVALID_ARG;
+    return stored == n_blocks_stored && cached == n_cache_blocks ? TF_OK : TF_INVALID_ARG;
 }
 
-tf_status tf_scene_file_validate(const unsigned char* data, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay)
+tf_status tf_scene_records_check(const unsigned char* r, long long n_records, const tf_params* pp, long long n_blocks_stored)
 {
-    const tf_status hs = tf_scene_header_decode(data, len, info, lay);
-    if (hs != TF_OK) return hs;
+    return records_check(r, n_records, pp, n_blocks_stored, false, 0);
+}
+
+tf_status tf_map_records_check(const unsigned char* r, long long n_records, const tf_params* pp, long long n_blocks_stored,
+                               long long n_cache_blocks)
+{
+    return records_check(r, n_records, pp, n_blocks_stored, true, n_cache_blocks);
+}
+
+// what follows a decoded header of either version
+static tf_status body_validate(const unsigned char* data, size_t len, const struct tf_scene_file_info* info, bool v2, long long n_cache,
+                               const TfSceneLayout* lay)
+{
     if (len != lay->file_bytes) return TF_INVALID_ARG;
     const tf_params& p = info->params;
     const int64_t n_total = (int64_t)p.n_buckets + p.n_excess;
-    if (get32(data + TF_SCENE_OFF_RECORDS_CRC) !=
+    if (get32(data + (v2 ? TF_MAP_OFF_RECORDS_CRC : TF_SCENE_OFF_RECORDS_CRC)) !=
         tf_scene_crc32(0u, data + lay->records_off, (size_t)info->n_records * TF_SCENE_RECORD_BYTES))
         return TF_INVALID_ARG;
-    const tf_status rs = tf_scene_records_check(data + lay->records_off, info->n_records, &p, info->n_blocks_stored);
+    const tf_status rs = records_check(data + lay->records_off, info->n_records, &p, info->n_blocks_stored, v2, n_cache);
     if (rs != TF_OK) return rs;
     if (!tf_scene_list_within(data + lay->vis_off, lay->n_vis, (int32_t)n_total)) return TF_INVALID_ARG;
     if (!tf_scene_list_within(data + lay->alloc_off, lay->n_alloc, p.n_blocks)) return TF_INVALID_ARG;
     if (!tf_scene_list_within(data + lay->excess_off, lay->n_excess, p.n_excess)) return TF_INVALID_ARG;
     return TF_OK;
+}
+
+tf_status tf_scene_file_validate(const unsigned char* data, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay)
+{
+    const tf_status hs = tf_scene_header_decode(data, len, info, lay);
+    return hs != TF_OK ? hs : body_validate(data, len, info, false, 0, lay);
+}
+
+tf_status tf_map_file_validate(const unsigned char* data, size_t len, struct tf_map_file_info* info, TfSceneLayout* lay)
+{
+    const tf_status hs = tf_map_header_decode(data, len, info, lay);
+    return hs != TF_OK ? hs : body_validate(data, len, &info->scene, info->version == (int)TF_MAP_VERSION, info->n_cache_blocks, lay);
 }
 
 extern "C" tf_status tf_scene_file_info(const char* path, struct tf_scene_file_info* info)
@@ -199,6 +281,25 @@ extern "C" tf_status tf_scene_file_info(const char* path, struct tf_scene_file_i
     const tf_status s = tf_scene_header_decode(hdr, got, &tmp, &lay);
     if (s != TF_OK) return s;
     if (size != tmp.file_bytes) return TF_INVALID_ARG;
+    *info = tmp;
+    return TF_OK;
+}
+
+extern "C" tf_status tf_map_file_info(const char* path, struct tf_map_file_info* info)
+{
+    if (!path || !info) return TF_INVALID_ARG;
+    FILE* f = fopen(path, "rb");
+    if (!f) return TF_INVALID_ARG;
+    unsigned char hdr[TF_MAP_HEADER_BYTES];
+    const size_t got = fread(hdr, 1, sizeof(hdr), f);
+    long long size = -1;
+    if (fseeko(f, 0, SEEK_END) == 0) size = (long long)ftello(f);
+    fclose(f);
+    struct tf_map_file_info tmp;
+    TfSceneLayout lay;
+    const tf_status s = tf_map_header_decode(hdr, got, &tmp, &lay);
+    if (s != TF_OK) return s;
+    if (size != tmp.scene.file_bytes) return TF_INVALID_ARG;
     *info = tmp;
     return TF_OK;
 }

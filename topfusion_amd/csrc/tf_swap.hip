@@ -20,7 +20,9 @@
 // MI355X design: the GlobalCache lives in HBM (2 KiB per hash entry: 2.4 GB at the reference's
 // 1.18 M entries -- the "host" of the lineage is a second tier in the 288 GB of the same
 // device), so a transfer is a device-side copy inside the frame's launches, with no host round
-// trip and no staging buffer; hipMemcpy moves it to / from a file (tf_swap_save / _load).
+// trip and no staging buffer; hipMemcpy moves it to / from a file (tf_swap_save / _load).  A file a
+// sequence resumes from -- states, flags and only the flagged blocks, with the scene -- is the map
+// checkpoint (tf_map_save / _load, tf_scene_ckpt.hip).
 // Three launches per frame after integration, over 4096-entry chunks like the allocation scans:
 // count swap-in candidates; swap in (ordered by a chunk prefix) + count swap-out candidates;
 // swap out.  The reallocation of listed swapped-out entries is the same count + prefix pattern

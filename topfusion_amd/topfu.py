@@ -344,11 +344,33 @@ class TopFu:
         L.check(L.load().tf_scene_ckpt_times(self._h, _ptr(ms)), "tf_scene_ckpt_times")
         return dict(zip(("index_kernels", "block_kernels", "copies", "file", "call", "block_kernel_bytes", "check"), ms.tolist()))
 
+    # -- map checkpoints (additions: tf_map_save / tf_map_load): a swapping context's too, both tiers ----
+    def save_map(self, path):
+        """save_scene's file on a context without swapping; on a swapping context the version-2 file,
+        which adds the GlobalCache: swap states, stored flags and the stored blocks (tf_map_save)."""
+        L.check(L.load().tf_map_save(self._h, str(path).encode()), "tf_map_save")
+
+    def load_map(self, path):
+        """load_scene for either kind of context (tf_map_load): the file's use_swapping must be the
+        context's.  A refused file leaves the context, GlobalCache included, as it was."""
+        L.check(L.load().tf_map_load(self._h, str(path).encode()), "tf_map_load")
+        self._framed = True
+
+    @classmethod
+    def from_map(cls, path, device=None, **overrides):
+        """from_scene for a map checkpoint of either version: the context is built from the file's
+        params, swapping included."""
+        return cls._from_file(path, device, overrides, L.map_file_info, "load_map")
+
     @classmethod
     def from_scene(cls, path, device=None, **overrides):
         """A context built from the file's params (with `overrides` applied, as default_params takes
         them) that has loaded the file; the pose algebra is the file's too."""
-        info = L.scene_file_info(path)
+        return cls._from_file(path, device, overrides, L.scene_file_info, "load_scene")
+
+    @classmethod
+    def _from_file(cls, path, device, overrides, file_info, load):
+        info = file_info(path)
         p = info["params"]
         for k, v in overrides.items():
             if k == "icp_iter_num":
@@ -363,7 +385,7 @@ class TopFu:
         t = cls(p, device=device)
         try:
             t.set_pose_algebra(info["pose_algebra"])
-            t.load_scene(path)
+            getattr(t, load)(path)
         except Exception:
             t.close()
             raise
