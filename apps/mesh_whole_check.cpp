@@ -8,8 +8,10 @@
 // face count is the extraction's.  Bit-exactness against the reference is the Python tests' job
 // (tests/test_gpu_mesh_whole.py), which reads the state this program dumps when given a prefix.
 //
-//   ./mesh_whole_check [mesh.ply=/tmp/mesh_whole_check.ply] [dump_prefix]
+//   ./mesh_whole_check [mesh.ply=/tmp/mesh_whole_check.ply] [dump_prefix] [--indexed out.ply]
 //   dump_prefix: the five buffers the whole reading resolves, as <prefix>.hash .vba .state .flags .store
+//   --indexed out.ply: also the whole map with shared vertices (Scene::extractMeshIndexed with TF_MESH_WHOLE,
+//   Scene::saveMeshIndexedWhole -- the streaming writer), its vertex and triangle counts printed
 #include <tfusion/engines.hpp>
 
 #include "synth_depth.hpp"
@@ -38,6 +40,14 @@ static const char* kNames[5] = { ".hash", ".vba", ".state", ".flags", ".store" }
 
 int main(int argc, char** argv)
 {
+    std::string indexedPath;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!std::strcmp(argv[i], "--indexed")) {
+            indexedPath = argv[i + 1];
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     const std::string path = argc > 1 ? argv[1] : "/tmp/mesh_whole_check.ply";
     const int cols = 96, rows = 72;
     cuda::setDevice(0);
@@ -100,6 +110,17 @@ int main(int argc, char** argv)
         std::fclose(f);
     }
     if (faces != whole) { ++fails; std::printf("MISMATCH: %lld faces in the file, %lld triangles extracted\n", faces, whole); }
+
+    if (!indexedPath.empty()) {
+        cuda::DeviceArray<float> verts, vnormals;
+        cuda::DeviceArray<unsigned> indices;
+        const long long nt = scene.extractMeshIndexed(verts, indices, &vnormals, TF_MESH_WHOLE);
+        const long long nv = (long long)verts.size() / 3;
+        if (nt != whole) { ++fails; std::printf("MISMATCH: %lld indexed triangles, %lld in the soup\n", nt, whole); }
+        if ((long long)indices.size() != nt * 3 || vnormals.size() != verts.size()) { ++fails; std::printf("MISMATCH: indexed buffer sizes\n"); }
+        scene.saveMeshIndexedWhole(indexedPath, TF_MESH_NORMALS);
+        std::printf("indexed whole mesh: %lld vertices, %lld triangles\n", nv, nt);
+    }
 
     for (int b = 0; b < 5; ++b) {
         const std::vector<unsigned char> after = download(scene.context(), kBuffers[b]);

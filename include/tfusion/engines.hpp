@@ -186,6 +186,34 @@ namespace tfusion
             if (attrs & TF_MESH_INDEXED) tf_engine_check(tf_mesh_save_ply_indexed(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_indexed");
             else tf_engine_check(tf_mesh_save_ply_attr(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_attr");
         }
+        // The mesh with shared vertices: 3 floats per vertex, 3 vertex numbers per triangle (extractMesh's
+        // triangles in its order), 3 normal floats per vertex when the pointer is not null; all resized to fit.
+        // flags: 0 = the resident blocks (tf_mesh_extract_indexed), TF_MESH_WHOLE = every block of either tier
+        // (tf_mesh_extract_indexed_whole).  Returns the triangle count; vertices.size() / 3 is the vertex count.
+        long long extractMeshIndexed(cuda::DeviceArray<float>& vertices, cuda::DeviceArray<unsigned>& indices,
+                                     cuda::DeviceArray<float>* normals = nullptr, int flags = 0)
+        {
+            if (flags & ~TF_MESH_WHOLE) tf_engine_check(TF_INVALID_ARG, "Scene::extractMeshIndexed");
+            const bool whole = (flags & TF_MESH_WHOLE) != 0;
+            auto call = [&](float* v, float* n, long long vcap, unsigned* i, long long tcap, long long* nv, long long* nt) {
+                return whole ? tf_mesh_extract_indexed_whole(ctx_, v, n, vcap, i, tcap, nv, nt)
+                             : tf_mesh_extract_indexed(ctx_, v, n, nullptr, vcap, i, tcap, nv, nt);
+            };
+            long long nv = 0, nt = 0, mv = 0, mt = 0;
+            tf_engine_check(call(nullptr, nullptr, 0, nullptr, 0, &nv, &nt), "Scene::extractMeshIndexed");
+            vertices.create((size_t)nv * 3);
+            indices.create((size_t)nt * 3);
+            if (normals) normals->create((size_t)nv * 3);
+            if (nt > 0)
+                tf_engine_check(call(vertices.ptr(), normals ? normals->ptr() : nullptr, nv, indices.ptr(), nt, &mv, &mt), "Scene::extractMeshIndexed");
+            return nt;
+        }
+        // the whole map's indexed mesh as a binary PLY, written in bounded pieces (tf_mesh_save_ply_indexed_whole):
+        // attrs = 0 or TF_MESH_NORMALS; the host holds one chunk, whatever the map
+        void saveMeshIndexedWhole(const std::string& path, int attrs = 0)
+        {
+            tf_engine_check(tf_mesh_save_ply_indexed_whole(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_indexed_whole");
+        }
 
         // Map checkpoints (additions: tf_map_save / tf_map_load).  saveMap writes the state the scene resumes
         // from, sized by what is live: of a swapping scene both tiers -- the hash, the active blocks, the

@@ -455,8 +455,10 @@ tf_status tf_time_stage(tf_ctx* ctx, int stage, const float pose_rt[12], int ite
  * write (Mesh extraction, the whole map).  The GlobalCache is read where it lies; nothing is
  * swapped in and neither tier is written.  On a context with no stored data -- any context without
  * use_swapping, a swapping one before its first eviction -- the whole mesh is byte-identical to the
- * resident one.  The indexed form is resident-only: its vertex numbering is keyed by VBA block, which a
- * stored block does not have. */
+ * resident one.  The indexed form exists in both readings: tf_mesh_extract_indexed and tf_mesh_save_ply_indexed
+ * are resident-only (their edge bits are keyed by VBA block, which a stored block does not have);
+ * tf_mesh_extract_indexed_whole and tf_mesh_save_ply_indexed_whole give the whole reading's triangles as a vertex
+ * table and indices, their edge bits keyed by a compact numbering of the entries that resolve. */
 /* addition (no reference counterpart): triangles in a fixed order (ascending hash entry, voxel
  * x + 8y + 64z, tetrahedron, triangle of the case) as float[n][9] -- three xyz vertices, right-hand
  * normal towards sdf >= 0 -- into the device buffer: the first min(n, capacity) of them;
@@ -542,6 +544,48 @@ tf_status tf_mesh_write_ply_indexed(const char* path, const float* host_vertices
  * only: TF_MESH_WHOLE in attrs is TF_INVALID_ARG (see DESIGN.md §10 for what rekeying the edge bits by hash
  * entry would take) */
 tf_status tf_mesh_save_ply_indexed(tf_ctx* ctx, const char* path, int attrs);
+
+/* addition (no reference counterpart): tf_mesh_extract_indexed in the whole reading -- tf_mesh_extract_whole's
+ * triangles in its order as a vertex table (positions float[nv][3], normals float[nv][3]; no colours: a swapping
+ * scene has no colour plane) and indices uint32[nt][3]: vertices[indices] is tf_mesh_extract_whole's float[nt][9]
+ * bit for bit, normals[indices] its normals.  A vertex is its Kuhn edge (p, d), as above; the edge's owner is the
+ * first entry on the hash walk of block floor(p / 8) that resolves (ptr >= 0, or ptr == -1 with stored data), and
+ * vertices are numbered by ascending owner hash entry, then p's voxel index in the owner block, then
+ * dx | dy << 1 | dz << 2.  The capacity, NULL, count-only, full-count and TF_INDEX_RANGE rules are
+ * tf_mesh_extract_indexed's, without the colour column.  On a context with no stored data the result is
+ * tf_mesh_extract_indexed's byte for byte (the same kernels).  TF_OOM when the scratch cannot be had -- one int
+ * per hash entry, and 448 B of edge bits and as much of prefixes per entry that RESOLVES (not per hash entry, not
+ * per VBA block), kept by the context and grown geometrically when a later extraction finds more entries; the
+ * context stays usable.  The resident form's scratch is separate: the two may alternate on one context.  Two
+ * extractions of one scene are byte-identical.  Synchronous; the scene and the GlobalCache are only read. */
+tf_status tf_mesh_extract_indexed_whole(tf_ctx* ctx, float* dev_vertices, float* dev_normals, long long vertex_capacity,
+                                        uint32_t* dev_indices, long long triangle_capacity, long long* n_vertices,
+                                        long long* n_triangles);
+/* addition (no reference counterpart): the whole map as an indexed PLY, written in bounded pieces.  attrs: 0 or
+ * TF_MESH_NORMALS (any other bit is TF_INVALID_ARG).  The columns of tf_mesh_extract_indexed_whole stay in a
+ * temporary device buffer and come to the host a chunk at a time through a pinned staging buffer kept by the
+ * context (TFUSION_MESH_CHUNK_BYTES bytes, read at tf_create; default 8388608 = 8 MiB; values outside
+ * [24, 2^30] read as the default); the streaming writer below interleaves each chunk into vertex records and then
+ * face records, so host memory is bounded by the chunk, never by the mesh.  The file is tf_mesh_write_ply_indexed's
+ * for the extracted arrays, byte for byte, whatever the chunk size.  TF_INDEX_RANGE beyond 2^31 - 1 vertices;
+ * TF_OOM when a buffer cannot be had; every index is checked against nv, chunk by chunk (TF_INVALID_ARG).  On
+ * any failure no file is left. */
+tf_status tf_mesh_save_ply_indexed_whole(tf_ctx* ctx, const char* path, int attrs);
+
+/* addition (no reference counterpart): the streaming form of tf_mesh_write_ply_indexed -- host only, no context.
+ * begin writes the header for nv vertices and nt faces with the columns attrs names (TF_MESH_NORMALS,
+ * TF_MESH_COLOURS); then the vertices in any number of pieces (normals / colours as attrs declared them, NULL
+ * otherwise), then the faces in any number of pieces (all vertices first; an index >= nv fails); end closes the
+ * file.  The writer's memory is a fixed record buffer.  After a failed call every further append fails, and end
+ * -- which must be called exactly once after a successful begin, and frees the stream -- removes the file and
+ * returns TF_INVALID_ARG, as it does when fewer records were appended than begin declared.  commit == 0: the
+ * caller gives up; the file is removed and end returns TF_OK. */
+typedef struct tf_ply_stream tf_ply_stream;
+tf_status tf_mesh_ply_begin(const char* path, long long nv, long long nt, int attrs, tf_ply_stream** out);
+tf_status tf_mesh_ply_vertices(tf_ply_stream* s, const float* host_vertices, const float* host_normals,
+                               const uint8_t* host_colours, long long n);
+tf_status tf_mesh_ply_faces(tf_ply_stream* s, const uint32_t* host_indices, long long n);
+tf_status tf_mesh_ply_end(tf_ply_stream* s, int commit);
 
 /* ---- scene checkpoints (additions: the reference cannot save its map; DESIGN.md §5 Scene checkpoints) --
  * A checkpoint is the state a sequence resumes from, sized by what is live: the hash entries that differ

@@ -199,6 +199,13 @@ def load():
                                      ctypes.POINTER(ctypes.c_longlong)], I),
         "tf_mesh_write_ply_indexed": ([ctypes.c_char_p, P, P, P, ctypes.c_longlong, P, ctypes.c_longlong], I),
         "tf_mesh_save_ply_indexed": ([P, ctypes.c_char_p, I], I),
+        "tf_mesh_extract_indexed_whole": ([P, P, P, ctypes.c_longlong, P, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong),
+                                           ctypes.POINTER(ctypes.c_longlong)], I),
+        "tf_mesh_save_ply_indexed_whole": ([P, ctypes.c_char_p, I], I),
+        "tf_mesh_ply_begin": ([ctypes.c_char_p, ctypes.c_longlong, ctypes.c_longlong, I, ctypes.POINTER(P)], I),
+        "tf_mesh_ply_vertices": ([P, P, P, P, ctypes.c_longlong], I),
+        "tf_mesh_ply_faces": ([P, P, ctypes.c_longlong], I),
+        "tf_mesh_ply_end": ([P, I], I),
         "tf_scene_save": ([P, ctypes.c_char_p], I),
         "tf_scene_load": ([P, ctypes.c_char_p], I),
         "tf_scene_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfSceneFileInfo)], I),

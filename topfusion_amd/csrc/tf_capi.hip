@@ -224,6 +224,9 @@ static tf_status ctx_reset(tf_ctx* c)
 //   TFUSION_FUSE_TAIL           on          0: engine batches in the 7-launch form                         test_gpu_hash_stress
 //   TFUSION_CKPT_CHUNK_BLOCKS   4096        blocks per staging chunk of tf_scene_save / tf_scene_load;     test_gpu_scene_ckpt
 //                                           outside [1, 2^18]: the default
+//   TFUSION_MESH_CHUNK_BYTES    8388608     bytes of the pinned chunk through which                        test_gpu_mesh_indexed_whole
+//                                           tf_mesh_save_ply_indexed_whole brings the columns to the
+//                                           host; outside [24, 2^30]: the default
 //   TFUSION_CKPT_TIMING         off         1: HIP events (and a wait) around the checkpoint kernels,      (tools)
 //                                           for tf_scene_ckpt_times
 //   TFUSION_PERCALL_EARLY       on          0: per-call frames wait for the whole frame                    test_gpu_percall, test_gpu_failures
@@ -252,6 +255,7 @@ static void tf_read_env(tf_ctx* c)
     c->vis_fault_launch = tf_env_count("TFUSION_VIS_FAULT");
     c->fuse_tail = tf_env_flag("TFUSION_FUSE_TAIL", 1);
     c->ckpt_chunk_blocks = tf_env_int("TFUSION_CKPT_CHUNK_BLOCKS", TF_CKPT_CHUNK_BLOCKS, 1, 1 << 18, TF_CKPT_CHUNK_BLOCKS);
+    c->mesh_chunk_bytes = tf_env_int("TFUSION_MESH_CHUNK_BYTES", TF_MESH_CHUNK_BYTES, 24, 1 << 30, TF_MESH_CHUNK_BYTES);
     c->ckpt_timing = tf_env_flag("TFUSION_CKPT_TIMING", 0);
     c->percall_early = tf_env_flag("TFUSION_PERCALL_EARLY", 1);
     c->percall_defer = tf_env_flag("TFUSION_PERCALL_DEFER", 1);

@@ -475,6 +475,15 @@ struct tf_ctx {
     unsigned* meshWPre;                  // [n_blocks][112]
     long long* meshVCount;               // [n_total] counts, then one total per 512-entry group
     long long* meshVBase;                // [n_total + 1]
+    // ... of the whole reading (tf_mesh_extract_indexed_whole): the slot of every hash entry (its rank among the
+    // entries that resolve, -1 otherwise), and the edge bits and prefixes per slot -- 896 B per resolving entry,
+    // grown when an extraction finds more of them than meshSlotCap; the pinned chunk of the streaming save
+    int* meshSlot;                       // [n_total] slots, then one count per 512-entry group, then the total
+    unsigned* meshSlotMask;              // [meshSlotCap][112]
+    unsigned* meshSlotWPre;              // [meshSlotCap][112]
+    long long meshSlotCap;
+    int mesh_chunk_bytes;                // TFUSION_MESH_CHUNK_BYTES; default TF_MESH_CHUNK_BYTES
+    unsigned char* meshPinned;           // [mesh_chunk_bytes], allocated by the first tf_mesh_save_ply_indexed_whole
     // scene checkpoints (tf_scene_ckpt.hip): per 256-entry group its (records, stored blocks) counts, then their
     // exclusive bases + the totals, then a flag; the bounded block staging buffer and its pinned twin;
     // allocated by the first save / load
@@ -489,6 +498,7 @@ struct tf_ctx {
 // the registry's status (tf_ctx_mem.h: the allocator's own code, unchanged) as the HIP error it is
 static inline hipError_t tf_mem_hip(int e) { return (hipError_t)e; }
 #define TF_CKPT_CHUNK_BLOCKS 4096        // 8 MiB of voxels (16 MiB with colour) per chunk, whatever n_blocks is
+#define TF_MESH_CHUNK_BYTES (8 << 20)    // the streaming PLY save's pinned chunk: 8 MiB, whatever the mesh is
 #define TF_VERDICT_WORDS 16
 
 // the launch of a stage's single kernel: timed by the dispatch's own timestamps when the

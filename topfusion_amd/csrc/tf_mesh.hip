@@ -33,7 +33,10 @@
 //                          the vertex base + prefix + popcount below
 //   k_mesh_emit_indices  : k_mesh_emit's structure; a triangle vertex (lo, hi) -> owner block, bit, index
 //
-// The indexed form keys its edge bits by VBA block, which a stored block does not have: it stays resident-only.
+// The indexed form's four kernels exist in both readings too, and differ in one thing: the row of a block's edge
+// words.  The resident one keys them by VBA block (MeshKeyBlock); a stored block has none, so the whole one
+// (tf_mesh_extract_indexed_whole) keys them by slot, the entry's rank among the entries that resolve
+// (MeshKeySlot; k_mesh_slot_count + k_mesh_slot_assign number them per extraction), in a scratch of its own.
 //
 // No workgroup waits on another inside a grid.  The scene (hash, VBA, block grid) and the GlobalCache are only read.
 #include "tf_mesh_dev.h"
@@ -244,25 +247,104 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_attr(Scene s, const unsign
 }
 
 // ---- the indexed form -------------------------------------------------------------------------------------
+// Where a block's TFM_EDGE_WORDS edge words lie in the mask and prefix arrays -- the one thing the two readings'
+// indexed kernels differ in.  key(b), b = (hash entry, VBA voxel offset) of a block as mesh_stage's hook sees it,
+// is the block's row there, or -1 for a block that owns nothing (missing, or outside the scratch).
+// Resident: the VBA block number.  Whole: the entry's slot, its rank among the entries that resolve
+// (k_mesh_slot_count / k_mesh_slot_assign below), so the scratch is as large as the map and no larger.
+struct MeshKeyBlock {
+    int n_blocks;
+    __device__ __forceinline__ int operator()(int2 b) const { return b.y >= 0 && (b.y >> 9) < n_blocks ? b.y >> 9 : -1; }
+};
+struct MeshKeySlot {
+    const int* slot;             // [n_total]
+    __device__ __forceinline__ int operator()(int2 b) const { return b.x >= 0 ? slot[b.x] : -1; }
+};
+
+// The slot numbering: slot[ei] = the number of resolving entries below ei where ei resolves, else -1; the
+// total behind the group counts.  An exclusive scan of a 0 / 1 predicate in 32 bits, in two launches (no
+// workgroup waits on another): each 512-entry group's count, then per group the sum of the lower groups'
+// counts (read, written by the launch before) plus the rank inside the group by wave ballots.
+__global__ __launch_bounds__(TFM_WG) void k_mesh_slot_count(MeshSceneWhole s, int* __restrict__ gcount)
+{
+    __shared__ int wsum[TFM_WG / 64];
+    const int t = threadIdx.x;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int idx = g * TFM_WG + t;
+        const bool r = idx < s.n_total && mesh_entry_resolves(s, idx);
+        const int c = __popcll(__ballot(r));
+        __syncthreads();             // the previous group's reads of wsum
+        if ((t & 63) == 0) wsum[t >> 6] = c;
+        __syncthreads();
+        if (t == 0) {
+            int sum = 0;
+            for (int w = 0; w < TFM_WG / 64; ++w) sum += wsum[w];
+            gcount[g] = sum;
+        }
+    }
+}
+
+__global__ __launch_bounds__(TFM_WG) void k_mesh_slot_assign(MeshSceneWhole s, const int* __restrict__ gcount, int* __restrict__ slot,
+                                                             int* __restrict__ total)
+{
+    __shared__ int wsum[TFM_WG / 64];
+    __shared__ int red[TFM_WG / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        int below = 0;
+        for (int i = t; i < g; i += TFM_WG) below += gcount[i];
+        below = wave_sum(below);
+        const int idx = g * TFM_WG + t;
+        const bool r = idx < s.n_total && mesh_entry_resolves(s, idx);
+        const unsigned long long bal = __ballot(r);
+        __syncthreads();             // the previous group's reads of wsum / red
+        if (lane == 0) { wsum[wave] = __popcll(bal); red[wave] = below; }
+        __syncthreads();
+        int base = 0, mine = 0;
+        for (int w = 0; w < TFM_WG / 64; ++w) { base += red[w]; mine += w < wave ? wsum[w] : 0; }
+        if (idx < s.n_total) slot[idx] = r ? base + mine + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+        if (g == ngroups - 1 && t == 0) {
+            int sum = base;
+            for (int w = 0; w < TFM_WG / 64; ++w) sum += wsum[w];
+            *total = sum;
+        }
+    }
+}
+
 struct MeshMarker {
     unsigned* lmask;             // LDS, [8][TFM_EDGE_WORDS]
     __device__ __forceinline__ void operator()(const TfmEdgeRef& r) { atomicOr(&lmask[r.owner * TFM_EDGE_WORDS + (r.bit >> 5)], 1u << (r.bit & 31u)); }
 };
 
-__global__ __launch_bounds__(TFM_WG) void k_mesh_mark(MeshScene s, unsigned* __restrict__ mask, int n_blocks)
+// mesh_stage's hook of the mark pass: the eight blocks' rows in the mask
+template <class Key>
+struct MeshKeyStage {
+    Key key;
+    int* nkey;                   // LDS, [8]
+    __device__ __forceinline__ void operator()(int t, int2 b) const
+    {
+        if (t < 8) nkey[t] = key(b);
+    }
+};
+
+template <class Scene, class Key>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_mark(Scene s, Key key, unsigned* __restrict__ mask)
 {
     __shared__ unsigned tile[TFM_TILE3];
-    __shared__ int nvoff[8];
+    __shared__ int nvoff[TFM_NVOFF(Scene, 8)];
+    __shared__ int nkey[8];
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
     __shared__ unsigned lmask[8 * TFM_EDGE_WORDS];
     const int t = threadIdx.x;
     const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasBlock{ s.v.hash, nullptr });    // (any order: OR commutes)
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, mesh_has_block(s, nullptr));    // (any order: OR commutes)
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
-            mesh_stage(s, ei, s.v.hash[ei], tile, nvoff);        // (its leading barrier: the previous entry's flush is done)
+            mesh_stage(s, ei, s.v.hash[ei], tile, nvoff, MeshKeyStage<Key>{ key, nkey });        // (its leading barrier: the previous entry's flush is done)
             for (int i = t; i < 8 * TFM_EDGE_WORDS; i += TFM_WG) lmask[i] = 0u;
             __syncthreads();
             MeshMarker mk = { lmask };
@@ -271,9 +353,9 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_mark(MeshScene s, unsigned* __r
             for (int i = t; i < 8 * TFM_EDGE_WORDS; i += TFM_WG) {
                 const unsigned w = lmask[i];
                 if (w) {
-                    // the owner holds a corner of a valid cube (w > 0), so its block exists; the guards only bound the store
-                    const int o = i / TFM_EDGE_WORDS, blk = nvoff[o] >> 9;
-                    if (nvoff[o] >= 0 && blk < n_blocks) atomicOr(&mask[(size_t)blk * TFM_EDGE_WORDS + (i - o * TFM_EDGE_WORDS)], w);
+                    // the owner holds a corner of a valid cube (w > 0), so its block exists; the guard only bounds the store
+                    const int o = i / TFM_EDGE_WORDS, row = nkey[o];
+                    if (row >= 0) atomicOr(&mask[(size_t)row * TFM_EDGE_WORDS + (i - o * TFM_EDGE_WORDS)], w);
                 }
             }
         }
@@ -282,7 +364,8 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_mark(MeshScene s, unsigned* __r
 
 // Per live entry (one wave each) the exclusive popcount prefix of its block's mask words and its vertex
 // count; dead entries count 0; each 512-entry group's total beside, as k_mesh_count leaves them.
-__global__ __launch_bounds__(TFM_WG) void k_mesh_vcount(MeshScene s, const unsigned* __restrict__ mask, unsigned* __restrict__ wpre, int n_blocks,
+template <class Scene, class Key>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_vcount(Scene s, Key key, const unsigned* __restrict__ mask, unsigned* __restrict__ wpre,
                                                         long long* __restrict__ count, long long* __restrict__ groupTot)
 {
     __shared__ int live[TFM_WG];
@@ -292,13 +375,13 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_vcount(MeshScene s, const unsig
     const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         if (t == 0) gsum = 0;            // (thread 0 read the previous group's sum itself; the list's barriers stand before the adds)
-        const int n = mesh_live_list(g, s.n_total, live, &nlive, MeshHasBlock{ s.v.hash, count });
+        const int n = mesh_live_list(g, s.n_total, live, &nlive, mesh_has_block(s, count));
         for (int k = wave; k < n; k += TFM_WG / 64) {
             const int ei = live[k];
-            const int blk = s.v.hash[ei].ptr;
+            const int row = key(make_int2(ei, s.v.hash[ei].ptr * TF_BLK3));
             int total = 0;
-            if (blk < n_blocks) {
-                const size_t at = (size_t)blk * TFM_EDGE_WORDS;
+            if (row >= 0) {
+                const size_t at = (size_t)row * TFM_EDGE_WORDS;
                 const int ca = __popc(mask[at + lane]);
                 const int cb = lane < TFM_EDGE_WORDS - 64 ? __popc(mask[at + 64 + lane]) : 0;
                 const int ia = mesh_wave_scan(ca), ib = mesh_wave_scan(cb);
@@ -319,8 +402,8 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_vcount(MeshScene s, const unsig
 
 // The vertex table: positions (may be nullptr), normals, colours (one RGBA word per vertex), each clipped
 // at `capacity` vertices.  The tile is the attributed kernel's; a block's vertices are contiguous.
-template <bool NORMALS, bool COLOURS>
-__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(MeshScene s, const unsigned* __restrict__ rgb, const unsigned* __restrict__ mask,
+template <bool NORMALS, bool COLOURS, class Scene, class Key>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(Scene s, Key key, const unsigned* __restrict__ rgb, const unsigned* __restrict__ mask,
                                                                const unsigned* __restrict__ wpre, const long long* __restrict__ vcount,
                                                                const long long* __restrict__ vbase, float* __restrict__ outPos,
                                                                float* __restrict__ outNrm, unsigned* __restrict__ outCol, long long capacity,
@@ -329,7 +412,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(MeshScene s, cons
     __shared__ unsigned tile[TFM_ATILE3];
     __shared__ int grad3[NORMALS ? 3 * TFM_TILE3 : 1];
     __shared__ unsigned ctile[COLOURS ? TFM_TILE3 : 1];
-    __shared__ int nvoff[27];
+    __shared__ int nvoff[TFM_NVOFF(Scene, 27)];
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
     __shared__ unsigned lm[TFM_EDGE_WORDS + 1], lpre[TFM_EDGE_WORDS];
@@ -342,9 +425,10 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(MeshScene s, cons
             const int ei = live[k];
             const TfHashEntry e = s.v.hash[ei];
             mesh_stage_attr<NORMALS, COLOURS>(s, rgb, ei, e, tile, ctile, nvoff);
-            if (t < TFM_EDGE_WORDS) {                // (vcount > 0: the entry is live and its block below n_blocks)
-                lm[t] = mask[(size_t)e.ptr * TFM_EDGE_WORDS + t];
-                lpre[t] = wpre[(size_t)e.ptr * TFM_EDGE_WORDS + t];
+            if (t < TFM_EDGE_WORDS) {                // (vcount > 0: the entry is live and has a row, k_mesh_vcount)
+                const size_t own = (size_t)key(make_int2(ei, e.ptr * TF_BLK3)) * TFM_EDGE_WORDS;
+                lm[t] = mask[own + t];
+                lpre[t] = wpre[own + t];
             }
             if (NORMALS) mesh_grad_fill(tile, grad3);
             __syncthreads();         // the mask words, and the gradients
@@ -389,7 +473,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_vertices(MeshScene s, cons
 struct MeshIndexWriter {
     const unsigned* lm;          // LDS: the entry's own mask words and prefixes
     const unsigned* lpre;
-    const int* nvoff;            // LDS: the eight blocks' voxel offsets
+    const int* nkey;             // LDS: the eight blocks' rows in the mask
     const long long* nbase;      // LDS: ... and their entries' vertex bases
     const unsigned* mask;
     const unsigned* wpre;
@@ -408,8 +492,8 @@ struct MeshIndexWriter {
                 unsigned m = 0u, pre = 0u;
                 if (r.owner == 0u) {
                     m = lm[w]; pre = lpre[w];
-                } else if (nvoff[r.owner] >= 0) {        // (always: the owner holds a corner of this valid cube)
-                    const size_t at = (size_t)(nvoff[r.owner] >> 9) * TFM_EDGE_WORDS + w;
+                } else if (nkey[r.owner] >= 0) {         // (always: the owner holds a corner of this valid cube)
+                    const size_t at = (size_t)nkey[r.owner] * TFM_EDGE_WORDS + w;
                     m = mask[at]; pre = wpre[at];
                 }
                 tri[v] = (unsigned)(nbase[r.owner] + tfm_edge_rank(m, pre, r.bit));
@@ -420,18 +504,25 @@ struct MeshIndexWriter {
     }
 };
 
-// mesh_stage's hook of k_mesh_emit_indices: the eight blocks' entries give their vertex bases (a missing
-// block owns nothing), and threads 64 .. 175 bring the entry's own mask words and prefixes
+// mesh_stage's hook of k_mesh_emit_indices: the eight blocks' rows in the mask and their entries' vertex
+// bases (a missing block owns nothing), and threads 64 .. 175 bring the entry's own mask words and prefixes
+template <class Key>
 struct MeshIndexStage {
+    Key key;
     const long long* vbase;
     const unsigned* mask;        // the entry's block's words
     const unsigned* wpre;
-    long long* nbase;            // LDS
+    int* nkey;                   // LDS
+    long long* nbase;
     unsigned* lm;
     unsigned* lpre;
     __device__ __forceinline__ void operator()(int t, int2 b) const
     {
-        if (t < 8) nbase[t] = b.y >= 0 ? vbase[b.x] : 0;
+        if (t < 8) {
+            const int row = key(b);
+            nkey[t] = row;
+            nbase[t] = row >= 0 ? vbase[b.x] : 0;
+        }
         if (t >= 64 && t < 64 + TFM_EDGE_WORDS) {
             lm[t - 64] = mask[t - 64];
             lpre[t - 64] = wpre[t - 64];
@@ -439,12 +530,14 @@ struct MeshIndexStage {
     }
 };
 
-__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_indices(MeshScene s, const unsigned* __restrict__ mask, const unsigned* __restrict__ wpre,
+template <class Scene, class Key>
+__global__ __launch_bounds__(TFM_WG) void k_mesh_emit_indices(Scene s, Key key, const unsigned* __restrict__ mask, const unsigned* __restrict__ wpre,
                                                               const long long* __restrict__ count, const long long* __restrict__ base,
                                                               const long long* __restrict__ vbase, unsigned* __restrict__ out, long long capacity)
 {
     __shared__ unsigned tile[TFM_TILE3];
-    __shared__ int nvoff[8];
+    __shared__ int nvoff[TFM_NVOFF(Scene, 8)];
+    __shared__ int nkey[8];
     __shared__ long long nbase[8];
     __shared__ int live[TFM_WG];
     __shared__ int nlive;
@@ -457,13 +550,15 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_emit_indices(MeshScene s, const
         for (int k = 0; k < n; ++k) {
             const int ei = live[k];
             const TfHashEntry e = s.v.hash[ei];
-            const size_t own = (size_t)e.ptr * TFM_EDGE_WORDS;
-            mesh_stage(s, ei, e, tile, nvoff, MeshIndexStage{ vbase, mask + own, wpre + own, nbase, lm, lpre });
+            // (count > 0: a valid cube of the entry's own, so it is live and has a row unless its block lies outside the scratch)
+            const int row = key(make_int2(ei, e.ptr * TF_BLK3));
+            const size_t own = (size_t)(row < 0 ? 0 : row) * TFM_EDGE_WORDS;
+            mesh_stage(s, ei, e, tile, nvoff, MeshIndexStage<Key>{ key, vbase, mask + own, wpre + own, nkey, nbase, lm, lpre });
             const TfmCube q = mesh_cube<TFM_TILE, 0>(tile);
             const int mine = tfm_cube_count(q);
             const int off = mesh_scan(mine, wsum);
             if (mine) {
-                MeshIndexWriter wr = { lm, lpre, nvoff, nbase, mask, wpre, out, t & 7, t >> 3 & 7, t >> 6, base[ei] + off, capacity };
+                MeshIndexWriter wr = { lm, lpre, nkey, nbase, mask, wpre, out, t & 7, t >> 3 & 7, t >> 6, base[ei] + off, capacity };
                 tfm_cube_emit_edges(q, wr);
             }
         }
@@ -530,6 +625,26 @@ static hipError_t tfk_mesh_emit_attr(tf_ctx* c, float* triangles, float* normals
     return hipGetLastError();
 }
 
+// The vertex counts and bases per hash entry (both readings'), the context's from the first indexed call on
+static hipError_t mesh_vcount_scratch(tf_ctx* c)
+{
+    if (c->meshVCount) return hipSuccess;
+    const size_t counts = sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c));
+    return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->meshVCount, counts),
+                                           TfCtxMem::dev(&c->meshVBase, sizeof(long long) * ((size_t)c->n_total + 1)) }));
+}
+
+// mark, count and the vertex prefix over masks already cleared
+template <class Scene, class Key>
+static hipError_t mesh_mark_count(tf_ctx* c, const Scene& s, Key key, unsigned* mask, unsigned* wpre)
+{
+    long long* groupTot = c->meshVCount + c->n_total;
+    hipLaunchKernelGGL((k_mesh_mark<Scene, Key>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, s, key, mask);
+    hipLaunchKernelGGL((k_mesh_vcount<Scene, Key>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, s, key, mask, wpre, c->meshVCount, groupTot);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? mesh_prefix(c, c->meshVCount, groupTot, c->meshVBase) : e;
+}
+
 // Triangle count + prefix (tfk_mesh_count), then the edge masks cleared (blocks are freed and reused: a
 // stale mask is a wrong mesh), marked and counted, and the vertex prefix: the totals land in
 // meshBase[n_total] and meshVBase[n_total].  The scratch is the context's from the first call on.
@@ -538,40 +653,83 @@ static hipError_t tfk_mesh_index_count(tf_ctx* c)
     hipError_t e = tfk_mesh_count(c);
     if (e != hipSuccess) return e;
     const size_t words = (size_t)c->p.n_blocks * TFM_EDGE_WORDS;
+    if ((e = mesh_vcount_scratch(c)) != hipSuccess) return e;
     if (!c->meshMask) {
-        const size_t counts = sizeof(long long) * ((size_t)c->n_total + (size_t)mesh_groups(c));
-        e = tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->meshMask, sizeof(unsigned) * words), TfCtxMem::dev(&c->meshWPre, sizeof(unsigned) * words),
-                                            TfCtxMem::dev(&c->meshVCount, counts),
-                                            TfCtxMem::dev(&c->meshVBase, sizeof(long long) * ((size_t)c->n_total + 1)) }));
+        e = tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->meshMask, sizeof(unsigned) * words), TfCtxMem::dev(&c->meshWPre, sizeof(unsigned) * words) }));
         if (e != hipSuccess) return e;
     }
     e = hipMemsetAsync(c->meshMask, 0, sizeof(unsigned) * words, c->stream);
     if (e != hipSuccess) return e;
-    long long* groupTot = c->meshVCount + c->n_total;
-    hipLaunchKernelGGL(k_mesh_mark, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->p.n_blocks);
-    hipLaunchKernelGGL(k_mesh_vcount, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->meshWPre, c->p.n_blocks,
-                       c->meshVCount, groupTot);
-    e = hipGetLastError();
-    return e == hipSuccess ? mesh_prefix(c, c->meshVCount, groupTot, c->meshVBase) : e;
+    return mesh_mark_count(c, mesh_scene(c), MeshKeyBlock{ c->p.n_blocks }, c->meshMask, c->meshWPre);
 }
 
-// after tfk_mesh_index_count on the same stream: the vertex table's columns (each may be nullptr, one at
-// least is not; colours need the colour plane), clipped at the same capacity
-static hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity)
+// ... of the whole reading (a swapping context with a GlobalCache).  The entries that resolve are numbered
+// first, and their number R comes to the host (one wait): the edge masks and prefixes are R rows of
+// TFM_EDGE_WORDS words, a scratch of their own beside the resident form's, grown geometrically when R
+// exceeds what is held and cleared every time, since the slots are numbered anew by every extraction.
+static hipError_t tfk_mesh_index_count_whole(tf_ctx* c)
 {
-    mesh_dispatch_attr(normals != nullptr, colours != nullptr, [&](auto N, auto C) {
-        hipLaunchKernelGGL((k_mesh_emit_vertices<N(), C()>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->vba_rgb_guard, c->meshMask,
-                           c->meshWPre, c->meshVCount, c->meshVBase, vertices, normals, reinterpret_cast<unsigned*>(colours), capacity,
-                           c->p.voxelSize);
+    hipError_t e = tfk_mesh_count(c, true);
+    if (e != hipSuccess) return e;
+    if ((e = mesh_vcount_scratch(c)) != hipSuccess) return e;
+    const int ng = mesh_groups(c);
+    if (!c->meshSlot) {
+        e = tf_mem_hip(c->mem.alloc(&c->meshSlot, sizeof(int) * ((size_t)c->n_total + (size_t)ng + 1)));
+        if (e != hipSuccess) return e;
+    }
+    const MeshSceneWhole s = mesh_scene_whole(c);
+    int* gcount = c->meshSlot + c->n_total;
+    hipLaunchKernelGGL(k_mesh_slot_count, mesh_grid(c), dim3(TFM_WG), 0, c->stream, s, gcount);
+    hipLaunchKernelGGL(k_mesh_slot_assign, mesh_grid(c), dim3(TFM_WG), 0, c->stream, s, gcount, c->meshSlot, gcount + ng);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    int R = 0;
+    e = hipMemcpyAsync(&R, gcount + ng, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    const long long need = R < 1 ? 1 : R;
+    if (need > c->meshSlotCap) {
+        const long long cap = need > 2 * c->meshSlotCap ? need : 2 * c->meshSlotCap;
+        (void)c->mem.release(c->meshSlotMask);
+        (void)c->mem.release(c->meshSlotWPre);
+        c->meshSlotCap = 0;
+        const size_t bytes = sizeof(unsigned) * TFM_EDGE_WORDS * (size_t)cap;
+        e = tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->meshSlotMask, bytes), TfCtxMem::dev(&c->meshSlotWPre, bytes) }));
+        if (e != hipSuccess) return e;
+        c->meshSlotCap = cap;
+    }
+    e = hipMemsetAsync(c->meshSlotMask, 0, sizeof(unsigned) * TFM_EDGE_WORDS * (size_t)need, c->stream);
+    if (e != hipSuccess) return e;
+    return mesh_mark_count(c, s, MeshKeySlot{ c->meshSlot }, c->meshSlotMask, c->meshSlotWPre);
+}
+
+// after tfk_mesh_index_count[_whole] on the same stream: the vertex table's columns (each may be nullptr, one at
+// least is not; colours need the colour plane and the resident reading), clipped at the same capacity
+static hipError_t tfk_mesh_emit_vertices(tf_ctx* c, float* vertices, float* normals, unsigned char* colours, long long capacity, bool whole = false)
+{
+    mesh_dispatch_attr(normals != nullptr, colours != nullptr && !whole, [&](auto N, auto C) {
+        if (whole) {
+            if constexpr (!C())
+                hipLaunchKernelGGL((k_mesh_emit_vertices<N(), false, MeshSceneWhole, MeshKeySlot>), mesh_grid(c), dim3(TFM_WG), 0, c->stream,
+                                   mesh_scene_whole(c), MeshKeySlot{ c->meshSlot }, nullptr, c->meshSlotMask, c->meshSlotWPre, c->meshVCount,
+                                   c->meshVBase, vertices, normals, nullptr, capacity, c->p.voxelSize);
+        } else {
+            hipLaunchKernelGGL((k_mesh_emit_vertices<N(), C(), MeshScene, MeshKeyBlock>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c),
+                               MeshKeyBlock{ c->p.n_blocks }, c->vba_rgb_guard, c->meshMask, c->meshWPre, c->meshVCount, c->meshVBase, vertices,
+                               normals, reinterpret_cast<unsigned*>(colours), capacity, c->p.voxelSize);
+        }
     });
     return hipGetLastError();
 }
 
-// after tfk_mesh_index_count on the same stream: three vertex numbers per triangle, the first `capacity` triangles
-static hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity)
+// after tfk_mesh_index_count[_whole] on the same stream: three vertex numbers per triangle, the first `capacity` triangles
+static hipError_t tfk_mesh_emit_indices(tf_ctx* c, unsigned* indices, long long capacity, bool whole = false)
 {
-    hipLaunchKernelGGL(k_mesh_emit_indices, mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c), c->meshMask, c->meshWPre, c->meshCount,
-                       c->meshBase, c->meshVBase, indices, capacity);
+    if (whole)
+        hipLaunchKernelGGL((k_mesh_emit_indices<MeshSceneWhole, MeshKeySlot>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene_whole(c),
+                           MeshKeySlot{ c->meshSlot }, c->meshSlotMask, c->meshSlotWPre, c->meshCount, c->meshBase, c->meshVBase, indices, capacity);
+    else
+        hipLaunchKernelGGL((k_mesh_emit_indices<MeshScene, MeshKeyBlock>), mesh_grid(c), dim3(TFM_WG), 0, c->stream, mesh_scene(c),
+                           MeshKeyBlock{ c->p.n_blocks }, c->meshMask, c->meshWPre, c->meshCount, c->meshBase, c->meshVBase, indices, capacity);
     return hipGetLastError();
 }
 
@@ -691,14 +849,39 @@ extern "C" tf_status tf_mesh_save_ply_attr(tf_ctx* c, const char* path, int attr
 }
 
 // ---- indexed mesh extraction (additions; DESIGN.md §Mesh extraction, indexed) ---------------------------
-// triangle and vertex totals after the count passes
-static tf_status mesh_index_count(tf_ctx* c, long long* nv, long long* nt)
+// triangle and vertex totals after the count passes.  whole: the reading over both tiers, by the slot-keyed
+// kernels where the context has a GlobalCache and by the resident ones where it has none
+static tf_status mesh_index_count(tf_ctx* c, long long* nv, long long* nt, bool whole = false)
 {
-    const hipError_t e = tfk_mesh_index_count(c);
+    const hipError_t e = mesh_reads_store(c, whole) ? tfk_mesh_index_count_whole(c) : tfk_mesh_index_count(c);
     if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return TF_OOM; }
     TF_CHECK(e);
     TF_CHECK(hipMemcpyAsync(nt, c->meshBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     TF_CHECK(hipMemcpyAsync(nv, c->meshVBase + c->n_total, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    return sync_checked(c);
+}
+
+// tf_mesh_extract_indexed and tf_mesh_extract_indexed_whole (no colours), after the flush
+static tf_status mesh_extract_indexed(tf_ctx* c, float* dev_vertices, float* dev_normals, uint8_t* dev_colours, long long vertex_capacity,
+                                      uint32_t* dev_indices, long long triangle_capacity, long long* n_vertices, long long* n_triangles,
+                                      bool whole = false)
+{
+    const bool any = dev_vertices || dev_normals || dev_colours;
+    if (!c || !n_vertices || !n_triangles || vertex_capacity < 0 || triangle_capacity < 0) return TF_INVALID_ARG;
+    if ((vertex_capacity > 0 && !any) || (triangle_capacity > 0 && !dev_indices)) return TF_INVALID_ARG;
+    if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    long long nv = 0, nt = 0;
+    tf_status s = mesh_index_count(c, &nv, &nt, whole);
+    if (s != TF_OK) return s;
+    *n_vertices = nv;
+    *n_triangles = nt;
+    if (nv > 0xffffffffLL) return TF_INDEX_RANGE;
+    const bool verts = any && vertex_capacity > 0 && nv > 0, tris = dev_indices && triangle_capacity > 0 && nt > 0;
+    if (!verts && !tris) return TF_OK;
+    const bool store = mesh_reads_store(c, whole);
+    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
+    if (verts) TF_CHECK(tfk_mesh_emit_vertices(c, dev_vertices, dev_normals, dev_colours, vertex_capacity, store));
+    if (tris) TF_CHECK(tfk_mesh_emit_indices(c, dev_indices, triangle_capacity, store));
     return sync_checked(c);
 }
 
@@ -707,22 +890,69 @@ extern "C" tf_status tf_mesh_extract_indexed(tf_ctx* c, float* dev_vertices, flo
                                              long long* n_vertices, long long* n_triangles)
 {
     TF_FLUSH(c);
-    const bool any = dev_vertices || dev_normals || dev_colours;
-    if (!c || !n_vertices || !n_triangles || vertex_capacity < 0 || triangle_capacity < 0) return TF_INVALID_ARG;
-    if ((vertex_capacity > 0 && !any) || (triangle_capacity > 0 && !dev_indices)) return TF_INVALID_ARG;
-    if (dev_colours && !c->p.voxel_rgb) return TF_INVALID_ARG;
+    return mesh_extract_indexed(c, dev_vertices, dev_normals, dev_colours, vertex_capacity, dev_indices, triangle_capacity, n_vertices, n_triangles);
+}
+
+extern "C" tf_status tf_mesh_extract_indexed_whole(tf_ctx* c, float* dev_vertices, float* dev_normals, long long vertex_capacity,
+                                                   uint32_t* dev_indices, long long triangle_capacity, long long* n_vertices,
+                                                   long long* n_triangles)
+{
+    TF_FLUSH(c);
+    return mesh_extract_indexed(c, dev_vertices, dev_normals, nullptr, vertex_capacity, dev_indices, triangle_capacity, n_vertices, n_triangles,
+                                true);
+}
+
+// The whole map as an indexed PLY in bounded pieces.  The device holds the columns (positions, normals,
+// indices: a quarter to a third of the soup's bytes); they come to the host through a pinned staging buffer of
+// mesh_chunk_bytes (TFUSION_MESH_CHUNK_BYTES), the context's from the first call on, a chunk of vertices
+// (position and normal rows side by side) or of faces at a time, and the streaming writer (tf_mesh_ply.cpp)
+// interleaves each chunk into the file's records.  Host memory is the chunk, whatever the mesh.
+extern "C" tf_status tf_mesh_save_ply_indexed_whole(tf_ctx* c, const char* path, int attrs)
+{
+    TF_FLUSH(c);
+    if (!c || !path || (attrs & ~TF_MESH_NORMALS)) return TF_INVALID_ARG;
     long long nv = 0, nt = 0;
-    tf_status s = mesh_index_count(c, &nv, &nt);
+    tf_status s = mesh_index_count(c, &nv, &nt, true);
     if (s != TF_OK) return s;
-    *n_vertices = nv;
-    *n_triangles = nt;
-    if (nv > 0xffffffffLL) return TF_INDEX_RANGE;
-    const bool verts = any && vertex_capacity > 0 && nv > 0, tris = dev_indices && triangle_capacity > 0 && nt > 0;
-    if (!verts && !tris) return TF_OK;
-    TF_CHECK(order_after_caller(c));                      // the caller may still use the buffers on stream 0
-    if (verts) TF_CHECK(tfk_mesh_emit_vertices(c, dev_vertices, dev_normals, dev_colours, vertex_capacity));
-    if (tris) TF_CHECK(tfk_mesh_emit_indices(c, dev_indices, triangle_capacity));
-    return sync_checked(c);
+    if (nv > 0x7fffffffLL) return TF_INDEX_RANGE;       // (the PLY's indices are int)
+    const bool nrm = attrs & TF_MESH_NORMALS, store = mesh_reads_store(c, true);
+    if (nt == 0) nv = 0;                                 // (no vertex is unreferenced)
+    if (!c->meshPinned) {
+        const hipError_t e = tf_mem_hip(c->mem.alloc(TfCtxMem::pin(&c->meshPinned, (size_t)c->mesh_chunk_bytes, hipHostMallocDefault)));
+        if (e != hipSuccess) { (void)hipGetLastError(); return TF_OOM; }
+    }
+    const size_t bp = 12 * (size_t)nv, bn = nrm ? bp : 0, bi = 12 * (size_t)nt;
+    char* dev = nullptr;
+    TfCtxMem tmp(c->mem.fns());                         // the device columns, freed when this returns
+    if (nt > 0) {
+        if (tmp.alloc(&dev, bp + bn + bi) != 0) { (void)hipGetLastError(); return TF_OOM; }
+        TF_CHECK(tfk_mesh_emit_vertices(c, (float*)dev, nrm ? (float*)(dev + bp) : nullptr, nullptr, nv, store));
+        TF_CHECK(tfk_mesh_emit_indices(c, (unsigned*)(dev + bp + bn), nt, store));
+    }
+    tf_ply_stream* ps = nullptr;
+    s = tf_mesh_ply_begin(path, nv, nt, attrs, &ps);
+    if (s != TF_OK) { (void)sync_checked(c); return s; }
+    unsigned char* pin = c->meshPinned;
+    const long long vrows = c->mesh_chunk_bytes / (nrm ? 24 : 12), frows = c->mesh_chunk_bytes / 12;
+    hipError_t e = hipSuccess;
+    for (long long v0 = 0; v0 < nv && s == TF_OK && e == hipSuccess; v0 += vrows) {
+        const long long k = nv - v0 < vrows ? nv - v0 : vrows;
+        e = hipMemcpyAsync(pin, dev + 12 * v0, 12 * (size_t)k, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && nrm) e = hipMemcpyAsync(pin + 12 * k, dev + bp + 12 * v0, 12 * (size_t)k, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) s = tf_mesh_ply_vertices(ps, (const float*)pin, nrm ? (const float*)(pin + 12 * k) : nullptr, nullptr, k);
+    }
+    for (long long t0 = 0; t0 < nt && s == TF_OK && e == hipSuccess; t0 += frows) {
+        const long long k = nt - t0 < frows ? nt - t0 : frows;
+        e = hipMemcpyAsync(pin, dev + bp + bn + 12 * t0, 12 * (size_t)k, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) s = tf_mesh_ply_faces(ps, (const uint32_t*)pin, k);
+    }
+    if (s == TF_OK && e != hipSuccess) s = tf_from_hip(e);
+    const tf_status s2 = sync_checked(c);               // (the stream is idle before the device buffer goes)
+    if (s == TF_OK) s = s2;
+    const tf_status s3 = tf_mesh_ply_end(ps, s == TF_OK);     // (a failure so far: the file is removed)
+    return s == TF_OK ? s3 : s;
 }
 
 extern "C" tf_status tf_mesh_save_ply_indexed(tf_ctx* c, const char* path, int attrs)

@@ -39,10 +39,11 @@ struct MeshSceneWhole {
 
 // A resolved block: where its voxels lie.  act = the VBA voxel offset (ptr * 512) or TF_VOFF_NONE, sto = the
 // GlobalCache voxel offset (entry * 512; tf_create bounds the table so it fits an int) or TFM_STO_NONE.
-// Both: the voxel is CombineVoxelInformation(stored, active); neither: the block is missing.
+// Both: the voxel is CombineVoxelInformation(stored, active); neither: the block is missing.  ent = the hash
+// entry the block was found at (-1: missing) -- what the indexed form keys a block's edge bits by.
 #define TFM_STO_NONE (-1)
 struct MeshBlk {
-    int act, sto;
+    int act, sto, ent;
 };
 
 // The entries of group g that pred(idx) accepts, into live[] (any order); returns their number.  pred
@@ -107,12 +108,14 @@ __device__ __forceinline__ int2 mesh_block_look(const MeshScene& s, int bx, int 
 __device__ __forceinline__ MeshBlk mesh_resolve_entry(const MeshSceneWhole& s, int ei, int ptr)
 {
     const bool stored = s.flags[ei] != 0;
-    MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE };
+    MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE, -1 };
     if (ptr >= 0) {
         d.act = ptr * TF_BLK3;
+        d.ent = ei;
         if (stored && s.state[ei] != 2) d.sto = ei * TF_BLK3;
     } else if (ptr == -1 && stored) {
         d.sto = ei * TF_BLK3;
+        d.ent = ei;
     }
     return d;
 }
@@ -142,7 +145,7 @@ __device__ __forceinline__ int mesh_walk_whole(const MeshSceneWhole& s, int bx, 
 // the cell, so a stored block is never in the grid -- and takes the hash walk, as a block outside the grid does.
 __device__ __forceinline__ MeshBlk mesh_block_resolve(const MeshSceneWhole& s, int bx, int by, int bz)
 {
-    const MeshBlk none = { TF_VOFF_NONE, TFM_STO_NONE };
+    const MeshBlk none = { TF_VOFF_NONE, TFM_STO_NONE, -1 };
     if (tf_grid_in(bx, by, bz)) {
         const int2 b = s.v.grid[tf_grid_cell(bx, by, bz)];
         if (b.x >= 0) return mesh_resolve_entry(s, b.x, b.y >> 9);
@@ -176,7 +179,9 @@ struct MeshNoHook {
 // (entry, voff) as found, so the caller can keep what belongs to the entry, and any thread may fill
 // LDS of the caller's there; the trailing one publishes the tile, nvoff and what the hook wrote.
 // The whole reading: nvoff holds TFM_NVOFF(Scene, 8) ints, the blocks' store offsets behind their active
-// ones, each voxel comes from where its block's descriptor says, and the hook sees (-1, active offset).
+// ones, each voxel comes from where its block's descriptor says, and the hook sees (entry, active offset) --
+// the entry the block resolved at (the grid's on a hit, the walk's otherwise), -1 for a missing block; a block
+// that lies in the GlobalCache alone has an entry and no active offset.
 #define TFM_NVOFF(Scene, n) ((Scene::whole ? 2 : 1) * (n))
 template <class Scene, class Hook = MeshNoHook>
 __device__ __forceinline__ void mesh_stage(const Scene& s, int ei, const TfHashEntry& e, unsigned* tile, int* nvoff, Hook hook = Hook())
@@ -187,7 +192,7 @@ __device__ __forceinline__ void mesh_stage(const Scene& s, int ei, const TfHashE
     if (t < 8) {
         if constexpr (Scene::whole) {
             const MeshBlk d = t == 0 ? mesh_resolve_entry(s, ei, e.ptr) : mesh_block_resolve(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
-            b.y = d.act;
+            b = make_int2(d.ent, d.act);
             nvoff[8 + t] = d.sto;
         } else {
             b = t == 0 ? make_int2(ei, e.ptr * TF_BLK3) : mesh_block_look(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
@@ -252,7 +257,7 @@ __device__ __forceinline__ void mesh_stage_attr(const Scene& s, const unsigned* 
         const int down = (ox < 0) + (oy < 0) + (oz < 0);
         int voff = TF_VOFF_NONE;
         if constexpr (Scene::whole) {
-            MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE };
+            MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE, -1 };
             if (t == 13) d = mesh_resolve_entry(s, ei, e.ptr);
             else if (down <= (NORMALS ? 1 : 0)) d = mesh_block_resolve(s, e.x + ox, e.y + oy, e.z + oz);
             voff = d.act;

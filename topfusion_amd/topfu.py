@@ -504,6 +504,50 @@ class TopFu:
                     hip.hipFree(d)
         return outs[0], outs[3], outs[1], outs[2]
 
+    # the whole reading with shared vertices (tf_mesh_extract_indexed_whole): the edge bits keyed by a compact
+    # numbering of the entries that resolve, so blocks in the GlobalCache own vertices too
+    def mesh_indexed_whole_count(self):
+        """(vertices, triangles) the whole map's indexed mesh has (the count passes alone)."""
+        nv, nt = ctypes.c_longlong(), ctypes.c_longlong()
+        L.check(L.load().tf_mesh_extract_indexed_whole(self._h, None, None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)),
+                "tf_mesh_extract_indexed_whole")
+        return nv.value, nt.value
+
+    def mesh_indexed_whole(self, normals=False):
+        """mesh(whole=True) with shared vertices: (vertices (nv, 3) float32, indices (nt, 3) uint32, normals
+        (nv, 3) float32 or None).  vertices[indices] is mesh(whole=True) bit for bit, normals[indices] are
+        mesh_attr(whole=True)'s.  Without stored data it is mesh_indexed() byte for byte."""
+        nv, nt = self.mesh_indexed_whole_count()
+        outs = [np.empty((nv, 3), np.float32), np.empty((nv, 3), np.float32) if normals else None, np.empty((nt, 3), np.uint32)]
+        if nt == 0:
+            return outs[0], outs[2], outs[1]
+        hip = L.hip_runtime()
+        devs = []
+        try:
+            for o in outs:
+                d = ctypes.c_void_p()
+                if o is not None and hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(max(o.nbytes, 16))) != 0:
+                    raise L.TfError(L.TF_OOM, "hipMalloc (mesh)")
+                devs.append(d)
+            mv, mt = ctypes.c_longlong(), ctypes.c_longlong()
+            L.check(L.load().tf_mesh_extract_indexed_whole(self._h, devs[0], devs[1], nv, devs[2], nt, ctypes.byref(mv),
+                                                           ctypes.byref(mt)), "tf_mesh_extract_indexed_whole")
+            assert (mv.value, mt.value) == (nv, nt), (mv.value, mt.value, nv, nt)
+            for o, d in zip(outs, devs):
+                if o is not None and hip.hipMemcpy(_ptr(o), d, ctypes.c_size_t(o.nbytes), 2) != 0:   # hipMemcpyDeviceToHost
+                    raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (mesh)")
+        finally:
+            for d in devs:
+                if d:
+                    hip.hipFree(d)
+        return outs[0], outs[2], outs[1]
+
+    def save_mesh_indexed_whole(self, path, normals=False):
+        """The whole map's indexed mesh as a binary PLY (tf_mesh_save_ply_indexed_whole): no host weld, and
+        written in bounded pieces -- the host holds one chunk (TFUSION_MESH_CHUNK_BYTES), whatever the map."""
+        L.check(L.load().tf_mesh_save_ply_indexed_whole(self._h, str(path).encode(), L.TF_MESH_NORMALS if normals else 0),
+                "tf_mesh_save_ply_indexed_whole")
+
     def save_mesh(self, path, normals=False, colours=False, indexed=False, whole=False):
         """The mesh as a binary PLY with welded vertices (tf_mesh_save_ply); with normals / colours,
         nx ny nz / red green blue alpha per vertex (tf_mesh_save_ply_attr).  indexed: the vertex table of
