@@ -12,6 +12,8 @@
 //   ... --mesh-indexed : the indexed vertex table as the GPU extracts it, no host weld
 //   ... --load-scene F : resume from the checkpoint F before the first frame (TopFu::loadScene)
 //   ... --save-scene F : write the checkpoint F after the last frame (TopFu::saveScene)
+//   ... --load-scene F --capacity BUCKETS,EXCESS,BLOCKS : resume in tables of these sizes, whatever F was saved
+//                        with (TopFu::loadMapResized: the map is re-hashed on the way in)
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -31,7 +33,7 @@ using namespace tfusion;
 
 int main(int argc, char** argv)
 {
-    std::string pgm, ppm, mesh, load_scene, save_scene;
+    std::string pgm, ppm, mesh, load_scene, save_scene, capacity;
     bool mesh_normals = false, mesh_indexed = false;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
@@ -40,6 +42,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--mesh") && i + 1 < argc) mesh = argv[++i];
         else if (!std::strcmp(argv[i], "--load-scene") && i + 1 < argc) load_scene = argv[++i];
         else if (!std::strcmp(argv[i], "--save-scene") && i + 1 < argc) save_scene = argv[++i];
+        else if (!std::strcmp(argv[i], "--capacity") && i + 1 < argc) capacity = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
         else if (!std::strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
         else pos.push_back(argv[i]);
@@ -67,13 +70,25 @@ int main(int argc, char** argv)
     params.rows = rows;
     const double s = cols / 640.0;
     params.intr = Intr(504.261f * s, 503.905f * s, 352.457f * s, 272.202f * s);
+    if (!capacity.empty() && (std::sscanf(capacity.c_str(), "%d,%d,%d", &params.n_buckets, &params.n_excess, &params.n_blocks) != 3 ||
+                              load_scene.empty())) {
+        std::fprintf(stderr, "--capacity BUCKETS,EXCESS,BLOCKS goes with --load-scene\n");
+        return 1;
+    }
     TopFu::Ptr topfu(new TopFu(params));
     auto scene_line = [](const char* what, const std::string& path) {
         const struct tf_scene_file_info info = TopFu::sceneFileInfo(path);
         std::printf("scene %s %s: %lld records, %lld blocks, %lld bytes\n", what, path.c_str(), info.n_records,
                     info.n_blocks_stored, info.file_bytes);
     };
-    if (!load_scene.empty()) {
+    if (!load_scene.empty() && !capacity.empty()) {
+        struct tf_resize_report rep;
+        topfu->loadMapResized(load_scene, &rep);
+        scene_line("loaded resized from", load_scene);
+        std::printf("resized into %d buckets, %d excess, %d blocks: %lld records carried, %lld dropped, %lld blocks, %lld excess slots, "
+                    "longest chain %d\n", params.n_buckets, params.n_excess, params.n_blocks, rep.records_carried, rep.records_dropped,
+                    rep.blocks, rep.excess_used, rep.longest_chain);
+    } else if (!load_scene.empty()) {
         topfu->loadScene(load_scene);
         scene_line("loaded from", load_scene);
     }

@@ -223,6 +223,14 @@ namespace tfusion
         // useSwapping is from then on the one that saved, bit for bit, through any further engine calls.
         void saveMap(const std::string& path) { tf_engine_check(tf_map_save(ctx_, path.c_str()), "tf_map_save"); }
         void loadMap(const std::string& path) { tf_engine_check(tf_map_load(ctx_, path.c_str()), "tf_map_load"); }
+        // Resized load (addition: tf_map_load_resized): a file saved with other table sizes into this scene -- the
+        // records with a block position are re-hashed as if inserted one by one into a reset table, the others
+        // dropped.  Throws with TF_CAPACITY when the map does not fit (report, when given, says what it needs);
+        // the scene is then as it was.
+        void loadMapResized(const std::string& path, struct tf_resize_report* report = nullptr)
+        {
+            tf_engine_check(tf_map_load_resized(ctx_, path.c_str(), report), "tf_map_load_resized");
+        }
 
     private:
         tf_ctx* ctx_ = nullptr;

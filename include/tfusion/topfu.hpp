@@ -332,11 +332,7 @@ namespace tfusion
         void loadScene(const std::string& path)
         {
             check(tf_scene_load(ctx_, path.c_str()), "tf_scene_load");
-            float rt[12];
-            check(tf_get_pose(ctx_, rt), "tf_get_pose");
-            frame_counter_ = stats().frame_counter;
-            poses_.clear();
-            poses_.push_back(affine_from_rt(rt));
+            after_load();
         }
         static struct tf_scene_file_info sceneFileInfo(const std::string& path)
         {
@@ -352,11 +348,14 @@ namespace tfusion
         void loadMap(const std::string& path)
         {
             check(tf_map_load(ctx_, path.c_str()), "tf_map_load");
-            float rt[12];
-            check(tf_get_pose(ctx_, rt), "tf_get_pose");
-            frame_counter_ = stats().frame_counter;
-            poses_.clear();
-            poses_.push_back(affine_from_rt(rt));
+            after_load();
+        }
+        // Resized load (addition: tf_map_load_resized): a file saved by a TopFu of other n_buckets / n_excess /
+        // n_blocks; the map is re-hashed into this one's tables (records without a block position are dropped).
+        void loadMapResized(const std::string& path, struct tf_resize_report* report = nullptr)
+        {
+            check(tf_map_load_resized(ctx_, path.c_str(), report), "tf_map_load_resized");
+            after_load();
         }
         static struct tf_map_file_info mapFileInfo(const std::string& path)
         {
@@ -372,6 +371,15 @@ namespace tfusion
         static void check(tf_status s, const char* what)
         {
             if (s != TF_OK) throw std::runtime_error(std::string(what) + ": " + tf_status_string(s));
+        }
+        // the wrapper's own frame counter and pose list follow a loaded map
+        void after_load()
+        {
+            float rt[12];
+            check(tf_get_pose(ctx_, rt), "tf_get_pose");
+            frame_counter_ = stats().frame_counter;
+            poses_.clear();
+            poses_.push_back(affine_from_rt(rt));
         }
         TopFuParams params_;
         tf_ctx* ctx_ = nullptr;

@@ -45,7 +45,8 @@ typedef enum tf_status {
     TF_OOM = 3,
     TF_HIP_ERROR = 4,
     TF_NO_DEVICE = 5,
-    TF_INDEX_RANGE = 6      /* tf_mesh_extract_indexed: the mesh has more than 2^32 - 1 vertices, nothing written */
+    TF_INDEX_RANGE = 6,     /* tf_mesh_extract_indexed: the mesh has more than 2^32 - 1 vertices, nothing written */
+    TF_CAPACITY = 7         /* tf_map_load_resized: the file's live content does not fit the context's tables; context untouched */
 } tf_status;
 
 /* TopFuParams (tfusion/include/tfusion/topfu.hpp:28-60) restricted to the fields the
@@ -664,6 +665,36 @@ struct tf_map_file_info {
 tf_status tf_map_file_info(const char* path, struct tf_map_file_info* info);
 /* tf_scene_ckpt_times reports the last tf_map_save / tf_map_load too: the cache blocks' kernel time is part
  * of ms[1], their bytes of ms[5]. */
+
+/* ---- resized load (addition; DESIGN.md §5 Resized load) --------------------------------------------------
+ * A map checkpoint into a context whose n_buckets, n_excess or n_blocks are not the file's: the records are
+ * re-hashed on the way in.  The result is the state a freshly reset context of the target's capacities reaches
+ * when the file's records with a block position (entry.ptr >= -1), in file order, are inserted one at a time by
+ * the reference's allocation rule: the bucket entry, or the end of the bucket's chain linked to
+ * excessList[lastFreeExcessListId--]; a block from allocList[lastFreeBlockId--] where the record has one.  Both
+ * free lists are the identity afterwards.  Records with ptr < -1 (a reset entry that only kept a visType, a swap
+ * state or a stored flag) have no position and are dropped, a stored block of theirs with them.  visibleIds is
+ * rebuilt: the ascending entries with visType > 0, the first vis_capacity of them.  Pose, frame counter and
+ * previous maps are the file's.  Two loads of one file give byte-identical contexts. */
+struct tf_resize_report {
+    long long records_carried;   /* records with a block position (ptr >= -1) placed in the new table */
+    long long records_dropped;   /* records with ptr < -1: no position, cannot be re-hashed */
+    long long blocks;            /* VBA blocks placed (records with ptr >= 0) */
+    long long cache_blocks;      /* GlobalCache blocks placed (carried records with hasStoredData) */
+    long long excess_used;       /* excess-list slots taken */
+    int longest_chain;           /* entries on the longest bucket chain, bucket entry included */
+    int pad;
+};
+/* addition (no reference counterpart): a version-1 file into a context without use_swapping, a version-2 file
+ * into a swapping one.  File and context must agree in cols, rows, voxel_rgb, use_swapping as a boolean, the
+ * bits of voxelSize and mu, and maxW (else TF_INVALID_ARG, as for a file tf_map_load would refuse as invalid);
+ * n_buckets, n_excess, n_blocks, vis_capacity, max_render_blocks and swap_transfer_blocks are the context's own.
+ * TF_CAPACITY: more records with a block than n_blocks, or more chained records than n_excess.  Every refusal
+ * leaves the context exactly as it was, the three GlobalCache buffers included.  report may be NULL; it is
+ * filled on TF_OK and on TF_CAPACITY (what would have been needed), zeroed otherwise.  tf_scene_ckpt_times
+ * reports the call as tf_map_load's, the placement kernels in ms[0].  Continuing a sequence after a resized load
+ * reproduces the saving context's frames when n_buckets is the file's. */
+tf_status tf_map_load_resized(tf_ctx* ctx, const char* path, struct tf_resize_report* report);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tfusion_hip.h")
 
 TF_OK, TF_ICP_FAIL, TF_INVALID_ARG, TF_OOM, TF_HIP_ERROR, TF_NO_DEVICE = range(6)
 TF_INDEX_RANGE = 6                             # tf_mesh_extract_indexed: more vertices than a u32 numbers
-TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2        # tf_mesh_save_ply_attr's attrs
+TF_CAPACITY = 7                                # tf_map_load_resized: the map does not fit the context's tables
+TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2       # tf_mesh_save_ply_attr's attrs
 TF_MESH_INDEXED = 4
 TF_MESH_WHOLE = 8                              # the reading over both tiers of a swapping scene (tf_mesh_extract_whole)
 
@@ -64,6 +65,15 @@ class TfSceneFileInfo(ctypes.Structure):
 class TfMapFileInfo(ctypes.Structure):
     """struct tf_map_file_info: a map checkpoint's header (version 1 or 2)."""
     _fields_ = [("scene", TfSceneFileInfo), ("version", ctypes.c_int), ("n_cache_blocks", ctypes.c_longlong)]
+
+
+class TfResizeReport(ctypes.Structure):
+    """struct tf_resize_report: what a resized load placed (or, on TF_CAPACITY, would have needed)."""
+    _fields_ = [(n, ctypes.c_longlong) for n in ("records_carried", "records_dropped", "blocks", "cache_blocks",
+                                                 "excess_used")] + [("longest_chain", ctypes.c_int), ("pad", ctypes.c_int)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
 
 
 class TfTotals(ctypes.Structure):
@@ -213,6 +223,7 @@ def load():
         "tf_map_save": ([P, ctypes.c_char_p], I),
         "tf_map_load": ([P, ctypes.c_char_p], I),
         "tf_map_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfMapFileInfo)], I),
+        "tf_map_load_resized": ([P, ctypes.c_char_p, ctypes.POINTER(TfResizeReport)], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():

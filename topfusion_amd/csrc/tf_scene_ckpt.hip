@@ -21,6 +21,9 @@
 // Map checkpoints (tf_map_save / tf_map_load, DESIGN.md §5 Map checkpoints) are the same calls; on a swapping
 // context they write version 2 of the file with the k_map_* forms further down: the GlobalCache's swap state
 // and stored flag in every record, the stored blocks gathered from store + index * 512 as a second payload.
+//
+// The resized load (tf_map_load_resized, DESIGN.md §5 Resized load) takes either version into a context of other
+// capacities: the k_rz_* kernels below re-hash the records into the new table before the same scatters run.
 #include "tf_host.h"
 #include "tf_scene_file.h"
 
@@ -246,13 +249,16 @@ __global__ __launch_bounds__(CK_WG) void k_map_records(const TfHashEntry* __rest
 // shape (16 B per lane, a wave instruction per KiB, contiguous inside a block).  The store is indexed by hash
 // entry, 2 KiB each, so the offset is formed in 64 bits (it passes 4 GiB above 2^21 entries); it is touched
 // once, so its side is nontemporal too.
-template <bool GATHER>
+// SKIP (the resized load): a list value of -1 names no entry, its block stays in the staging buffer
+template <bool GATHER, bool SKIP = false>
 __device__ __forceinline__ void ck_copy_store(ck_u4* __restrict__ store, const int* __restrict__ storedIdx, int nb,
                                               ck_u4* __restrict__ stage)
 {
     const size_t n = (size_t)nb << 7;
     for (size_t u = (size_t)blockIdx.x * CK_WG + threadIdx.x; u < n; u += (size_t)gridDim.x * CK_WG) {
-        ck_u4* p = store + (size_t)storedIdx[u >> 7] * 128u + ((unsigned)u & 127u);
+        const int idx = storedIdx[u >> 7];
+        if (SKIP && idx < 0) continue;
+        ck_u4* p = store + (size_t)idx * 128u + ((unsigned)u & 127u);
         if (GATHER) __builtin_nontemporal_store(__builtin_nontemporal_load(p), stage + u);
         else __builtin_nontemporal_store(__builtin_nontemporal_load(stage + u), p);
     }
@@ -282,6 +288,211 @@ __global__ __launch_bounds__(CK_WG) void k_map_apply(const ck_u2* __restrict__ r
         swapState[a.x] = (unsigned char)(c.y >> 8);
         swapFlags[a.x] = (unsigned char)(c.y >> 16);
     }
+}
+
+// ---- the resized load (tf_map_load_resized, DESIGN.md §5 Resized load): the file's records re-hashed into tables
+// of other capacities.  Record j (file order) with ptr >= -1 is carried; h(j) its bucket in the new table, m(j) its
+// rank among the carried records of that bucket by record number, o(j) / b(j) the records before j with m > 0 / with
+// ptr >= 0:  t(j) = h if m == 0 else n_buckets + n_excess - 1 - o(j),  ptr'(j) = n_blocks - 1 - b(j) -- what one
+// insertion after another by the reference's allocation rule into a reset table gives.
+//
+//   k_rz_hash   : h(j) (-1: dropped) and the first round's atomicMin of j per bucket
+//   k_rz_round  : round r -- the record a bucket's minimum names has rank r and becomes the successor of the
+//                 bucket's rank r - 1 record; the others bid (atomicMin) for round r + 1.  Three bucket arrays in
+//                 rotation (this round's minima, the last round's winners, the next round's bids), so no array is
+//                 read and bid into in one launch; the host runs rounds until no record is left: longest_chain
+//                 of them.  A minimum over record numbers does not depend on the order the atomics land in.
+//   k_rz_count  : per 256 records those with m > 0, with ptr >= 0, with a stored block (dropped ones too: their
+//                 blocks lie in the file's second payload); k_map_prefix scans them
+//   k_rz_place  : t(j), ptr'(j), and the two lists the scatters walk: ptr' per active block, t (-1: a dropped
+//                 record's, skipped) per stored block
+//   k_rz_apply  : hash[t] = {pos, the successor's excess slot + 1, ptr'}, visType and the cache bytes at t
+//   k_rz_vis_*  : the ascending entries with visType > 0, the first vis_capacity of them, by count / prefix / emit
+//
+// Everything up to k_rz_count writes scratch only: the fit is checked on its totals before the context is touched.
+#define RZ_NONE 0x7f7f7f7f                                 // no record (above every record number); memset's 0x7f
+
+__global__ __launch_bounds__(CK_WG) void k_rz_hash(const ck_u2* __restrict__ records, int n, unsigned mask, int sw, int* __restrict__ rzH,
+                                                   int* __restrict__ rzRank, int* __restrict__ rzSucc, int* __restrict__ bid,
+                                                   int* __restrict__ tally)
+{
+    const int ng = (n + CK_WG - 1) / CK_WG;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int j = g * CK_WG + threadIdx.x;
+        bool carried = false, cached = false;
+        if (j < n) {
+            const ck_u2 a = records[3 * (size_t)j], b = records[3 * (size_t)j + 1], c = records[3 * (size_t)j + 2];
+            carried = (int)c.x >= -1;
+            cached = carried && sw && ((c.y >> 16) & 0xffu) != 0u;
+            int h = -1;
+            if (carried) {
+                h = tf_hash_index((short)(a.y & 0xffffu), (short)(a.y >> 16), (short)(b.x & 0xffffu), mask);
+                atomicMin(bid + h, j);
+            }
+            rzH[j] = h;
+            rzRank[j] = -1;
+            rzSucc[j] = -1;
+        }
+        const int nc = __popcll(__ballot(carried)), ns = __popcll(__ballot(cached));
+        if ((threadIdx.x & 63) == 0 && nc) {               // (sums: the order they land in does not show)
+            atomicAdd(tally + 0, nc);
+            if (ns) atomicAdd(tally + 1, ns);
+        }
+    }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_rz_round(int n, int r, const int* __restrict__ rzH, int* __restrict__ rzRank,
+                                                    int* __restrict__ rzSucc, const int* __restrict__ cur, int* __restrict__ prev,
+                                                    int* __restrict__ next, int* __restrict__ left)
+{
+    const int ng = (n + CK_WG - 1) / CK_WG;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int j = g * CK_WG + threadIdx.x;
+        bool waits = false;
+        if (j < n) {
+            const int h = rzH[j];
+            if (h >= 0 && rzRank[j] < 0) {
+                if (cur[h] == j) {
+                    rzRank[j] = r;
+                    const int p = prev[h];                 // the bucket's record of rank r - 1 (this thread alone reads
+                    if (p != RZ_NONE) rzSucc[p] = j;       // and clears it: it is round r + 1's bidding array)
+                    prev[h] = RZ_NONE;
+                } else {
+                    atomicMin(next + h, j);
+                    waits = true;
+                }
+            }
+        }
+        const int nw = __popcll(__ballot(waits));
+        if ((threadIdx.x & 63) == 0 && nw) atomicAdd(left, nw);
+    }
+}
+
+// does record j use an excess slot, hold a block, name a stored block (after the rounds)
+__device__ __forceinline__ void rz_classify(const ck_u2* __restrict__ records, const int* __restrict__ rzRank, int j, int n, int sw,
+                                            bool& exc, bool& blk, bool& sto)
+{
+    exc = blk = sto = false;
+    if (j < n) {
+        const ck_u2 c = records[3 * (size_t)j + 2];
+        exc = rzRank[j] > 0;
+        blk = (int)c.x >= 0;
+        sto = sw && ((c.y >> 16) & 0xffu) != 0u;
+    }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_rz_count(const ck_u2* __restrict__ records, const int* __restrict__ rzRank, int n, int sw,
+                                                    int4* __restrict__ groupCnt)
+{
+    __shared__ int4 wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n + CK_WG - 1) / CK_WG;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        bool exc, blk, sto;
+        rz_classify(records, rzRank, g * CK_WG + t, n, sw, exc, blk, sto);
+        const int ne = __popcll(__ballot(exc)), nb = __popcll(__ballot(blk)), ns = __popcll(__ballot(sto));
+        __syncthreads();
+        if ((t & 63) == 0) wcnt[t >> 6] = make_int4(ne, nb, ns, 0);
+        __syncthreads();
+        if (t == 0) {
+            int4 s = make_int4(0, 0, 0, 0);
+            for (int w = 0; w < CK_WG / 64; ++w) { s.x += wcnt[w].x; s.y += wcnt[w].y; s.z += wcnt[w].z; }
+            groupCnt[g] = s;
+        }
+    }
+}
+
+// rzH becomes ptr'(j) (its h is spent once t is known); rzT[j] = -1 marks a dropped record
+__global__ __launch_bounds__(CK_WG) void k_rz_place(const ck_u2* __restrict__ records, int n, int sw, const int4* __restrict__ base,
+                                                    int n_buckets, int n_excess, int n_blocks, int* __restrict__ rzH,
+                                                    const int* __restrict__ rzRank, int* __restrict__ rzT, int* __restrict__ blockPtr,
+                                                    int* __restrict__ storedIdx)
+{
+    __shared__ int4 wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int j = g * CK_WG + t;
+        bool exc, blk, sto;
+        rz_classify(records, rzRank, j, n, sw, exc, blk, sto);
+        const unsigned long long me = __ballot(exc), mb = __ballot(blk), ms = __ballot(sto), below = (1ull << lane) - 1ull;
+        __syncthreads();
+        if (lane == 0) wcnt[w] = make_int4(__popcll(me), __popcll(mb), __popcll(ms), 0);
+        __syncthreads();
+        int4 b = base[g];
+        for (int k = 0; k < w; ++k) { b.x += wcnt[k].x; b.y += wcnt[k].y; b.z += wcnt[k].z; }
+        if (j < n) {
+            const int h = rzH[j];
+            const int at = h < 0 ? -1 : exc ? n_buckets + n_excess - 1 - (b.x + __popcll(me & below)) : h;
+            const int ptr = blk ? n_blocks - 1 - (b.y + __popcll(mb & below)) : -1;
+            rzT[j] = at;
+            rzH[j] = ptr;
+            if (blk) blockPtr[b.y + __popcll(mb & below)] = ptr;
+            if (sto) storedIdx[b.z + __popcll(ms & below)] = at;
+        }
+    }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_rz_apply(const ck_u2* __restrict__ records, int n, int sw, int n_buckets,
+                                                    const int* __restrict__ rzPtr, const int* __restrict__ rzSucc,
+                                                    const int* __restrict__ rzT, TfHashEntry* __restrict__ hash,
+                                                    unsigned char* __restrict__ visType, unsigned char* __restrict__ swapState,
+                                                    unsigned char* __restrict__ swapFlags)
+{
+    for (int j = blockIdx.x * CK_WG + threadIdx.x; j < n; j += gridDim.x * CK_WG) {
+        const int at = rzT[j];
+        if (at < 0) continue;
+        const ck_u2 a = records[3 * (size_t)j], b = records[3 * (size_t)j + 1], c = records[3 * (size_t)j + 2];
+        const int succ = rzSucc[j];
+        const unsigned offset = succ >= 0 ? (unsigned)(rzT[succ] - n_buckets + 1) : 0u;
+        *reinterpret_cast<ck_u4*>(hash + at) = ck_u4{ a.y, b.x & 0xffffu, offset, (unsigned)rzPtr[j] };
+        visType[at] = (unsigned char)c.y;
+        if (sw) {
+            swapState[at] = (unsigned char)(c.y >> 8);
+            swapFlags[at] = (unsigned char)(c.y >> 16);
+        }
+    }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_rz_vis_count(const unsigned char* __restrict__ visType, int n_total, int2* __restrict__ groupCnt)
+{
+    __shared__ int wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int idx = g * CK_WG + t;
+        const int nv = __popcll(__ballot(idx < n_total && visType[idx] != 0));
+        __syncthreads();
+        if ((t & 63) == 0) wcnt[t >> 6] = nv;
+        __syncthreads();
+        if (t == 0) {
+            int s = 0;
+            for (int w = 0; w < CK_WG / 64; ++w) s += wcnt[w];
+            groupCnt[g] = make_int2(s, 0);
+        }
+    }
+}
+
+__global__ __launch_bounds__(CK_WG) void k_rz_vis_emit(const unsigned char* __restrict__ visType, int n_total, const int2* __restrict__ base,
+                                                       int capacity, int* __restrict__ visibleIds)
+{
+    __shared__ int wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int idx = g * CK_WG + t;
+        const bool v = idx < n_total && visType[idx] != 0;
+        const unsigned long long mv = __ballot(v);
+        __syncthreads();
+        if (lane == 0) wcnt[w] = __popcll(mv);
+        __syncthreads();
+        int at = base[g].x + __popcll(mv & ((1ull << lane) - 1ull));
+        for (int k = 0; k < w; ++k) at += wcnt[k];
+        if (v && at < capacity) visibleIds[at] = idx;
+    }
+}
+
+// k_map_scatter over a list in which -1 stands for a block that is not carried
+__global__ __launch_bounds__(CK_WG) void k_rz_scatter_store(TfVoxel* store, const int* __restrict__ storedIdx, int nb,
+                                                            const ck_u4* __restrict__ stage)
+{
+    ck_copy_store<false, true>((ck_u4*)store, storedIdx, nb, (ck_u4*)stage);
 }
 
 static int ck_groups(const tf_ctx* c) { return (c->n_total + CK_WG - 1) / CK_WG; }
@@ -382,10 +593,10 @@ static hipError_t tfk_map_gather(tf_ctx* c, const int* storedIdx, int nb)
     return hipGetLastError();
 }
 
-static hipError_t tfk_map_scatter(tf_ctx* c, const int* storedIdx, int nb)
+static hipError_t tfk_map_scatter(tf_ctx* c, const int* storedIdx, int nb, bool skip = false)
 {
-    hipLaunchKernelGGL(k_map_scatter, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, c->swapStore, storedIdx, nb,
-                       (const ck_u4*)c->ckptStage);
+    hipLaunchKernelGGL(skip ? k_rz_scatter_store : k_map_scatter, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, c->swapStore,
+                       storedIdx, nb, (const ck_u4*)c->ckptStage);
     return hipGetLastError();
 }
 
@@ -604,6 +815,12 @@ extern "C" tf_status tf_scene_save(tf_ctx* c, const char* path)
 
 static bool bits_equal(float a, float b) { return memcmp(&a, &b, sizeof(float)) == 0; }
 
+// the two halves every load ends with (below scene_load)
+static tf_status ckpt_load_blocks(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
+                                  const int* ptr_dev, const int* sto_dev, bool skip);
+static tf_status ckpt_load_finish(tf_ctx* c, const unsigned char* data, const struct tf_scene_file_info& info, const TfSceneLayout& lay,
+                                  int lastFreeBlockId, int lastFreeExcessListId, int noVisibleEntries);
+
 // the validated file into the context (nothing here fails on the file's contents)
 static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay)
 {
@@ -646,6 +863,27 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
             if (s != TF_OK) return s;
         }
     }
+    s = ckpt_load_blocks(c, data, minfo, lay, ptr_dev, sto_dev, false);
+    if (s != TF_OK) return s;
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {              // the block grid from the hash, as after a hash upload
+        const hipError_t e = sw ? tfk_map_apply(c, rec_dev, info.n_records) : tfk_ckpt_apply(c, rec_dev, info.n_records);
+        return e == hipSuccess ? tfk_grid_rebuild(c) : e;
+    });
+    if (s != TF_OK) return s;
+    s = ckpt_h2d(c, c->visibleIds, data + lay.vis_off, 4 * lay.n_vis);
+    if (s == TF_OK) s = ckpt_h2d(c, c->allocList, data + lay.alloc_off, 4 * lay.n_alloc);
+    if (s == TF_OK) s = ckpt_h2d(c, c->excessList, data + lay.excess_off, 4 * lay.n_excess);
+    if (s != TF_OK) return s;
+    return ckpt_load_finish(c, data, info, lay, info.lastFreeBlockId, info.lastFreeExcessListId, info.noVisibleEntries);
+}
+
+// the file's two block payloads through the staging buffer to where the lists say: active blocks to ptr * 512 (and
+// the colour plane), stored ones to store + entry * 512 (`skip`: -1 in that list names no entry)
+static tf_status ckpt_load_blocks(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
+                                  const int* ptr_dev, const int* sto_dev, bool skip)
+{
+    const struct tf_scene_file_info& info = minfo.scene;
+    tf_status s = TF_OK;
     for (long long b0 = 0; b0 < info.n_blocks_stored; b0 += c->ckpt_chunk_blocks) {
         const int nb = (int)(info.n_blocks_stored - b0 < c->ckpt_chunk_blocks ? info.n_blocks_stored - b0 : c->ckpt_chunk_blocks);
         s = ckpt_h2d(c, c->ckptStage, data + lay.blocks_off + (size_t)b0 * lay.block_bytes, (size_t)nb * lay.block_bytes);
@@ -658,18 +896,18 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
         const int nb = (int)(minfo.n_cache_blocks - b0 < c->ckpt_chunk_blocks ? minfo.n_cache_blocks - b0 : c->ckpt_chunk_blocks);
         s = ckpt_h2d(c, c->ckptStage, data + lay.stored_off + (size_t)b0 * TF_SCENE_BLOCK_BYTES, (size_t)nb * TF_SCENE_BLOCK_BYTES);
         if (s != TF_OK) return s;
-        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_map_scatter(c, sto_dev + b0, nb); });
+        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_map_scatter(c, sto_dev + b0, nb, skip); });
         if (s != TF_OK) return s;
         c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)TF_SCENE_BLOCK_BYTES;
     }
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] {              // the block grid from the hash, as after a hash upload
-        const hipError_t e = sw ? tfk_map_apply(c, rec_dev, info.n_records) : tfk_ckpt_apply(c, rec_dev, info.n_records);
-        return e == hipSuccess ? tfk_grid_rebuild(c) : e;
-    });
-    if (s != TF_OK) return s;
-    s = ckpt_h2d(c, c->visibleIds, data + lay.vis_off, 4 * lay.n_vis);
-    if (s == TF_OK) s = ckpt_h2d(c, c->allocList, data + lay.alloc_off, 4 * lay.n_alloc);
-    if (s == TF_OK) s = ckpt_h2d(c, c->excessList, data + lay.excess_off, 4 * lay.n_excess);
+    return TF_OK;
+}
+
+// the end of a load: the file's previous maps, pose and frame counter; the counters as given
+static tf_status ckpt_load_finish(tf_ctx* c, const unsigned char* data, const struct tf_scene_file_info& info, const TfSceneLayout& lay,
+                                  int lastFreeBlockId, int lastFreeExcessListId, int noVisibleEntries)
+{
+    tf_status s = TF_OK;
     size_t o = lay.maps_off;
     for (int l = 0; l < TF_LEVELS && s == TF_OK; ++l) {
         s = ckpt_h2d(c, c->prev_pts[l], data + o, lay.map_bytes[l]);
@@ -686,9 +924,9 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
     if (s != TF_OK) return s;
     TfDevState* st = c->st_host;
     memcpy(st->pose, info.pose, sizeof(info.pose));
-    st->lastFreeBlockId = info.lastFreeBlockId;
-    st->lastFreeExcessListId = info.lastFreeExcessListId;
-    st->noVisibleEntries = info.noVisibleEntries;
+    st->lastFreeBlockId = lastFreeBlockId;
+    st->lastFreeExcessListId = lastFreeExcessListId;
+    st->noVisibleEntries = noVisibleEntries;
     st->frame_counter = info.frame_counter;
     // the free lists and the blocks in use need not be what frames alone leave (a scene that came
     // through tf_upload): every later reset clears everything (tf_reset.h)
@@ -699,9 +937,118 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
     return s;
 }
 
-extern "C" tf_status tf_map_load(tf_ctx* c, const char* path)
+// the validated file into a context of other capacities: the placement into scratch, the fit check, then the commit
+// in scene_load's order.  TF_CAPACITY leaves the context as it was.
+static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
+                                    struct tf_resize_report* report)
 {
-    TF_FLUSH(c);
+    TfCtxMem tmp(c->mem.fns());
+    unsigned char* rec_dev = nullptr;
+    int *ptr_dev = nullptr, *sto_dev = nullptr, *rz = nullptr, *bid = nullptr, *tally = nullptr;
+    int4* grp = nullptr;
+    const struct tf_scene_file_info& info = minfo.scene;
+    const int sw = minfo.version == (int)TF_MAP_VERSION;
+    if (info.n_records > 0x7fffffffll / 4) return TF_INVALID_ARG;      // (a valid file has at most n_total of them)
+    const int n = (int)info.n_records, ng = (n + CK_WG - 1) / CK_WG, nbk = c->p.n_buckets;
+    const size_t rec_bytes = (size_t)n * TF_SCENE_RECORD_BYTES;
+    TF_CHECK(tfk_ckpt_scratch(c));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * (size_t)minfo.n_cache_blocks)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&rz, sizeof(int) * 4 * (size_t)n)));             // h / ptr', rank, successor, t per record
+    TF_CHECK(tf_mem_hip(tmp.alloc(&bid, sizeof(int) * 3 * (size_t)nbk)));          // the rounds' three bucket arrays
+    TF_CHECK(tf_mem_hip(tmp.alloc(&grp, sizeof(int4) * (2 * (size_t)ng + 1))));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&tally, sizeof(int) * 4)));                      // carried, carried with a stored block, left
+    int *rzH = rz, *rzRank = rz + n, *rzSucc = rz + 2 * (size_t)n, *rzT = rz + 3 * (size_t)n;
+    tf_status s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
+    if (s != TF_OK) return s;
+    const ck_u2* rec = (const ck_u2*)rec_dev;
+    const dim3 grid(ck_grid((size_t)n)), wg(CK_WG);
+    int host_tally[4] = { 0, 0, 0, 0 };
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+        hipError_t e = hipMemsetAsync(bid, 0x7f, sizeof(int) * 3 * (size_t)nbk, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(tally, 0, sizeof(int) * 4, c->stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rz_hash, grid, wg, 0, c->stream, rec, n, (unsigned)(nbk - 1), sw, rzH, rzRank, rzSucc, bid, tally);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    TF_CHECK(hipMemcpyAsync(host_tally, tally, sizeof(host_tally), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    int rounds = 0;
+    for (int left = host_tally[0]; left > 0; ++rounds) {   // a round ranks one record of every bucket that has any left
+        int* cur = bid + (size_t)(rounds % 3) * nbk;
+        int* prev = bid + (size_t)((rounds + 2) % 3) * nbk;
+        int* next = bid + (size_t)((rounds + 1) % 3) * nbk;
+        s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+            const hipError_t e = hipMemsetAsync(tally + 2, 0, sizeof(int), c->stream);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_rz_round, grid, wg, 0, c->stream, n, rounds, rzH, rzRank, rzSucc, cur, prev, next, tally + 2);
+            return hipGetLastError();
+        });
+        if (s != TF_OK) return s;
+        TF_CHECK(hipMemcpyAsync(&left, tally + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        TF_CHECK(hipStreamSynchronize(c->stream));
+    }
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+        hipLaunchKernelGGL(k_rz_count, grid, wg, 0, c->stream, rec, rzRank, n, sw, grp);
+        hipLaunchKernelGGL(k_map_prefix, dim3(1), wg, 0, c->stream, grp, ng, grp + ng);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    int4 totals;                                           // excess slots, active blocks, stored blocks in the file
+    TF_CHECK(hipMemcpyAsync(&totals, grp + 2 * (size_t)ng, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    if (report) {
+        report->records_carried = host_tally[0];
+        report->records_dropped = (long long)n - host_tally[0];
+        report->blocks = totals.y;
+        report->cache_blocks = host_tally[1];
+        report->excess_used = totals.x;
+        report->longest_chain = rounds;
+    }
+    if (totals.y != info.n_blocks_stored || totals.z != minfo.n_cache_blocks) return TF_INVALID_ARG;      // (the validation's counts)
+    if (totals.y > c->p.n_blocks || totals.x > c->p.n_excess) return TF_CAPACITY;
+    // ---- the commit ----
+    TF_CHECK(tfk_reset_scene(c));                          // full: hash, VBA, colour, both lists (identity), block grid cells
+    TF_CHECK(hipMemsetAsync(c->visType, 0, (size_t)c->n_total, c->stream));
+    if (sw) {
+        TF_CHECK(hipMemsetAsync(c->swapState, 0, (size_t)c->n_total, c->stream));
+        TF_CHECK(hipMemsetAsync(c->swapFlags, 0, (size_t)c->n_total, c->stream));
+    }
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+        hipLaunchKernelGGL(k_rz_place, grid, wg, 0, c->stream, rec, n, sw, (const int4*)(grp + ng), nbk, c->p.n_excess, c->p.n_blocks, rzH,
+                           rzRank, rzT, ptr_dev, sto_dev);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    s = ckpt_load_blocks(c, data, minfo, lay, ptr_dev, sto_dev, true);
+    if (s != TF_OK) return s;
+    int2* vcnt = (int2*)c->ckptGroup;                      // the context's own group scratch: a count per 256 entries
+    const int ngt = ck_groups(c);
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+        hipLaunchKernelGGL(k_rz_apply, grid, wg, 0, c->stream, rec, n, sw, nbk, rzH, rzSucc, rzT, c->hash, c->visType, c->swapState,
+                           c->swapFlags);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = tfk_grid_rebuild(c);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rz_vis_count, dim3(ck_grid((size_t)c->n_total)), wg, 0, c->stream, c->visType, c->n_total, vcnt);
+        hipLaunchKernelGGL(k_ckpt_prefix, dim3(1), wg, 0, c->stream, vcnt, ngt, vcnt + ngt);
+        hipLaunchKernelGGL(k_rz_vis_emit, dim3(ck_grid((size_t)c->n_total)), wg, 0, c->stream, c->visType, c->n_total, vcnt + ngt,
+                           c->p.vis_capacity, c->visibleIds);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    int2 nvis;
+    TF_CHECK(hipMemcpyAsync(&nvis, vcnt + 2 * (size_t)ngt, sizeof(nvis), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    return ckpt_load_finish(c, data, info, lay, c->p.n_blocks - 1 - totals.y, c->p.n_excess - 1 - totals.x,
+                            nvis.x < c->p.vis_capacity ? nvis.x : c->p.vis_capacity);
+}
+
+// tf_map_load, or with `resized` tf_map_load_resized: the capacities need not agree, the records are re-hashed
+static tf_status map_load(tf_ctx* c, const char* path, bool resized, struct tf_resize_report* report)
+{
     if (!c || !path) return TF_INVALID_ARG;
     {
         const tf_status s0 = sync_checked(c);
@@ -728,15 +1075,30 @@ extern "C" tf_status tf_map_load(tf_ctx* c, const char* path)
         const tf_params& a = minfo.scene.params;
         const tf_params& b = c->p;
         // (a version-2 file has use_swapping == 1, a version-1 file 0: the layout's rule; the context's may be any non-zero value)
-        if (a.cols != b.cols || a.rows != b.rows || a.n_buckets != b.n_buckets || a.n_excess != b.n_excess || a.n_blocks != b.n_blocks ||
-            a.voxel_rgb != b.voxel_rgb || (a.use_swapping != 0) != (b.use_swapping != 0) || !bits_equal(a.voxelSize, b.voxelSize) ||
-            !bits_equal(a.mu, b.mu) || a.maxW != b.maxW || minfo.scene.noVisibleEntries > b.vis_capacity)
+        if (a.cols != b.cols || a.rows != b.rows || a.voxel_rgb != b.voxel_rgb || (a.use_swapping != 0) != (b.use_swapping != 0) ||
+            !bits_equal(a.voxelSize, b.voxelSize) || !bits_equal(a.mu, b.mu) || a.maxW != b.maxW)
+            s = TF_INVALID_ARG;
+        if (!resized && (a.n_buckets != b.n_buckets || a.n_excess != b.n_excess || a.n_blocks != b.n_blocks ||
+                         minfo.scene.noVisibleEntries > b.vis_capacity))
             s = TF_INVALID_ARG;
     }
-    if (s == TF_OK) s = scene_load(c, data, minfo, lay);
+    if (s == TF_OK) s = resized ? scene_load_resized(c, data, minfo, lay, report) : scene_load(c, data, minfo, lay);
     free(data);
     c->ckpt_ms[CK_T_CALL] = ck_now_ms() - t_call;
     return s;
+}
+
+extern "C" tf_status tf_map_load(tf_ctx* c, const char* path)
+{
+    TF_FLUSH(c);
+    return map_load(c, path, false, nullptr);
+}
+
+extern "C" tf_status tf_map_load_resized(tf_ctx* c, const char* path, struct tf_resize_report* report)
+{
+    TF_FLUSH(c);
+    if (report) memset(report, 0, sizeof(*report));
+    return map_load(c, path, true, report);
 }
 
 extern "C" tf_status tf_scene_load(tf_ctx* c, const char* path)

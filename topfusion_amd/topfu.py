@@ -356,11 +356,30 @@ class TopFu:
         L.check(L.load().tf_map_load(self._h, str(path).encode()), "tf_map_load")
         self._framed = True
 
+    def load_map_resized(self, path):
+        """load_map into a context whose n_buckets, n_excess or n_blocks are not the file's (tf_map_load_resized):
+        the records are re-hashed on the way in, as if inserted one by one into a reset table; records without
+        a block position are dropped.  Returns the report as a dict (records_carried, records_dropped, blocks,
+        cache_blocks, excess_used, longest_chain).  A map that does not fit is TfError with TF_CAPACITY; its
+        .report holds what would have been needed, and the context is as it was."""
+        rep = L.TfResizeReport()
+        status = L.load().tf_map_load_resized(self._h, str(path).encode(), ctypes.byref(rep))
+        if status != L.TF_OK:
+            err = L.TfError(status, "tf_map_load_resized")
+            err.report = rep.as_dict() if status == L.TF_CAPACITY else None
+            raise err
+        self._framed = True
+        return rep.as_dict()
+
     @classmethod
-    def from_map(cls, path, device=None, **overrides):
+    def from_map(cls, path, device=None, resize=False, **overrides):
         """from_scene for a map checkpoint of either version: the context is built from the file's
-        params, swapping included."""
-        return cls._from_file(path, device, overrides, L.map_file_info, "load_map")
+        params, swapping included.  resize=True: `overrides` may change n_buckets, n_excess and n_blocks,
+        and the file is loaded with load_map_resized (the report is kept as .resize_report)."""
+        return cls._from_file(path, device, overrides, L.map_file_info, "_load_map_resized_keep" if resize else "load_map")
+
+    def _load_map_resized_keep(self, path):
+        self.resize_report = self.load_map_resized(path)
 
     @classmethod
     def from_scene(cls, path, device=None, **overrides):
