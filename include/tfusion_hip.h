@@ -61,7 +61,7 @@ typedef struct tf_params {
     float icp_truncate_depth_dist;      /* m; <= 0 disables */
     float icp_dist_thres;               /* m */
     float icp_angle_thres;              /* rad */
-    int   icp_iter_num[4];              /* per level 0..3 */
+    int   icp_iter_num[4];              /* per level 0..3; none negative, [3] == 0 (three pyramid levels) */
     float mu;                           /* TSDF truncation band (SceneParams::mu) */
     int   maxW;
     float voxelSize;                    /* m */

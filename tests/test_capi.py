@@ -82,6 +82,18 @@ def test_status_strings_and_invalid_args():
     assert L.tf_create(ctypes.byref(bad), ctypes.byref(ctx)) == _lib.TF_INVALID_ARG
 
 
+@pytest.mark.parametrize("iters", [(10, 5, 4, 1), (10, 5, 0, 2), (-1, 5, 4, 0), (10, -5, 4, 0), (10, 5, -4, 0), (10, 5, 4, -1)])
+def test_create_refuses_iteration_counts_set_params_refuses(iters):
+    """tf_create takes the iteration counts tf_icp_set_params takes: none negative, and none at a fourth
+    level (the pyramids have three).  Refused before any device is looked for."""
+    L = _lib.load()
+    ctx = ctypes.c_void_p()
+    bad = _lib.default_params(icp_iter_num=iters)
+    assert list(bad.icp_iter_num) == list(iters)
+    assert L.tf_create(ctypes.byref(bad), ctypes.byref(ctx)) == _lib.TF_INVALID_ARG
+    assert not ctx.value
+
+
 def test_no_silent_cpu_fallback(monkeypatch):
     """The product fails loudly when the HIP library is missing."""
     monkeypatch.setattr(_lib, "_lib", None)

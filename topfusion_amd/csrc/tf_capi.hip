@@ -77,6 +77,9 @@ static bool params_valid(const tf_params* p)
     if (p->n_blocks > (1 << 21) - 1) return false;
     if ((p->n_buckets + p->n_excess) % 16) return false;
     if (p->bilateral_kernel_size < 1 || p->bilateral_kernel_size > 7) return false;
+    // the tracker's iteration counts, as tf_icp_set_params takes them: none negative, three pyramid levels (TF_LEVELS)
+    for (int l = 0; l < 4; ++l) if (p->icp_iter_num[l] < 0) return false;
+    if (p->icp_iter_num[3] != 0) return false;
     if (p->voxelSize <= 0 || p->mu <= 0) return false;
     // steps per pixel ceil(2*|e-s|) with |e-s| ~ 2*mu/(8*voxel) must fit the 6-bit key field
     if (4.0f * p->mu / (8.0f * p->voxelSize) + 2.0f > 60.0f) return false;
