@@ -484,11 +484,12 @@ struct tf_ctx {
     long long meshSlotCap;
     int mesh_chunk_bytes;                // TFUSION_MESH_CHUNK_BYTES; default TF_MESH_CHUNK_BYTES
     unsigned char* meshPinned;           // [mesh_chunk_bytes], allocated by the first tf_mesh_save_ply_indexed_whole
-    // scene checkpoints (tf_scene_ckpt.hip): per 256-entry group its (records, stored blocks) counts, then their
-    // exclusive bases + the totals, then a flag; the bounded block staging buffer and its pinned twin;
-    // allocated by the first save / load
+    // scene checkpoints (tf_scene_ckpt.hip): an ordered pass's scratch over the n_total entries -- per 256-entry
+    // group its counts (records, stored blocks, blocks in the GlobalCache, 0; the resized load's visible list: one
+    // count, the rest 0), then their exclusive bases + the totals, then a flag, int4 each whatever the context;
+    // the bounded block staging buffer and its pinned twin; allocated by the first save / load
     int ckpt_chunk_blocks;               // blocks per staging chunk (TFUSION_CKPT_CHUNK_BLOCKS; default TF_CKPT_CHUNK_BLOCKS)
-    int2* ckptGroup;
+    int4* ckptGroup;                     // [2 * groups + 2]
     unsigned char* ckptStage;
     unsigned char* ckptPinned;
     hipEvent_t ckptEv[2];                // around the checkpoint kernels (tf_scene_ckpt_times)

@@ -1,29 +1,30 @@
-// tf_scene_ckpt.hip -- scene checkpoints for gfx950 (an addition: the reference cannot save its map;
-// DESIGN.md §5 Scene checkpoints, the file in tf_scene_file.h).  The scene is written in hash-entry order
-// by the scheme the mesh passes use -- an ordered count, a prefix, an emit pass -- as plain launches on
-// the context stream:
+// tf_scene_ckpt.hip -- scene and map checkpoints for gfx950 (an addition: the reference cannot save its map;
+// DESIGN.md §5 Scene checkpoints / Map checkpoints / Resized load, the file in tf_scene_file.h).  Everything that
+// is written in order here -- the records in hash-entry order, the lists the block copies walk, the re-hashed
+// placement, the visible list -- is made by one ordered compaction, the scheme the mesh passes use: a count per
+// 256 items, a prefix, an emit pass, as plain launches on the context stream:
 //
-//   k_ckpt_count   : per 256-entry group the entries that get a record (HashEntry not ResetScene's, or
-//                    visType != 0) and those of them with a stored block (ptr >= 0)
-//   k_ckpt_prefix  : exclusive scan of the group counts (one workgroup: a group count per 256 entries)
-//   k_ckpt_records : every record at its base (24 B, three 8-byte stores), and the stored blocks' ptr in
-//                    record order -- the list the gather walks
-//   k_ckpt_gather  : blocks [b0, b0 + nb) of that list from the VBA (and the colour plane) into the
-//                    staging buffer, 16 B per lane: a wave instruction moves 1 KiB, contiguous on both
-//                    sides inside a block; no atomics
-//   k_ckpt_scatter : the reverse (load): staging -> ptr * 512
-//   k_ckpt_apply   : hash[index], visType[index] from the records (the block grid is rebuilt after)
+//   k_ck_pass<false, P> : per 256-item group how many items take a place in each of pass P's (up to three) lists
+//   k_ck_prefix         : exclusive scan of the group counts (one workgroup: a count per 256 items) + the totals
+//   k_ck_pass<true, P>  : every item with its place in each list -- the group's base, the waves before, the lanes below
 //
-// The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of its
-// own over int2 group counts (8 B per 256 entries) rather than k_mesh_prefix over 64-bit per-entry
-// counts, and shares no scratch with a mesh extraction.  No workgroup waits on another inside a grid.
+// and the passes are: CkSavePass (an entry gets a record / holds a block / has a stored block in the GlobalCache:
+// the record table and the two lists the gathers walk), CkRzPass (the resized load's placement) and CkVisPass (its
+// visible list).  The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of
+// its own over int4 group counts (16 B per 256 items, the fourth lane zero; a pass with fewer lists leaves the
+// others zero) rather than k_mesh_prefix over 64-bit per-entry counts, and shares no scratch with a mesh extraction.
+// No atomics in these passes, and no workgroup waits on another inside a grid.  Beside them:
 //
-// Map checkpoints (tf_map_save / tf_map_load, DESIGN.md §5 Map checkpoints) are the same calls; on a swapping
-// context they write version 2 of the file with the k_map_* forms further down: the GlobalCache's swap state
-// and stored flag in every record, the stored blocks gathered from store + index * 512 as a second payload.
+//   k_ck_copy<GATHER>             : blocks [b0, b0 + nb) of the ptr list between the VBA (and the colour plane) and
+//                                   the staging buffer, 16 B per lane: a wave instruction moves 1 KiB, contiguous on
+//                                   both sides inside a block; no atomics
+//   k_ck_copy_store<GATHER, SKIP> : the same between the GlobalCache's store + entry * 512 and the staging buffer
+//   k_ck_apply                    : hash[index], visType[index] (and the cache bytes) from the records (load; the
+//                                   block grid is rebuilt after)
+//   k_rz_hash, k_rz_round, k_rz_apply : the resized load's re-hash (further down)
 //
-// The resized load (tf_map_load_resized, DESIGN.md §5 Resized load) takes either version into a context of other
-// capacities: the k_rz_* kernels below re-hash the records into the new table before the same scatters run.
+// A swapping context (tf_map_save / tf_map_load) differs by a uniform `sw`: the GlobalCache's swap state and stored
+// flag in the record predicate and in every record (version 2 of the file), the stored blocks as a second payload.
 #include "tf_host.h"
 #include "tf_scene_file.h"
 
@@ -36,92 +37,130 @@
 typedef unsigned ck_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned ck_u2 __attribute__((ext_vector_type(2)));
 
-// does entry idx get a record, does the record carry a block; e: its four words
-__device__ __forceinline__ void ck_classify(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType, int idx,
-                                            int n_total, ck_u4& e, unsigned& vis, bool& rec, bool& blk)
+// ---- the record (tf_scene_file.h): 24 bytes as three 8-byte words -- the entry's index, the HashEntry's four words,
+// then visType, swapState, hasStoredData, 0.  Without the GlobalCache (version 1) the last three bytes are zero.
+struct CkRecord { unsigned idx; ck_u4 e; unsigned tail; };
+
+__device__ __forceinline__ void ck_record_store(ck_u2* __restrict__ records, size_t k, const CkRecord& r)
 {
-    e = ck_u4{ 0u, 0u, 0u, 0xfffffffeu };
-    vis = 0;
-    if (idx < n_total) {
-        e = *reinterpret_cast<const ck_u4*>(hash + idx);
-        vis = visType[idx];
-    }
-    rec = idx < n_total && ((e.x | e.y | e.z) != 0u || e.w != 0xfffffffeu || vis != 0u);
-    blk = rec && (int)e.w >= 0;
+    ck_u2* p = records + 3 * k;
+    p[0] = ck_u2{ r.idx, r.e.x };
+    p[1] = ck_u2{ r.e.y, r.e.z };
+    p[2] = ck_u2{ r.e.w, r.tail };
 }
 
-__global__ __launch_bounds__(CK_WG) void k_ckpt_count(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
-                                                      int n_total, int n_blocks, int2* __restrict__ groupCnt, int* __restrict__ bad)
+__device__ __forceinline__ CkRecord ck_record_load(const ck_u2* __restrict__ records, size_t k)
 {
-    __shared__ int2 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG;
+    const ck_u2 a = records[3 * k], b = records[3 * k + 1], c = records[3 * k + 2];
+    return CkRecord{ a.x, ck_u4{ a.y, b.x, b.y, c.x }, c.y };
+}
+
+// a record's last word at entry `at` (with sw: swapState / swapFlags were cleared over the whole table before)
+__device__ __forceinline__ void ck_tail_apply(unsigned tail, int at, int sw, unsigned char* __restrict__ visType,
+                                              unsigned char* __restrict__ swapState, unsigned char* __restrict__ swapFlags)
+{
+    visType[at] = (unsigned char)tail;
+    if (sw) {
+        swapState[at] = (unsigned char)(tail >> 8);
+        swapFlags[at] = (unsigned char)(tail >> 16);
+    }
+}
+
+// ---- the ordered compaction.  A pass P names its items 0 .. n - 1 and gives
+//   unsigned P::classify(i, i < n, item) : bit q set -- item i takes a place in list q (0 for i >= n); `item` is what
+//                                          emit needs of it again
+//   void P::emit(i, item, bits, at0, at1, at2) : for every i < n; at_q is the number of items below i with bit q
+// The skeleton owns the ballots, the per-wave tally in LDS and its two barriers (the first ends the previous group's
+// reads of the tally), the group count (count mode: grp[g]) and base + waves before + lanes below (emit mode: the
+// bases stand behind the counts, grp[ng + g]).  All 256 threads of a group reach both barriers.
+__device__ __forceinline__ void ck_add(int4& s, const int4 v) { s.x += v.x; s.y += v.y; s.z += v.z; }
+
+template <bool EMIT, class Pass>
+__global__ __launch_bounds__(CK_WG) void k_ck_pass(const Pass p, int n, int4* __restrict__ grp)
+{
+    __shared__ int4 wcnt[CK_WG / 64];
+    const int t = threadIdx.x, ng = (n + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
     for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        ck_u4 e; unsigned vis; bool rec, blk;
-        ck_classify(hash, visType, g * CK_WG + t, n_total, e, vis, rec, blk);
-        if (blk && (int)e.w >= n_blocks) *bad = 1;            // a block outside the VBA (an uploaded table): not saveable
-        const int nr = __popcll(__ballot(rec)), nb = __popcll(__ballot(blk));
+        const int i = g * CK_WG + t;
+        typename Pass::Item item;
+        const unsigned bits = p.classify(i, i < n, item);
+        const unsigned long long m0 = __ballot(bits & 1u), m1 = __ballot(bits & 2u), m2 = __ballot(bits & 4u);
         __syncthreads();
-        if ((t & 63) == 0) wcnt[t >> 6] = make_int2(nr, nb);
+        if (lane == 0) wcnt[w] = make_int4(__popcll(m0), __popcll(m1), __popcll(m2), 0);
         __syncthreads();
-        if (t == 0) {
-            int2 s = make_int2(0, 0);
-            for (int w = 0; w < CK_WG / 64; ++w) { s.x += wcnt[w].x; s.y += wcnt[w].y; }
-            groupCnt[g] = s;
+        if (!EMIT) {
+            if (t == 0) {
+                int4 s = make_int4(0, 0, 0, 0);
+                for (int k = 0; k < CK_WG / 64; ++k) ck_add(s, wcnt[k]);
+                grp[g] = s;
+            }
+        } else {
+            int4 b = grp[ng + g];
+            for (int k = 0; k < w; ++k) ck_add(b, wcnt[k]);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (i < n) p.emit(i, item, bits, b.x + __popcll(m0 & below), b.y + __popcll(m1 & below), b.z + __popcll(m2 & below));
         }
     }
 }
 
 // base[g] = sum of cnt[0, g), base[ng] = the totals.  One workgroup: thread t owns a contiguous slice.
-__global__ __launch_bounds__(CK_WG) void k_ckpt_prefix(const int2* __restrict__ cnt, int ng, int2* __restrict__ base)
+__global__ __launch_bounds__(CK_WG) void k_ck_prefix(const int4* __restrict__ cnt, int ng, int4* __restrict__ base)
 {
-    __shared__ int2 part[CK_WG];
+    __shared__ int4 part[CK_WG];
     const int t = threadIdx.x, per = (ng + CK_WG - 1) / CK_WG;
     const int first = min(t * per, ng), last = min(first + per, ng);
-    int2 s = make_int2(0, 0);
-    for (int g = first; g < last; ++g) { s.x += cnt[g].x; s.y += cnt[g].y; }
+    int4 s = make_int4(0, 0, 0, 0);
+    for (int g = first; g < last; ++g) ck_add(s, cnt[g]);
     part[t] = s;
     __syncthreads();
     if (t == 0) {
-        int2 run = make_int2(0, 0);
-        for (int k = 0; k < CK_WG; ++k) { const int2 v = part[k]; part[k] = run; run.x += v.x; run.y += v.y; }
+        int4 run = make_int4(0, 0, 0, 0);
+        for (int k = 0; k < CK_WG; ++k) { const int4 v = part[k]; part[k] = run; ck_add(run, v); }
         base[ng] = run;
     }
     __syncthreads();
     s = part[t];
-    for (int g = first; g < last; ++g) { base[g] = s; s.x += cnt[g].x; s.y += cnt[g].y; }
+    for (int g = first; g < last; ++g) { base[g] = s; ck_add(s, cnt[g]); }
 }
 
-__global__ __launch_bounds__(CK_WG) void k_ckpt_records(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
-                                                        int n_total, const int2* __restrict__ base, ck_u2* __restrict__ records,
-                                                        int* __restrict__ blockPtr)
-{
-    __shared__ int2 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        const int idx = g * CK_WG + t;
-        ck_u4 e; unsigned vis; bool rec, blk;
-        ck_classify(hash, visType, idx, n_total, e, vis, rec, blk);
-        const unsigned long long mr = __ballot(rec), mb = __ballot(blk), below = (1ull << lane) - 1ull;
-        __syncthreads();
-        if (lane == 0) wcnt[w] = make_int2(__popcll(mr), __popcll(mb));
-        __syncthreads();
-        int2 b = base[g];
-        for (int k = 0; k < w; ++k) { b.x += wcnt[k].x; b.y += wcnt[k].y; }
-        if (rec) {
-            ck_u2* r = records + 3 * (size_t)(b.x + __popcll(mr & below));
-            r[0] = ck_u2{ (unsigned)idx, e.x };
-            r[1] = ck_u2{ e.y, e.z };
-            r[2] = ck_u2{ e.w, vis };
+// save: entry idx gets a record (HashEntry not ResetScene's, or visType or a cache byte != 0), the record carries a
+// block (ptr >= 0), the entry has a stored block (hasStoredData).  Emit: the record at its place, the block's ptr and
+// the flagged entry's index in record order -- the lists the two gathers walk.
+struct CkSavePass {
+    typedef CkRecord Item;
+    const TfHashEntry* hash;
+    const unsigned char *visType, *swapState, *swapFlags;
+    int sw, n_blocks;
+    int* bad;                                              // the count launch's: set when a block lies outside the VBA
+    ck_u2* records;                                        // (an uploaded table): not saveable.  The emit launch's:
+    int *blockPtr, *storedIdx;                             // the record table and the two lists
+
+    __device__ __forceinline__ unsigned classify(int idx, bool in, CkRecord& r) const
+    {
+        r = CkRecord{ (unsigned)idx, ck_u4{ 0u, 0u, 0u, 0xfffffffeu }, 0u };
+        if (in) {
+            r.e = *reinterpret_cast<const ck_u4*>(hash + idx);
+            r.tail = visType[idx];
+            if (sw) r.tail |= (unsigned)swapState[idx] << 8 | (unsigned)swapFlags[idx] << 16;
         }
-        if (blk) blockPtr[b.y + __popcll(mb & below)] = (int)e.w;
+        const bool rec = (r.e.x | r.e.y | r.e.z) != 0u || r.e.w != 0xfffffffeu || r.tail != 0u;
+        const bool blk = rec && (int)r.e.w >= 0;
+        if (bad && blk && (int)r.e.w >= n_blocks) *bad = 1;
+        return (unsigned)rec | (unsigned)blk << 1 | (r.tail >> 16 != 0u ? 4u : 0u);
     }
-}
+    __device__ __forceinline__ void emit(int idx, const CkRecord& r, unsigned bits, int at_rec, int at_blk, int at_sto) const
+    {
+        if (bits & 1u) ck_record_store(records, (size_t)at_rec, r);
+        if (bits & 2u) blockPtr[at_blk] = (int)r.e.w;
+        if (bits & 4u) storedIdx[at_sto] = idx;
+    }
+};
 
 // 16-byte unit u of the chunk: block u / U, unit u % U of it (U = 128, or 256 with colour: the block's
 // voxels, then its colour words)
 template <bool GATHER>
-__device__ __forceinline__ void ck_copy(ck_u4* __restrict__ vba, ck_u4* __restrict__ rgb, const int* __restrict__ blockPtr,
-                                        int nb, ck_u4* __restrict__ stage)
+__global__ __launch_bounds__(CK_WG) void k_ck_copy(ck_u4* __restrict__ vba, ck_u4* __restrict__ rgb, const int* __restrict__ blockPtr,
+                                                   int nb, ck_u4* __restrict__ stage)
 {
     const unsigned sh = rgb ? 8u : 7u, U = 1u << sh;
     const size_t n = (size_t)nb << sh;
@@ -134,125 +173,14 @@ __device__ __forceinline__ void ck_copy(ck_u4* __restrict__ vba, ck_u4* __restri
     }
 }
 
-__global__ __launch_bounds__(CK_WG) void k_ckpt_gather(const TfVoxel* vba, const unsigned* rgb, const int* __restrict__ blockPtr, int nb,
-                                                       ck_u4* __restrict__ stage)
-{
-    ck_copy<true>((ck_u4*)vba, (ck_u4*)rgb, blockPtr, nb, stage);
-}
-
-__global__ __launch_bounds__(CK_WG) void k_ckpt_scatter(TfVoxel* vba, unsigned* rgb, const int* __restrict__ blockPtr, int nb,
-                                                        const ck_u4* __restrict__ stage)
-{
-    ck_copy<false>((ck_u4*)vba, (ck_u4*)rgb, blockPtr, nb, (ck_u4*)stage);
-}
-
-__global__ __launch_bounds__(CK_WG) void k_ckpt_apply(const ck_u2* __restrict__ records, long long n_records, TfHashEntry* __restrict__ hash,
-                                                      unsigned char* __restrict__ visType)
-{
-    for (long long k = (long long)blockIdx.x * CK_WG + threadIdx.x; k < n_records; k += (long long)gridDim.x * CK_WG) {
-        const ck_u2 a = records[3 * k], b = records[3 * k + 1], c = records[3 * k + 2];
-        *reinterpret_cast<ck_u4*>(hash + a.x) = ck_u4{ a.y, b.x, b.y, c.x };
-        visType[a.x] = (unsigned char)c.y;
-    }
-}
-
-// ---- the swapping forms (map checkpoints, version 2 of the file): the same passes with the GlobalCache's two
-// bytes per entry in the record predicate and in the record, a third tally (entries with hasStoredData) from
-// the same ballots, and a second list -- the entry indices of flagged records, in record order -- that the
-// store's gather walks.  The version-1 kernels above are launched as they were.
-// cache: swapState | hasStoredData << 8; sto: the entry's stored block is state
-__device__ __forceinline__ void ck_classify_map(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
-                                                const unsigned char* __restrict__ swapState, const unsigned char* __restrict__ swapFlags,
-                                                int idx, int n_total, ck_u4& e, unsigned& vis, unsigned& cache, bool& rec, bool& blk,
-                                                bool& sto)
-{
-    ck_classify(hash, visType, idx, n_total, e, vis, rec, blk);
-    cache = 0;
-    if (idx < n_total) cache = (unsigned)swapState[idx] | (unsigned)swapFlags[idx] << 8;
-    rec = rec || cache != 0u;                              // (blk implies rec already: ptr >= 0 is not ResetScene's)
-    sto = (cache >> 8) != 0u;
-}
-
-__global__ __launch_bounds__(CK_WG) void k_map_count(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
-                                                     const unsigned char* __restrict__ swapState,
-                                                     const unsigned char* __restrict__ swapFlags, int n_total, int n_blocks,
-                                                     int4* __restrict__ groupCnt, int* __restrict__ bad)
-{
-    __shared__ int4 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        ck_u4 e; unsigned vis, cache; bool rec, blk, sto;
-        ck_classify_map(hash, visType, swapState, swapFlags, g * CK_WG + t, n_total, e, vis, cache, rec, blk, sto);
-        if (blk && (int)e.w >= n_blocks) *bad = 1;
-        const int nr = __popcll(__ballot(rec)), nb = __popcll(__ballot(blk)), ns = __popcll(__ballot(sto));
-        __syncthreads();
-        if ((t & 63) == 0) wcnt[t >> 6] = make_int4(nr, nb, ns, 0);
-        __syncthreads();
-        if (t == 0) {
-            int4 s = make_int4(0, 0, 0, 0);
-            for (int w = 0; w < CK_WG / 64; ++w) { s.x += wcnt[w].x; s.y += wcnt[w].y; s.z += wcnt[w].z; }
-            groupCnt[g] = s;
-        }
-    }
-}
-
-// k_ckpt_prefix over three counts (.w unused)
-__global__ __launch_bounds__(CK_WG) void k_map_prefix(const int4* __restrict__ cnt, int ng, int4* __restrict__ base)
-{
-    __shared__ int4 part[CK_WG];
-    const int t = threadIdx.x, per = (ng + CK_WG - 1) / CK_WG;
-    const int first = min(t * per, ng), last = min(first + per, ng);
-    int4 s = make_int4(0, 0, 0, 0);
-    for (int g = first; g < last; ++g) { s.x += cnt[g].x; s.y += cnt[g].y; s.z += cnt[g].z; }
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int4 run = make_int4(0, 0, 0, 0);
-        for (int k = 0; k < CK_WG; ++k) { const int4 v = part[k]; part[k] = run; run.x += v.x; run.y += v.y; run.z += v.z; }
-        base[ng] = run;
-    }
-    __syncthreads();
-    s = part[t];
-    for (int g = first; g < last; ++g) { base[g] = s; s.x += cnt[g].x; s.y += cnt[g].y; s.z += cnt[g].z; }
-}
-
-__global__ __launch_bounds__(CK_WG) void k_map_records(const TfHashEntry* __restrict__ hash, const unsigned char* __restrict__ visType,
-                                                       const unsigned char* __restrict__ swapState,
-                                                       const unsigned char* __restrict__ swapFlags, int n_total,
-                                                       const int4* __restrict__ base, ck_u2* __restrict__ records,
-                                                       int* __restrict__ blockPtr, int* __restrict__ storedIdx)
-{
-    __shared__ int4 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        const int idx = g * CK_WG + t;
-        ck_u4 e; unsigned vis, cache; bool rec, blk, sto;
-        ck_classify_map(hash, visType, swapState, swapFlags, idx, n_total, e, vis, cache, rec, blk, sto);
-        const unsigned long long mr = __ballot(rec), mb = __ballot(blk), ms = __ballot(sto), below = (1ull << lane) - 1ull;
-        __syncthreads();
-        if (lane == 0) wcnt[w] = make_int4(__popcll(mr), __popcll(mb), __popcll(ms), 0);
-        __syncthreads();
-        int4 b = base[g];
-        for (int k = 0; k < w; ++k) { b.x += wcnt[k].x; b.y += wcnt[k].y; b.z += wcnt[k].z; }
-        if (rec) {
-            ck_u2* r = records + 3 * (size_t)(b.x + __popcll(mr & below));
-            r[0] = ck_u2{ (unsigned)idx, e.x };
-            r[1] = ck_u2{ e.y, e.z };
-            r[2] = ck_u2{ e.w, vis | cache << 8 };         // visType, swapState, hasStoredData, 0
-        }
-        if (blk) blockPtr[b.y + __popcll(mb & below)] = (int)e.w;
-        if (sto) storedIdx[b.z + __popcll(ms & below)] = idx;
-    }
-}
-
-// blocks [0, nb) of the entry-index list between the GlobalCache's store and the staging buffer: ck_copy's
+// blocks [0, nb) of the entry-index list between the GlobalCache's store and the staging buffer: k_ck_copy's
 // shape (16 B per lane, a wave instruction per KiB, contiguous inside a block).  The store is indexed by hash
 // entry, 2 KiB each, so the offset is formed in 64 bits (it passes 4 GiB above 2^21 entries); it is touched
 // once, so its side is nontemporal too.
 // SKIP (the resized load): a list value of -1 names no entry, its block stays in the staging buffer
-template <bool GATHER, bool SKIP = false>
-__device__ __forceinline__ void ck_copy_store(ck_u4* __restrict__ store, const int* __restrict__ storedIdx, int nb,
-                                              ck_u4* __restrict__ stage)
+template <bool GATHER, bool SKIP>
+__global__ __launch_bounds__(CK_WG) void k_ck_copy_store(ck_u4* __restrict__ store, const int* __restrict__ storedIdx, int nb,
+                                                         ck_u4* __restrict__ stage)
 {
     const size_t n = (size_t)nb << 7;
     for (size_t u = (size_t)blockIdx.x * CK_WG + threadIdx.x; u < n; u += (size_t)gridDim.x * CK_WG) {
@@ -264,29 +192,14 @@ __device__ __forceinline__ void ck_copy_store(ck_u4* __restrict__ store, const i
     }
 }
 
-__global__ __launch_bounds__(CK_WG) void k_map_gather(const TfVoxel* store, const int* __restrict__ storedIdx, int nb,
-                                                      ck_u4* __restrict__ stage)
-{
-    ck_copy_store<true>((ck_u4*)store, storedIdx, nb, stage);
-}
-
-__global__ __launch_bounds__(CK_WG) void k_map_scatter(TfVoxel* store, const int* __restrict__ storedIdx, int nb,
-                                                       const ck_u4* __restrict__ stage)
-{
-    ck_copy_store<false>((ck_u4*)store, storedIdx, nb, (ck_u4*)stage);
-}
-
-// k_ckpt_apply with the two cache bytes (swapState / swapFlags were cleared over the whole table before)
-__global__ __launch_bounds__(CK_WG) void k_map_apply(const ck_u2* __restrict__ records, long long n_records, TfHashEntry* __restrict__ hash,
-                                                     unsigned char* __restrict__ visType, unsigned char* __restrict__ swapState,
-                                                     unsigned char* __restrict__ swapFlags)
+__global__ __launch_bounds__(CK_WG) void k_ck_apply(const ck_u2* __restrict__ records, long long n_records, int sw,
+                                                    TfHashEntry* __restrict__ hash, unsigned char* __restrict__ visType,
+                                                    unsigned char* __restrict__ swapState, unsigned char* __restrict__ swapFlags)
 {
     for (long long k = (long long)blockIdx.x * CK_WG + threadIdx.x; k < n_records; k += (long long)gridDim.x * CK_WG) {
-        const ck_u2 a = records[3 * k], b = records[3 * k + 1], c = records[3 * k + 2];
-        *reinterpret_cast<ck_u4*>(hash + a.x) = ck_u4{ a.y, b.x, b.y, c.x };
-        visType[a.x] = (unsigned char)c.y;
-        swapState[a.x] = (unsigned char)(c.y >> 8);
-        swapFlags[a.x] = (unsigned char)(c.y >> 16);
+        const CkRecord r = ck_record_load(records, (size_t)k);
+        *reinterpret_cast<ck_u4*>(hash + r.idx) = r.e;
+        ck_tail_apply(r.tail, (int)r.idx, sw, visType, swapState, swapFlags);
     }
 }
 
@@ -302,14 +215,13 @@ __global__ __launch_bounds__(CK_WG) void k_map_apply(const ck_u2* __restrict__ r
 //                 rotation (this round's minima, the last round's winners, the next round's bids), so no array is
 //                 read and bid into in one launch; the host runs rounds until no record is left: longest_chain
 //                 of them.  A minimum over record numbers does not depend on the order the atomics land in.
-//   k_rz_count  : per 256 records those with m > 0, with ptr >= 0, with a stored block (dropped ones too: their
-//                 blocks lie in the file's second payload); k_map_prefix scans them
-//   k_rz_place  : t(j), ptr'(j), and the two lists the scatters walk: ptr' per active block, t (-1: a dropped
-//                 record's, skipped) per stored block
+//   CkRzPass    : counted -- per 256 records those with m > 0, with ptr >= 0, with a stored block (dropped ones too:
+//                 their blocks lie in the file's second payload); emitted -- t(j), ptr'(j), and the two lists the
+//                 scatters walk: ptr' per active block, t (-1: a dropped record's, skipped) per stored block
 //   k_rz_apply  : hash[t] = {pos, the successor's excess slot + 1, ptr'}, visType and the cache bytes at t
-//   k_rz_vis_*  : the ascending entries with visType > 0, the first vis_capacity of them, by count / prefix / emit
+//   CkVisPass   : the ascending entries with visType > 0, the first vis_capacity of them
 //
-// Everything up to k_rz_count writes scratch only: the fit is checked on its totals before the context is touched.
+// Everything up to CkRzPass's count writes scratch only: the fit is checked on its totals before the context is touched.
 #define RZ_NONE 0x7f7f7f7f                                 // no record (above every record number); memset's 0x7f
 
 __global__ __launch_bounds__(CK_WG) void k_rz_hash(const ck_u2* __restrict__ records, int n, unsigned mask, int sw, int* __restrict__ rzH,
@@ -368,68 +280,33 @@ __global__ __launch_bounds__(CK_WG) void k_rz_round(int n, int r, const int* __r
     }
 }
 
-// does record j use an excess slot, hold a block, name a stored block (after the rounds)
-__device__ __forceinline__ void rz_classify(const ck_u2* __restrict__ records, const int* __restrict__ rzRank, int j, int n, int sw,
-                                            bool& exc, bool& blk, bool& sto)
-{
-    exc = blk = sto = false;
-    if (j < n) {
+// after the rounds: record j uses an excess slot, holds a block, names a stored block.  Emit: rzH becomes ptr'(j)
+// (its h is spent once t is known); rzT[j] = -1 marks a dropped record
+struct CkRzPass {
+    struct Item {};
+    const ck_u2* records;
+    const int* rzRank;
+    int sw, n_buckets, n_excess, n_blocks;
+    int *rzH, *rzT, *blockPtr, *storedIdx;
+
+    __device__ __forceinline__ unsigned classify(int j, bool in, Item&) const
+    {
+        if (!in) return 0u;
         const ck_u2 c = records[3 * (size_t)j + 2];
-        exc = rzRank[j] > 0;
-        blk = (int)c.x >= 0;
-        sto = sw && ((c.y >> 16) & 0xffu) != 0u;
+        const bool exc = rzRank[j] > 0, blk = (int)c.x >= 0, sto = sw && ((c.y >> 16) & 0xffu) != 0u;
+        return (unsigned)exc | (unsigned)blk << 1 | (unsigned)sto << 2;
     }
-}
-
-__global__ __launch_bounds__(CK_WG) void k_rz_count(const ck_u2* __restrict__ records, const int* __restrict__ rzRank, int n, int sw,
-                                                    int4* __restrict__ groupCnt)
-{
-    __shared__ int4 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n + CK_WG - 1) / CK_WG;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        bool exc, blk, sto;
-        rz_classify(records, rzRank, g * CK_WG + t, n, sw, exc, blk, sto);
-        const int ne = __popcll(__ballot(exc)), nb = __popcll(__ballot(blk)), ns = __popcll(__ballot(sto));
-        __syncthreads();
-        if ((t & 63) == 0) wcnt[t >> 6] = make_int4(ne, nb, ns, 0);
-        __syncthreads();
-        if (t == 0) {
-            int4 s = make_int4(0, 0, 0, 0);
-            for (int w = 0; w < CK_WG / 64; ++w) { s.x += wcnt[w].x; s.y += wcnt[w].y; s.z += wcnt[w].z; }
-            groupCnt[g] = s;
-        }
+    __device__ __forceinline__ void emit(int j, const Item&, unsigned bits, int at_exc, int at_blk, int at_sto) const
+    {
+        const int h = rzH[j];
+        const int at = h < 0 ? -1 : (bits & 1u) ? n_buckets + n_excess - 1 - at_exc : h;
+        const int ptr = (bits & 2u) ? n_blocks - 1 - at_blk : -1;
+        rzT[j] = at;
+        rzH[j] = ptr;
+        if (bits & 2u) blockPtr[at_blk] = ptr;
+        if (bits & 4u) storedIdx[at_sto] = at;
     }
-}
-
-// rzH becomes ptr'(j) (its h is spent once t is known); rzT[j] = -1 marks a dropped record
-__global__ __launch_bounds__(CK_WG) void k_rz_place(const ck_u2* __restrict__ records, int n, int sw, const int4* __restrict__ base,
-                                                    int n_buckets, int n_excess, int n_blocks, int* __restrict__ rzH,
-                                                    const int* __restrict__ rzRank, int* __restrict__ rzT, int* __restrict__ blockPtr,
-                                                    int* __restrict__ storedIdx)
-{
-    __shared__ int4 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        const int j = g * CK_WG + t;
-        bool exc, blk, sto;
-        rz_classify(records, rzRank, j, n, sw, exc, blk, sto);
-        const unsigned long long me = __ballot(exc), mb = __ballot(blk), ms = __ballot(sto), below = (1ull << lane) - 1ull;
-        __syncthreads();
-        if (lane == 0) wcnt[w] = make_int4(__popcll(me), __popcll(mb), __popcll(ms), 0);
-        __syncthreads();
-        int4 b = base[g];
-        for (int k = 0; k < w; ++k) { b.x += wcnt[k].x; b.y += wcnt[k].y; b.z += wcnt[k].z; }
-        if (j < n) {
-            const int h = rzH[j];
-            const int at = h < 0 ? -1 : exc ? n_buckets + n_excess - 1 - (b.x + __popcll(me & below)) : h;
-            const int ptr = blk ? n_blocks - 1 - (b.y + __popcll(mb & below)) : -1;
-            rzT[j] = at;
-            rzH[j] = ptr;
-            if (blk) blockPtr[b.y + __popcll(mb & below)] = ptr;
-            if (sto) storedIdx[b.z + __popcll(ms & below)] = at;
-        }
-    }
-}
+};
 
 __global__ __launch_bounds__(CK_WG) void k_rz_apply(const ck_u2* __restrict__ records, int n, int sw, int n_buckets,
                                                     const int* __restrict__ rzPtr, const int* __restrict__ rzSucc,
@@ -440,170 +317,114 @@ __global__ __launch_bounds__(CK_WG) void k_rz_apply(const ck_u2* __restrict__ re
     for (int j = blockIdx.x * CK_WG + threadIdx.x; j < n; j += gridDim.x * CK_WG) {
         const int at = rzT[j];
         if (at < 0) continue;
-        const ck_u2 a = records[3 * (size_t)j], b = records[3 * (size_t)j + 1], c = records[3 * (size_t)j + 2];
+        const CkRecord r = ck_record_load(records, (size_t)j);
         const int succ = rzSucc[j];
         const unsigned offset = succ >= 0 ? (unsigned)(rzT[succ] - n_buckets + 1) : 0u;
-        *reinterpret_cast<ck_u4*>(hash + at) = ck_u4{ a.y, b.x & 0xffffu, offset, (unsigned)rzPtr[j] };
-        visType[at] = (unsigned char)c.y;
-        if (sw) {
-            swapState[at] = (unsigned char)(c.y >> 8);
-            swapFlags[at] = (unsigned char)(c.y >> 16);
-        }
+        *reinterpret_cast<ck_u4*>(hash + at) = ck_u4{ r.e.x, r.e.y & 0xffffu, offset, (unsigned)rzPtr[j] };
+        ck_tail_apply(r.tail, at, sw, visType, swapState, swapFlags);
     }
 }
 
-__global__ __launch_bounds__(CK_WG) void k_rz_vis_count(const unsigned char* __restrict__ visType, int n_total, int2* __restrict__ groupCnt)
-{
-    __shared__ int wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        const int idx = g * CK_WG + t;
-        const int nv = __popcll(__ballot(idx < n_total && visType[idx] != 0));
-        __syncthreads();
-        if ((t & 63) == 0) wcnt[t >> 6] = nv;
-        __syncthreads();
-        if (t == 0) {
-            int s = 0;
-            for (int w = 0; w < CK_WG / 64; ++w) s += wcnt[w];
-            groupCnt[g] = make_int2(s, 0);
-        }
+struct CkVisPass {
+    struct Item {};
+    const unsigned char* visType;
+    int capacity;
+    int* visibleIds;
+
+    __device__ __forceinline__ unsigned classify(int idx, bool in, Item&) const { return in && visType[idx] != 0 ? 1u : 0u; }
+    __device__ __forceinline__ void emit(int idx, const Item&, unsigned bits, int at, int, int) const
+    {
+        if ((bits & 1u) && at < capacity) visibleIds[at] = idx;
     }
-}
+};
 
-__global__ __launch_bounds__(CK_WG) void k_rz_vis_emit(const unsigned char* __restrict__ visType, int n_total, const int2* __restrict__ base,
-                                                       int capacity, int* __restrict__ visibleIds)
-{
-    __shared__ int wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n_total + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        const int idx = g * CK_WG + t;
-        const bool v = idx < n_total && visType[idx] != 0;
-        const unsigned long long mv = __ballot(v);
-        __syncthreads();
-        if (lane == 0) wcnt[w] = __popcll(mv);
-        __syncthreads();
-        int at = base[g].x + __popcll(mv & ((1ull << lane) - 1ull));
-        for (int k = 0; k < w; ++k) at += wcnt[k];
-        if (v && at < capacity) visibleIds[at] = idx;
-    }
-}
-
-// k_map_scatter over a list in which -1 stands for a block that is not carried
-__global__ __launch_bounds__(CK_WG) void k_rz_scatter_store(TfVoxel* store, const int* __restrict__ storedIdx, int nb,
-                                                            const ck_u4* __restrict__ stage)
-{
-    ck_copy_store<false, true>((ck_u4*)store, storedIdx, nb, (ck_u4*)stage);
-}
-
-static int ck_groups(const tf_ctx* c) { return (c->n_total + CK_WG - 1) / CK_WG; }
+// ---- the launchers -----------------------------------------------------------------------------------
+static int ck_groups(int n) { return (n + CK_WG - 1) / CK_WG; }
 static int ck_grid(size_t items) { const size_t g = (items + CK_WG - 1) / CK_WG; return (int)(g < 1 ? 1 : g > 2048 ? 2048 : g); }
 
-// the context's checkpoint scratch, from the first call on: the group counts, their bases + totals and
-// the "not saveable" flag; the device staging buffer and its pinned twin, ckpt_chunk_blocks blocks each
-static hipError_t tfk_ckpt_scratch(tf_ctx* c)
-{
-    if (c->ckptGroup) return hipSuccess;
-    const size_t ng = (size_t)ck_groups(c);
-    const size_t stage = (size_t)c->ckpt_chunk_blocks * TF_SCENE_BLOCK_BYTES * (c->p.voxel_rgb ? 2 : 1);
-    const size_t cnt = c->p.use_swapping ? sizeof(int4) : sizeof(int2);      // three tallies per group with the GlobalCache
-    return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->ckptGroup, cnt * (2 * ng + 2)), TfCtxMem::dev(&c->ckptStage, stage),
-                                           TfCtxMem::pin(&c->ckptPinned, stage, hipHostMallocDefault) }));
-}
-
-static size_t tfk_ckpt_stage_bytes(const tf_ctx* c)
+// what the staging buffer and its pinned twin hold: ckpt_chunk_blocks blocks (with their colour)
+static size_t ck_stage_bytes(const tf_ctx* c)
 {
     return (size_t)c->ckpt_chunk_blocks * TF_SCENE_BLOCK_BYTES * (c->p.voxel_rgb ? 2 : 1);
 }
 
-// count + prefix; totals[0] = {records, blocks}, totals[1].x = the "not saveable" flag (device addresses)
-static hipError_t tfk_ckpt_count(tf_ctx* c, const int2** totals)
+// the context's checkpoint scratch, from the first call on: a pass's scratch over the n_total entries -- the group
+// counts, their bases + totals -- and the "not saveable" flag; the device staging buffer and its pinned twin
+static hipError_t tfk_ckpt_scratch(tf_ctx* c)
 {
-    const int ng = ck_groups(c);
-    int2* cnt = c->ckptGroup;
-    int2* base = cnt + ng;
-    int* bad = (int*)(base + ng + 1);
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int2), c->stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ckpt_count, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->n_total,
-                       c->p.n_blocks, cnt, bad);
-    hipLaunchKernelGGL(k_ckpt_prefix, dim3(1), dim3(CK_WG), 0, c->stream, cnt, ng, base);
-    *totals = base + ng;
+    if (c->ckptGroup) return hipSuccess;
+    const size_t ng = (size_t)ck_groups(c->n_total);
+    return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->ckptGroup, sizeof(int4) * (2 * ng + 2)),
+                                           TfCtxMem::dev(&c->ckptStage, ck_stage_bytes(c)),
+                                           TfCtxMem::pin(&c->ckptPinned, ck_stage_bytes(c), hipHostMallocDefault) }));
+}
+
+// a pass over n items with its scratch grp: [0, ng) the group counts, [ng, 2 ng] their bases and the totals.
+// count + prefix (nothing but grp is written); then, once the caller has seen the totals, emit
+template <class Pass>
+static hipError_t tfk_ck_count(tf_ctx* c, const Pass& p, int n, int4* grp)
+{
+    hipLaunchKernelGGL((k_ck_pass<false, Pass>), dim3(ck_grid((size_t)n)), dim3(CK_WG), 0, c->stream, p, n, grp);
+    hipLaunchKernelGGL(k_ck_prefix, dim3(1), dim3(CK_WG), 0, c->stream, (const int4*)grp, ck_groups(n), grp + ck_groups(n));
     return hipGetLastError();
 }
 
-// after tfk_ckpt_count: records (n_records x 24 B) and the stored blocks' ptr list, device buffers of the caller
-static hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr)
+template <class Pass>
+static hipError_t tfk_ck_emit(tf_ctx* c, const Pass& p, int n, int4* grp)
 {
-    hipLaunchKernelGGL(k_ckpt_records, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->n_total,
-                       c->ckptGroup + ck_groups(c), (ck_u2*)records, blockPtr);
+    hipLaunchKernelGGL((k_ck_pass<true, Pass>), dim3(ck_grid((size_t)n)), dim3(CK_WG), 0, c->stream, p, n, grp);
     return hipGetLastError();
 }
 
-// nb <= ckpt_chunk_blocks blocks of the list into / out of the staging buffer
-static hipError_t tfk_ckpt_gather(tf_ctx* c, const int* blockPtr, int nb)
+static CkSavePass ck_save_pass(const tf_ctx* c)
 {
-    hipLaunchKernelGGL(k_ckpt_gather, dim3(ck_grid((size_t)nb * 256)), dim3(CK_WG), 0, c->stream, c->vba,
-                       c->p.voxel_rgb ? c->vba_rgb : nullptr, blockPtr, nb, (ck_u4*)c->ckptStage);
+    return CkSavePass{ c->hash, c->visType, c->swapState, c->swapFlags, c->p.use_swapping != 0, c->p.n_blocks, nullptr, nullptr, nullptr, nullptr };
+}
+
+// count + prefix; totals[0] = {records, blocks, flagged (0 without swapping), -}, totals[1].x = the "not saveable"
+// flag (device addresses)
+static hipError_t tfk_ckpt_count(tf_ctx* c, const int4** totals)
+{
+    CkSavePass p = ck_save_pass(c);
+    *totals = c->ckptGroup + 2 * ck_groups(c->n_total);
+    p.bad = (int*)(*totals + 1);
+    const hipError_t e = hipMemsetAsync(p.bad, 0, sizeof(int4), c->stream);
+    return e != hipSuccess ? e : tfk_ck_count(c, p, c->n_total, c->ckptGroup);
+}
+
+// after tfk_ckpt_count: records (n_records x 24 B), the stored blocks' ptr list and (swapping) the flagged entries'
+// index list, device buffers of the caller
+static hipError_t tfk_ckpt_records(tf_ctx* c, void* records, int* blockPtr, int* storedIdx)
+{
+    CkSavePass p = ck_save_pass(c);
+    p.records = (ck_u2*)records;
+    p.blockPtr = blockPtr;
+    p.storedIdx = storedIdx;
+    return tfk_ck_emit(c, p, c->n_total, c->ckptGroup);
+}
+
+// nb <= ckpt_chunk_blocks blocks of the ptr list into (gather) / out of the staging buffer
+static hipError_t tfk_ckpt_copy(tf_ctx* c, bool gather, const int* blockPtr, int nb)
+{
+    const auto k = gather ? k_ck_copy<true> : k_ck_copy<false>;
+    hipLaunchKernelGGL(k, dim3(ck_grid((size_t)nb * 256)), dim3(CK_WG), 0, c->stream, (ck_u4*)c->vba,
+                       (ck_u4*)(c->p.voxel_rgb ? c->vba_rgb : nullptr), blockPtr, nb, (ck_u4*)c->ckptStage);
     return hipGetLastError();
 }
 
-static hipError_t tfk_ckpt_scatter(tf_ctx* c, const int* blockPtr, int nb)
+// ... and stored blocks of the entry list (skip: -1 in it names no entry)
+static hipError_t tfk_ckpt_copy_store(tf_ctx* c, bool gather, bool skip, const int* storedIdx, int nb)
 {
-    hipLaunchKernelGGL(k_ckpt_scatter, dim3(ck_grid((size_t)nb * 256)), dim3(CK_WG), 0, c->stream, c->vba,
-                       c->p.voxel_rgb ? c->vba_rgb : nullptr, blockPtr, nb, (const ck_u4*)c->ckptStage);
-    return hipGetLastError();
-}
-
-static hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_records)
-{
-    if (n_records == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ckpt_apply, dim3(ck_grid((size_t)n_records)), dim3(CK_WG), 0, c->stream, (const ck_u2*)records, n_records, c->hash,
-                       c->visType);
-    return hipGetLastError();
-}
-
-// the swapping forms: totals[0] = {records, blocks, flagged, -}, totals[1].x = the "not saveable" flag
-static hipError_t tfk_map_count(tf_ctx* c, const int4** totals)
-{
-    const int ng = ck_groups(c);
-    int4* cnt = (int4*)c->ckptGroup;
-    int4* base = cnt + ng;
-    int* bad = (int*)(base + ng + 1);
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(int4), c->stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_map_count, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->swapState,
-                       c->swapFlags, c->n_total, c->p.n_blocks, cnt, bad);
-    hipLaunchKernelGGL(k_map_prefix, dim3(1), dim3(CK_WG), 0, c->stream, cnt, ng, base);
-    *totals = base + ng;
-    return hipGetLastError();
-}
-
-static hipError_t tfk_map_records(tf_ctx* c, void* records, int* blockPtr, int* storedIdx)
-{
-    hipLaunchKernelGGL(k_map_records, dim3(ck_grid((size_t)c->n_total)), dim3(CK_WG), 0, c->stream, c->hash, c->visType, c->swapState,
-                       c->swapFlags, c->n_total, (const int4*)c->ckptGroup + ck_groups(c), (ck_u2*)records, blockPtr, storedIdx);
-    return hipGetLastError();
-}
-
-// nb <= ckpt_chunk_blocks stored blocks of the entry list into / out of the staging buffer
-static hipError_t tfk_map_gather(tf_ctx* c, const int* storedIdx, int nb)
-{
-    hipLaunchKernelGGL(k_map_gather, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, c->swapStore, storedIdx, nb,
+    const auto k = gather ? k_ck_copy_store<true, false> : skip ? k_ck_copy_store<false, true> : k_ck_copy_store<false, false>;
+    hipLaunchKernelGGL(k, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, (ck_u4*)c->swapStore, storedIdx, nb,
                        (ck_u4*)c->ckptStage);
     return hipGetLastError();
 }
 
-static hipError_t tfk_map_scatter(tf_ctx* c, const int* storedIdx, int nb, bool skip = false)
-{
-    hipLaunchKernelGGL(skip ? k_rz_scatter_store : k_map_scatter, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, c->swapStore,
-                       storedIdx, nb, (const ck_u4*)c->ckptStage);
-    return hipGetLastError();
-}
-
-static hipError_t tfk_map_apply(tf_ctx* c, const void* records, long long n_records)
+static hipError_t tfk_ckpt_apply(tf_ctx* c, const void* records, long long n_records, int sw)
 {
     if (n_records == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_map_apply, dim3(ck_grid((size_t)n_records)), dim3(CK_WG), 0, c->stream, (const ck_u2*)records, n_records, c->hash,
+    hipLaunchKernelGGL(k_ck_apply, dim3(ck_grid((size_t)n_records)), dim3(CK_WG), 0, c->stream, (const ck_u2*)records, n_records, sw, c->hash,
                        c->visType, c->swapState, c->swapFlags);
     return hipGetLastError();
 }
@@ -638,29 +459,40 @@ static tf_status ck_timed_kernels(tf_ctx* c, int which, F launch)
     return TF_OK;
 }
 
-// `bytes` of device memory to the file through the pinned buffer, a staging chunk at a time
-// (bound > 0: the bytes are a list of ints that must lie in [0, bound), as load will require)
-static tf_status ckpt_d2h_write(tf_ctx* c, FILE* f, const void* dev, size_t bytes, int bound = 0)
+// `bytes` of device memory through the pinned buffer, a staging chunk at a time: sink(the chunk, its offset, its
+// size) takes each on the host (and accounts for its own time)
+template <class Sink>
+static tf_status ckpt_d2h(tf_ctx* c, const void* dev, size_t bytes, Sink sink)
 {
-    const size_t cap = tfk_ckpt_stage_bytes(c);
+    const size_t cap = ck_stage_bytes(c);
     for (size_t o = 0; o < bytes; o += cap) {
         const size_t n = bytes - o < cap ? bytes - o : cap;
         const double t0 = ck_now_ms();
         TF_CHECK(hipMemcpyAsync(c->ckptPinned, (const char*)dev + o, n, hipMemcpyDeviceToHost, c->stream));
         TF_CHECK(hipStreamSynchronize(c->stream));
-        const double t1 = ck_now_ms();
-        if (bound > 0 && !tf_scene_list_within(c->ckptPinned, n / 4, bound)) return TF_INVALID_ARG;
-        if (fwrite(c->ckptPinned, 1, n, f) != n) return TF_INVALID_ARG;
-        c->ckpt_ms[CK_T_COPY] += t1 - t0;
-        c->ckpt_ms[CK_T_FILE] += ck_now_ms() - t1;
+        c->ckpt_ms[CK_T_COPY] += ck_now_ms() - t0;
+        const tf_status s = sink((const unsigned char*)c->ckptPinned, o, n);
+        if (s != TF_OK) return s;
     }
     return TF_OK;
+}
+
+// ... to the file (bound > 0: the bytes are a list of ints that must lie in [0, bound), as load will require)
+static tf_status ckpt_d2h_write(tf_ctx* c, FILE* f, const void* dev, size_t bytes, int bound = 0)
+{
+    return ckpt_d2h(c, dev, bytes, [&](const unsigned char* chunk, size_t, size_t n) -> tf_status {
+        const double t0 = ck_now_ms();
+        if (bound > 0 && !tf_scene_list_within(chunk, n / 4, bound)) return TF_INVALID_ARG;
+        if (fwrite(chunk, 1, n, f) != n) return TF_INVALID_ARG;
+        c->ckpt_ms[CK_T_FILE] += ck_now_ms() - t0;
+        return TF_OK;
+    });
 }
 
 // ... and host bytes to device memory the same way
 static tf_status ckpt_h2d(tf_ctx* c, void* dev, const unsigned char* host, size_t bytes)
 {
-    const size_t cap = tfk_ckpt_stage_bytes(c);
+    const size_t cap = ck_stage_bytes(c);
     for (size_t o = 0; o < bytes; o += cap) {
         const size_t n = bytes - o < cap ? bytes - o : cap;
         const double t0 = ck_now_ms();
@@ -668,6 +500,25 @@ static tf_status ckpt_h2d(tf_ctx* c, void* dev, const unsigned char* host, size_
         TF_CHECK(hipMemcpyAsync((char*)dev + o, c->ckptPinned, n, hipMemcpyHostToDevice, c->stream));
         TF_CHECK(hipStreamSynchronize(c->stream));
         c->ckpt_ms[CK_T_COPY] += ck_now_ms() - t0;
+    }
+    return TF_OK;
+}
+
+// one block payload, n blocks of block_bytes each in list order, between the file and where the list says, in chunks
+// of at most ckpt_chunk_blocks blocks through the staging buffer; kernels(b0, nb) enqueues the copy of blocks
+// [b0, b0 + nb) of the list.  Save (f): the gather, then the chunk D2H and into the file.  Load (data, the payload in
+// memory): the chunk H2D, then the scatter -- waited for, so the staging buffer is free again.
+template <class K>
+static tf_status ckpt_payload(tf_ctx* c, long long n, size_t block_bytes, FILE* f, const unsigned char* data, K kernels)
+{
+    for (long long b0 = 0; b0 < n; b0 += c->ckpt_chunk_blocks) {
+        const int nb = (int)(n - b0 < c->ckpt_chunk_blocks ? n - b0 : c->ckpt_chunk_blocks);
+        tf_status s = TF_OK;
+        if (data) s = ckpt_h2d(c, c->ckptStage, data + (size_t)b0 * block_bytes, (size_t)nb * block_bytes);
+        if (s == TF_OK) s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return kernels(b0, nb); });
+        if (s == TF_OK && f) s = ckpt_d2h_write(c, f, c->ckptStage, (size_t)nb * block_bytes);
+        if (s != TF_OK) return s;
+        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)block_bytes;        // read + written
     }
     return TF_OK;
 }
@@ -697,28 +548,16 @@ static tf_status scene_save(tf_ctx* c, FILE* f)
     info.lastFreeExcessListId = st->lastFreeExcessListId;
     info.noVisibleEntries = st->noVisibleEntries;
     memcpy(info.pose, st->pose, sizeof(info.pose));
-    if (sw) {
-        const int4* totals_dev = nullptr;
-        s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_map_count(c, &totals_dev); });
-        if (s != TF_OK) return s;
-        int4 totals[2];
-        TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
-        TF_CHECK(hipStreamSynchronize(c->stream));
-        if (totals[1].x) return TF_INVALID_ARG;
-        info.n_records = totals[0].x;
-        info.n_blocks_stored = totals[0].y;
-        minfo.n_cache_blocks = totals[0].z;
-    } else {
-        const int2* totals_dev = nullptr;
-        s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_count(c, &totals_dev); });
-        if (s != TF_OK) return s;
-        int2 totals[2];
-        TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
-        TF_CHECK(hipStreamSynchronize(c->stream));
-        if (totals[1].x) return TF_INVALID_ARG;            // an entry's ptr lies outside the VBA (uploaded tables)
-        info.n_records = totals[0].x;
-        info.n_blocks_stored = totals[0].y;
-    }
+    const int4* totals_dev = nullptr;
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_count(c, &totals_dev); });
+    if (s != TF_OK) return s;
+    int4 totals[2];
+    TF_CHECK(hipMemcpyAsync(totals, totals_dev, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    if (totals[1].x) return TF_INVALID_ARG;                // an entry's ptr lies outside the VBA (uploaded tables)
+    info.n_records = totals[0].x;
+    info.n_blocks_stored = totals[0].y;
+    minfo.n_cache_blocks = totals[0].z;                    // (0 without swapping)
     TfSceneLayout lay;
     if (!tf_map_layout(&minfo, &lay)) return TF_INVALID_ARG;       // counters outside their lists (tf_set_counters)
     info.file_bytes = (long long)lay.file_bytes;
@@ -735,42 +574,32 @@ static tf_status scene_save(tf_ctx* c, FILE* f)
     TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
     TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
     if (sw) TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * (size_t)minfo.n_cache_blocks)));
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return sw ? tfk_map_records(c, rec_dev, ptr_dev, sto_dev) : tfk_ckpt_records(c, rec_dev, ptr_dev); });
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ckpt_records(c, rec_dev, ptr_dev, sto_dev); });
     if (s != TF_OK) return s;
     {   // the record table: to the host whole (24 B per record), checked by load's own rule before any block
         // moves -- chain offsets, duplicate ptr (tables that came through tf_upload) -- then summed and written
         std::vector<unsigned char> rec(rec_bytes);
-        double t0 = ck_now_ms();
-        const size_t cap = tfk_ckpt_stage_bytes(c);
-        for (size_t o = 0; o < rec_bytes; o += cap) {
-            const size_t n = rec_bytes - o < cap ? rec_bytes - o : cap;
-            TF_CHECK(hipMemcpyAsync(c->ckptPinned, (const char*)rec_dev + o, n, hipMemcpyDeviceToHost, c->stream));
-            TF_CHECK(hipStreamSynchronize(c->stream));
-            memcpy(rec.data() + o, c->ckptPinned, n);
-        }
-        double t1 = ck_now_ms();
-        c->ckpt_ms[CK_T_COPY] += t1 - t0;
+        s = ckpt_d2h(c, rec_dev, rec_bytes, [&](const unsigned char* chunk, size_t o, size_t n) -> tf_status {
+            const double t0 = ck_now_ms();
+            memcpy(rec.data() + o, chunk, n);
+            c->ckpt_ms[CK_T_COPY] += ck_now_ms() - t0;
+            return TF_OK;
+        });
+        if (s != TF_OK) return s;
+        const double t1 = ck_now_ms();
         s = sw ? tf_map_records_check(rec.data(), info.n_records, &info.params, info.n_blocks_stored, minfo.n_cache_blocks)
                : tf_scene_records_check(rec.data(), info.n_records, &info.params, info.n_blocks_stored);
         if (s != TF_OK) return s;
         records_crc = tf_scene_crc32(0u, rec.data(), rec_bytes);
-        t0 = ck_now_ms();
+        const double t0 = ck_now_ms();
         c->ckpt_ms[CK_T_CHECK] += t0 - t1;
         if (fwrite(rec.data(), 1, rec_bytes, f) != rec_bytes) return TF_INVALID_ARG;
         c->ckpt_ms[CK_T_FILE] += ck_now_ms() - t0;
     }
-    for (long long b0 = 0; b0 < info.n_blocks_stored && s == TF_OK; b0 += c->ckpt_chunk_blocks) {
-        const int nb = (int)(info.n_blocks_stored - b0 < c->ckpt_chunk_blocks ? info.n_blocks_stored - b0 : c->ckpt_chunk_blocks);
-        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_ckpt_gather(c, ptr_dev + b0, nb); });
-        if (s == TF_OK) s = ckpt_d2h_write(c, f, c->ckptStage, (size_t)nb * lay.block_bytes);
-        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)lay.block_bytes;     // read + written
-    }
-    for (long long b0 = 0; b0 < minfo.n_cache_blocks && s == TF_OK; b0 += c->ckpt_chunk_blocks) {      // the GlobalCache's
-        const int nb = (int)(minfo.n_cache_blocks - b0 < c->ckpt_chunk_blocks ? minfo.n_cache_blocks - b0 : c->ckpt_chunk_blocks);
-        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_map_gather(c, sto_dev + b0, nb); });
-        if (s == TF_OK) s = ckpt_d2h_write(c, f, c->ckptStage, (size_t)nb * TF_SCENE_BLOCK_BYTES);
-        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)TF_SCENE_BLOCK_BYTES;
-    }
+    s = ckpt_payload(c, info.n_blocks_stored, lay.block_bytes, f, nullptr,
+                     [&](long long b0, int nb) { return tfk_ckpt_copy(c, true, ptr_dev + b0, nb); });
+    if (s == TF_OK) s = ckpt_payload(c, minfo.n_cache_blocks, TF_SCENE_BLOCK_BYTES, f, nullptr,          // the GlobalCache's
+                                     [&](long long b0, int nb) { return tfk_ckpt_copy_store(c, true, false, sto_dev + b0, nb); });
     if (s == TF_OK) s = ckpt_d2h_write(c, f, c->visibleIds, 4 * lay.n_vis, c->n_total);
     if (s == TF_OK) s = ckpt_d2h_write(c, f, c->allocList, 4 * lay.n_alloc, c->p.n_blocks);
     if (s == TF_OK) s = ckpt_d2h_write(c, f, c->excessList, 4 * lay.n_excess, c->p.n_excess);
@@ -815,66 +644,18 @@ extern "C" tf_status tf_scene_save(tf_ctx* c, const char* path)
 
 static bool bits_equal(float a, float b) { return memcmp(&a, &b, sizeof(float)) == 0; }
 
-// the two halves every load ends with (below scene_load)
-static tf_status ckpt_load_blocks(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
-                                  const int* ptr_dev, const int* sto_dev, bool skip);
-static tf_status ckpt_load_finish(tf_ctx* c, const unsigned char* data, const struct tf_scene_file_info& info, const TfSceneLayout& lay,
-                                  int lastFreeBlockId, int lastFreeExcessListId, int noVisibleEntries);
-
-// the validated file into the context (nothing here fails on the file's contents)
-static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay)
+// what every load opens its writes to the context with: a full ResetScene (hash, VBA, colour, both lists (identity),
+// block grid cells), visType zeroed; swapping: the loader's own states and flags of entries the file does not name
+// must not survive; the store itself is not cleared: a stored block whose flag is 0 is read by nobody
+static tf_status ckpt_clear_context(tf_ctx* c, bool sw)
 {
-    TfCtxMem tmp(c->mem.fns());                            // the record table and the lists, freed when this returns
-    unsigned char* rec_dev = nullptr;
-    int* ptr_dev = nullptr;
-    int* sto_dev = nullptr;
-    const struct tf_scene_file_info& info = minfo.scene;
-    const bool sw = minfo.version == (int)TF_MAP_VERSION;
-    TF_CHECK(tfk_ckpt_scratch(c));
-    TF_CHECK(tfk_reset_scene(c));                          // full: hash, VBA, colour, both lists (identity), block grid cells
+    TF_CHECK(tfk_reset_scene(c));
     TF_CHECK(hipMemsetAsync(c->visType, 0, (size_t)c->n_total, c->stream));
-    if (sw) {   // the loader's own states and flags of entries the file does not name must not survive; the store
-                // itself is not cleared: a stored block whose flag is 0 is read by nobody
+    if (sw) {
         TF_CHECK(hipMemsetAsync(c->swapState, 0, (size_t)c->n_total, c->stream));
         TF_CHECK(hipMemsetAsync(c->swapFlags, 0, (size_t)c->n_total, c->stream));
     }
-    const size_t rec_bytes = (size_t)info.n_records * TF_SCENE_RECORD_BYTES;
-    TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
-    TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
-    tf_status s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
-    if (s != TF_OK) return s;
-    {   // the stored blocks' ptr, in record order; version 2: and the entries with a block in the GlobalCache
-        std::vector<int> ptrs, stored;
-        ptrs.reserve((size_t)info.n_blocks_stored);
-        stored.reserve((size_t)minfo.n_cache_blocks);
-        const unsigned char* r = data + lay.records_off;
-        for (long long k = 0; k < info.n_records; ++k, r += TF_SCENE_RECORD_BYTES) {
-            int idx, ptr;
-            memcpy(&idx, r, sizeof(int));
-            memcpy(&ptr, r + 16, sizeof(int));
-            if (ptr >= 0) ptrs.push_back(ptr);
-            if (sw && r[22]) stored.push_back(idx);
-        }
-        s = ckpt_h2d(c, ptr_dev, (const unsigned char*)ptrs.data(), sizeof(int) * ptrs.size());
-        if (s != TF_OK) return s;
-        if (sw) {
-            TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * stored.size())));
-            s = ckpt_h2d(c, sto_dev, (const unsigned char*)stored.data(), sizeof(int) * stored.size());
-            if (s != TF_OK) return s;
-        }
-    }
-    s = ckpt_load_blocks(c, data, minfo, lay, ptr_dev, sto_dev, false);
-    if (s != TF_OK) return s;
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] {              // the block grid from the hash, as after a hash upload
-        const hipError_t e = sw ? tfk_map_apply(c, rec_dev, info.n_records) : tfk_ckpt_apply(c, rec_dev, info.n_records);
-        return e == hipSuccess ? tfk_grid_rebuild(c) : e;
-    });
-    if (s != TF_OK) return s;
-    s = ckpt_h2d(c, c->visibleIds, data + lay.vis_off, 4 * lay.n_vis);
-    if (s == TF_OK) s = ckpt_h2d(c, c->allocList, data + lay.alloc_off, 4 * lay.n_alloc);
-    if (s == TF_OK) s = ckpt_h2d(c, c->excessList, data + lay.excess_off, 4 * lay.n_excess);
-    if (s != TF_OK) return s;
-    return ckpt_load_finish(c, data, info, lay, info.lastFreeBlockId, info.lastFreeExcessListId, info.noVisibleEntries);
+    return TF_OK;
 }
 
 // the file's two block payloads through the staging buffer to where the lists say: active blocks to ptr * 512 (and
@@ -882,25 +663,11 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
 static tf_status ckpt_load_blocks(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
                                   const int* ptr_dev, const int* sto_dev, bool skip)
 {
-    const struct tf_scene_file_info& info = minfo.scene;
-    tf_status s = TF_OK;
-    for (long long b0 = 0; b0 < info.n_blocks_stored; b0 += c->ckpt_chunk_blocks) {
-        const int nb = (int)(info.n_blocks_stored - b0 < c->ckpt_chunk_blocks ? info.n_blocks_stored - b0 : c->ckpt_chunk_blocks);
-        s = ckpt_h2d(c, c->ckptStage, data + lay.blocks_off + (size_t)b0 * lay.block_bytes, (size_t)nb * lay.block_bytes);
-        if (s != TF_OK) return s;
-        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_ckpt_scatter(c, ptr_dev + b0, nb); });   // (waited for: the
-        if (s != TF_OK) return s;                                                                          // staging buffer is free again)
-        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)lay.block_bytes;
-    }
-    for (long long b0 = 0; b0 < minfo.n_cache_blocks; b0 += c->ckpt_chunk_blocks) {        // the GlobalCache's, to store + index * 512
-        const int nb = (int)(minfo.n_cache_blocks - b0 < c->ckpt_chunk_blocks ? minfo.n_cache_blocks - b0 : c->ckpt_chunk_blocks);
-        s = ckpt_h2d(c, c->ckptStage, data + lay.stored_off + (size_t)b0 * TF_SCENE_BLOCK_BYTES, (size_t)nb * TF_SCENE_BLOCK_BYTES);
-        if (s != TF_OK) return s;
-        s = ck_timed_kernels(c, CK_T_BLOCKS, [&] { return tfk_map_scatter(c, sto_dev + b0, nb, skip); });
-        if (s != TF_OK) return s;
-        c->ckpt_ms[CK_T_BLOCK_BYTES] += 2.0 * (double)nb * (double)TF_SCENE_BLOCK_BYTES;
-    }
-    return TF_OK;
+    const tf_status s = ckpt_payload(c, minfo.scene.n_blocks_stored, lay.block_bytes, nullptr, data + lay.blocks_off,
+                                     [&](long long b0, int nb) { return tfk_ckpt_copy(c, false, ptr_dev + b0, nb); });
+    if (s != TF_OK) return s;
+    return ckpt_payload(c, minfo.n_cache_blocks, TF_SCENE_BLOCK_BYTES, nullptr, data + lay.stored_off,
+                        [&](long long b0, int nb) { return tfk_ckpt_copy_store(c, false, skip, sto_dev + b0, nb); });
 }
 
 // the end of a load: the file's previous maps, pose and frame counter; the counters as given
@@ -937,6 +704,57 @@ static tf_status ckpt_load_finish(tf_ctx* c, const unsigned char* data, const st
     return s;
 }
 
+// the validated file into the context (nothing here fails on the file's contents)
+static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay)
+{
+    TfCtxMem tmp(c->mem.fns());                            // the record table and the lists, freed when this returns
+    unsigned char* rec_dev = nullptr;
+    int* ptr_dev = nullptr;
+    int* sto_dev = nullptr;
+    const struct tf_scene_file_info& info = minfo.scene;
+    const bool sw = minfo.version == (int)TF_MAP_VERSION;
+    TF_CHECK(tfk_ckpt_scratch(c));
+    tf_status s = ckpt_clear_context(c, sw);
+    if (s != TF_OK) return s;
+    const size_t rec_bytes = (size_t)info.n_records * TF_SCENE_RECORD_BYTES;
+    TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&ptr_dev, sizeof(int) * (size_t)info.n_blocks_stored)));
+    s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
+    if (s != TF_OK) return s;
+    {   // the stored blocks' ptr, in record order; version 2: and the entries with a block in the GlobalCache
+        std::vector<int> ptrs, stored;
+        ptrs.reserve((size_t)info.n_blocks_stored);
+        stored.reserve((size_t)minfo.n_cache_blocks);
+        const unsigned char* r = data + lay.records_off;
+        for (long long k = 0; k < info.n_records; ++k, r += TF_SCENE_RECORD_BYTES) {
+            int idx, ptr;
+            memcpy(&idx, r, sizeof(int));
+            memcpy(&ptr, r + 16, sizeof(int));
+            if (ptr >= 0) ptrs.push_back(ptr);
+            if (sw && r[22]) stored.push_back(idx);
+        }
+        s = ckpt_h2d(c, ptr_dev, (const unsigned char*)ptrs.data(), sizeof(int) * ptrs.size());
+        if (s != TF_OK) return s;
+        if (sw) {
+            TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * stored.size())));
+            s = ckpt_h2d(c, sto_dev, (const unsigned char*)stored.data(), sizeof(int) * stored.size());
+            if (s != TF_OK) return s;
+        }
+    }
+    s = ckpt_load_blocks(c, data, minfo, lay, ptr_dev, sto_dev, false);
+    if (s != TF_OK) return s;
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {              // the block grid from the hash, as after a hash upload
+        const hipError_t e = tfk_ckpt_apply(c, rec_dev, info.n_records, sw);
+        return e == hipSuccess ? tfk_grid_rebuild(c) : e;
+    });
+    if (s != TF_OK) return s;
+    s = ckpt_h2d(c, c->visibleIds, data + lay.vis_off, 4 * lay.n_vis);
+    if (s == TF_OK) s = ckpt_h2d(c, c->allocList, data + lay.alloc_off, 4 * lay.n_alloc);
+    if (s == TF_OK) s = ckpt_h2d(c, c->excessList, data + lay.excess_off, 4 * lay.n_excess);
+    if (s != TF_OK) return s;
+    return ckpt_load_finish(c, data, info, lay, info.lastFreeBlockId, info.lastFreeExcessListId, info.noVisibleEntries);
+}
+
 // the validated file into a context of other capacities: the placement into scratch, the fit check, then the commit
 // in scene_load's order.  TF_CAPACITY leaves the context as it was.
 static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
@@ -949,7 +767,7 @@ static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const 
     const struct tf_scene_file_info& info = minfo.scene;
     const int sw = minfo.version == (int)TF_MAP_VERSION;
     if (info.n_records > 0x7fffffffll / 4) return TF_INVALID_ARG;      // (a valid file has at most n_total of them)
-    const int n = (int)info.n_records, ng = (n + CK_WG - 1) / CK_WG, nbk = c->p.n_buckets;
+    const int n = (int)info.n_records, ng = ck_groups(n), nbk = c->p.n_buckets;
     const size_t rec_bytes = (size_t)n * TF_SCENE_RECORD_BYTES;
     TF_CHECK(tfk_ckpt_scratch(c));
     TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
@@ -957,7 +775,7 @@ static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const 
     TF_CHECK(tf_mem_hip(tmp.alloc(&sto_dev, sizeof(int) * (size_t)minfo.n_cache_blocks)));
     TF_CHECK(tf_mem_hip(tmp.alloc(&rz, sizeof(int) * 4 * (size_t)n)));             // h / ptr', rank, successor, t per record
     TF_CHECK(tf_mem_hip(tmp.alloc(&bid, sizeof(int) * 3 * (size_t)nbk)));          // the rounds' three bucket arrays
-    TF_CHECK(tf_mem_hip(tmp.alloc(&grp, sizeof(int4) * (2 * (size_t)ng + 1))));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&grp, sizeof(int4) * (2 * (size_t)ng + 1))));    // the placement pass's scratch
     TF_CHECK(tf_mem_hip(tmp.alloc(&tally, sizeof(int) * 4)));                      // carried, carried with a stored block, left
     int *rzH = rz, *rzRank = rz + n, *rzSucc = rz + 2 * (size_t)n, *rzT = rz + 3 * (size_t)n;
     tf_status s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
@@ -990,11 +808,8 @@ static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const 
         TF_CHECK(hipMemcpyAsync(&left, tally + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         TF_CHECK(hipStreamSynchronize(c->stream));
     }
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
-        hipLaunchKernelGGL(k_rz_count, grid, wg, 0, c->stream, rec, rzRank, n, sw, grp);
-        hipLaunchKernelGGL(k_map_prefix, dim3(1), wg, 0, c->stream, grp, ng, grp + ng);
-        return hipGetLastError();
-    });
+    const CkRzPass place = { rec, rzRank, sw, nbk, c->p.n_excess, c->p.n_blocks, rzH, rzT, ptr_dev, sto_dev };
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ck_count(c, place, n, grp); });
     if (s != TF_OK) return s;
     int4 totals;                                           // excess slots, active blocks, stored blocks in the file
     TF_CHECK(hipMemcpyAsync(&totals, grp + 2 * (size_t)ng, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
@@ -1010,37 +825,24 @@ static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const 
     if (totals.y != info.n_blocks_stored || totals.z != minfo.n_cache_blocks) return TF_INVALID_ARG;      // (the validation's counts)
     if (totals.y > c->p.n_blocks || totals.x > c->p.n_excess) return TF_CAPACITY;
     // ---- the commit ----
-    TF_CHECK(tfk_reset_scene(c));                          // full: hash, VBA, colour, both lists (identity), block grid cells
-    TF_CHECK(hipMemsetAsync(c->visType, 0, (size_t)c->n_total, c->stream));
-    if (sw) {
-        TF_CHECK(hipMemsetAsync(c->swapState, 0, (size_t)c->n_total, c->stream));
-        TF_CHECK(hipMemsetAsync(c->swapFlags, 0, (size_t)c->n_total, c->stream));
-    }
-    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
-        hipLaunchKernelGGL(k_rz_place, grid, wg, 0, c->stream, rec, n, sw, (const int4*)(grp + ng), nbk, c->p.n_excess, c->p.n_blocks, rzH,
-                           rzRank, rzT, ptr_dev, sto_dev);
-        return hipGetLastError();
-    });
+    s = ckpt_clear_context(c, sw != 0);
+    if (s != TF_OK) return s;
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ck_emit(c, place, n, grp); });
     if (s != TF_OK) return s;
     s = ckpt_load_blocks(c, data, minfo, lay, ptr_dev, sto_dev, true);
     if (s != TF_OK) return s;
-    int2* vcnt = (int2*)c->ckptGroup;                      // the context's own group scratch: a count per 256 entries
-    const int ngt = ck_groups(c);
+    const CkVisPass vis = { c->visType, c->p.vis_capacity, c->visibleIds };        // over the context's own group scratch
     s = ck_timed_kernels(c, CK_T_INDEX, [&] {
         hipLaunchKernelGGL(k_rz_apply, grid, wg, 0, c->stream, rec, n, sw, nbk, rzH, rzSucc, rzT, c->hash, c->visType, c->swapState,
                            c->swapFlags);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = tfk_grid_rebuild(c);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_rz_vis_count, dim3(ck_grid((size_t)c->n_total)), wg, 0, c->stream, c->visType, c->n_total, vcnt);
-        hipLaunchKernelGGL(k_ckpt_prefix, dim3(1), wg, 0, c->stream, vcnt, ngt, vcnt + ngt);
-        hipLaunchKernelGGL(k_rz_vis_emit, dim3(ck_grid((size_t)c->n_total)), wg, 0, c->stream, c->visType, c->n_total, vcnt + ngt,
-                           c->p.vis_capacity, c->visibleIds);
-        return hipGetLastError();
+        if (e == hipSuccess) e = tfk_ck_count(c, vis, c->n_total, c->ckptGroup);
+        return e == hipSuccess ? tfk_ck_emit(c, vis, c->n_total, c->ckptGroup) : e;
     });
     if (s != TF_OK) return s;
-    int2 nvis;
-    TF_CHECK(hipMemcpyAsync(&nvis, vcnt + 2 * (size_t)ngt, sizeof(nvis), hipMemcpyDeviceToHost, c->stream));
+    int4 nvis;
+    TF_CHECK(hipMemcpyAsync(&nvis, c->ckptGroup + 2 * (size_t)ck_groups(c->n_total), sizeof(nvis), hipMemcpyDeviceToHost, c->stream));
     TF_CHECK(hipStreamSynchronize(c->stream));
     return ckpt_load_finish(c, data, info, lay, c->p.n_blocks - 1 - totals.y, c->p.n_excess - 1 - totals.x,
                             nvis.x < c->p.vis_capacity ? nvis.x : c->p.vis_capacity);
