@@ -45,7 +45,7 @@ __global__ void k_acc(int n, double* out)
     }
 }
 
-// The (c, s) chain of icp_sv_cs with V multiplied out (SV_CS_W0) and its second v_rsq_f64 seeded
+// The (c, s) chain of icp_sv_cs with V multiplied out (V = W0 + W0 t) and its second v_rsq_f64 seeded
 // from the unrefined first one, q0 = 1/2 + |beta| y / 2 (the seed was tried as a switch and did not
 // win; its errors bound the kept chain's, whose second rsq starts from the refined
 // q), on X = 2^-300 .. 2^520 and |beta| / gamma in [0, 1]: max relative errors [0] v_rsq_f64 on the seeds' range [1/2, 1], [1] the seed q0

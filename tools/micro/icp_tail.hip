@@ -1,4 +1,4 @@
-// Latency of the persistent ICP kernel's serial tail on one wave (gfx950): the LDL^T solve,
+// Latency of the persistent ICP kernel's serial tail on one wave (gfx950): the solve,
 // Rodrigues and compose of tf_icp.hip, and the f64 primitives they chain, each repeated N times
 // with every repetition depending on the last.  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 //   -fhip-fp32-correctly-rounded-divide-sqrt icp_tail.hip -o icp_tail  (tools/micro/Makefile)
@@ -6,6 +6,49 @@
 #include <cstdio>
 #include "../../topfusion_amd/csrc/tf_icp_tail.h"
 #include "../../topfusion_amd/csrc/tf_pose.h"
+
+// the previous canonical solve (rounds 2-4), the timing baseline of which == 1:
+// LDL^T of the symmetric normal matrix in double with one reciprocal per pivot, then forward,
+// diagonal and backward substitution -- ~270 uniform operations with short dependency chains
+// (the pivoting elimination it replaces issued ~2.5x as many, 21 of them full divisions)
+__device__ __forceinline__ void icp_solve6_ldl(const float (&Af)[6][6], const float (&bf)[6], float (&x)[6])
+{
+    double L[6][6], d[6], r[6], y[6], xs[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double w[6];
+#pragma unroll
+        for (int k = 0; k < j; ++k) w[k] = L[j][k] * d[k];
+        double dj = Af[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) dj = dj - L[j][k] * w[k];
+        d[j] = dj;
+        r[j] = 1.0 / dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double sacc = Af[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) sacc = sacc - L[i][k] * w[k];
+            L[i][j] = sacc * r[j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double sacc = bf[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) sacc = sacc - L[i][k] * y[k];
+        y[i] = sacc;
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double sacc = y[i] * r[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) sacc = sacc - L[k][i] * xs[k];
+        xs[i] = sacc;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = (float)xs[i];
+}
 
 // one instantiation per variant (its own register allocation: a runtime switch over all of them
 // spilled the large ones), one wave
@@ -86,9 +129,8 @@ __global__ void __launch_bounds__(64) k_tail(const float* in, float* out, long l
     if (threadIdx.x == 0) { cyc[which] = t1 - t0; out[which] = aff[3] + bv[0] + (float)dacc; }
 }
 
-// icp_tail_rows (row layout) against the scalar tail on random ICP-like systems: sums of 7-vector
-// outer products (the rows), small random increments, a random affine; every output bit compared.
-// Also each form's latency with the whole system changing every repetition (nothing hoisted).
+// random ICP-like systems: sums of 7-vector outer products (the rows), small random increments, a
+// random affine
 __device__ __forceinline__ float rnd(unsigned& st)
 {
     st = st * 1664525u + 1013904223u;
@@ -115,70 +157,6 @@ __device__ void make_system(unsigned seed, float (&sm)[27], float (&aff)[12])
         aff[4 * j + 3] = rnd(st);
     }
 }
-__device__ void tail_scalar(const float (&sm)[27], const float (&aff)[12], float (&out)[12], float (&rv)[6])
-{
-    float Am[6][6], bv[6];
-    int shift = 0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 7; ++j) {
-            const float v = sm[shift++];
-            if (j == 6) bv[i] = v; else { Am[j][i] = v; Am[i][j] = v; }
-        }
-    float R[9], tinc[12];
-    icp_solve6_schur(Am, bv, rv);
-    icp_rodrigues(rv, R);
-    for (int j = 0; j < 3; ++j) {
-        tinc[4 * j + 0] = R[3 * j + 0]; tinc[4 * j + 1] = R[3 * j + 1];
-        tinc[4 * j + 2] = R[3 * j + 2]; tinc[4 * j + 3] = rv[3 + j];
-    }
-    tf_rigid_mul(tinc, aff, out);
-}
-__global__ void __launch_bounds__(64) k_rows_check(int nsys, int* bad, int* first_bad)
-{
-    __shared__ double xs[9];
-    const int lane = threadIdx.x;
-    for (int sys = 0; sys < nsys; ++sys) {
-        float sm[27], aff[12], o_s[12], rv_s[6], orow[4], rv_r[6];
-        make_system((unsigned)sys, sm, aff);
-        tail_scalar(sm, aff, o_s, rv_s);
-        icp_tail_rows(sm, aff, lane, xs, orow, rv_r);
-        bool ok = true;
-        for (int k = 0; k < 6; ++k) ok = ok && __float_as_uint(rv_s[k]) == __float_as_uint(rv_r[k]);
-        if (lane < 3)
-            for (int c = 0; c < 4; ++c) ok = ok && __float_as_uint(orow[c]) == __float_as_uint(o_s[4 * lane + c]);
-        if (__builtin_amdgcn_ballot_w64(!ok && lane < 3) != 0 && lane == 0) {
-            if (*bad == 0) *first_bad = sys;
-            *bad += 1;
-        }
-    }
-}
-template <int ROWS>
-__global__ void __launch_bounds__(64) k_rows_time(int n, long long* cyc, float* out)
-{
-    __shared__ double xs[9];
-    const int lane = threadIdx.x;
-    float sm[27], aff[12];
-    make_system(7u, sm, aff);
-    float acc = 0.f;
-    const long long t0 = clock64();
-    for (int it = 0; it < n; ++it) {
-        float rv[6];
-        if constexpr (ROWS) {
-            float orow[4];
-            icp_tail_rows(sm, aff, lane, xs, orow, rv);
-            acc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, orow[3]), 0));
-        } else {
-            float o[12];
-            tail_scalar(sm, aff, o, rv);
-            acc = o[3];
-        }
-        sm[0] += acc * 1e-30f;          // the next repetition's whole system depends on this one
-        sm[22] += rv[4] * 1e-30f;
-    }
-    const long long t1 = clock64();
-    if (lane == 0) { cyc[ROWS] = t1 - t0; out[ROWS] = acc; }
-}
-
 
 // candidate: S' = det R * P - Q adj(R) Q^T (one division on the chain; 1/det R off it)
 __device__ __forceinline__ void icp_solve6_schur2(const float (&Af)[6][6], const float (&bf)[6], float (&x)[6])
@@ -272,23 +250,6 @@ int main()
     const char* names[] = { "solve+rodrigues+compose (canonical)", "solve (LDL^T, r2-4)", "rodrigues", "10x f64 div", "10x f64 sqrt",
                             "10x f64 fma", "10x f32 fma", "10x f32 div", "cv solve (SVD)", "cv solve+rot+compose",
                             "10x f64 add", "10x f64 mul", "10x readlane+add", "10x f32 add", "solve (block Schur)" };
-    {   // the row-layout tail: bit-exact against the scalar one, and each one's latency
-        int* dBad; int hb[2] = { 0, -1 };
-        hipMalloc(&dBad, 2 * sizeof(int));
-        hipMemcpy(dBad, hb, sizeof(hb), hipMemcpyHostToDevice);
-        const int nsys = 20000;
-        hipLaunchKernelGGL(k_rows_check, dim3(1), dim3(64), 0, 0, nsys, dBad, dBad + 1);
-        hipMemcpy(hb, dBad, sizeof(hb), hipMemcpyDeviceToHost);
-        printf("row-layout tail vs scalar tail: %d of %d random systems differ in any output bit (first %d)\n", hb[0], nsys, hb[1]);
-        long long hc[2];
-        for (int w = 0; w < 2; ++w) {
-            if (w) { hipLaunchKernelGGL(k_rows_time<1>, dim3(1), dim3(64), 0, 0, 10, dC, dO); hipLaunchKernelGGL(k_rows_time<1>, dim3(1), dim3(64), 0, 0, N, dC, dO); }
-            else { hipLaunchKernelGGL(k_rows_time<0>, dim3(1), dim3(64), 0, 0, 10, dC, dO); hipLaunchKernelGGL(k_rows_time<0>, dim3(1), dim3(64), 0, 0, N, dC, dO); }
-        }
-        hipMemcpy(hc, dC, sizeof(hc), hipMemcpyDeviceToHost);
-        printf("%-26s %8.1f cycles per repetition (s_memtime, system changing every repetition)\n", "tail scalar", (double)hc[0] / N);
-        printf("%-26s %8.1f cycles per repetition (s_memtime, system changing every repetition)\n", "tail row layout", (double)hc[1] / N);
-    }
     {   // the S' solve (one division on the chain) against the canonical Schur solve
         int* dD; float* dM; hipMalloc(&dD, sizeof(int)); hipMalloc(&dM, sizeof(float));
         long long hc[2];

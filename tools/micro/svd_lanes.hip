@@ -2,10 +2,7 @@
 // serial one (icp_cv_solve_svd6) and the oracle (tfo_cv_solve_svd6), bit for bit, on captured ICP
 // systems (tools/svd_systems.py), random ICP-like systems and degenerate ones (A = 0, rank
 // deficient, huge / tiny scales); then the latency of both forms on one wave, each solve
-// depending on the last.  Built three times (plain, -DTF_SV_STATS, -DTF_SV_TIMING) and once more
-// with -DSV_ONESHOT=0 (svd_lanes_oneshot0: every sweep through the levels) for the A/B of the
-// batched final-sweep test; `make svd_lanes_cs` builds an off-twin per switch of the (c, s) chain
-// and the level (SV_CS_W0, SV_CS_LATE, SV_CH_MASK, SV_BCAST2) and svd_lanes_cs0 with all four off.
+// depending on the last.  Built three times (plain, -DTF_SV_STATS, -DTF_SV_TIMING).
 //   make -C tools/micro svd_lanes;  ./tools/micro/svd_lanes tests/golden/icp_systems_C2_opencv4.f32
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -213,8 +210,7 @@ int main(int argc, char** argv)
         for (int k = 0; k < 9; ++k) printf("  %-36s %9.1f\n", nm[k], (double)t[k] / (N + 20));
     }
 #endif
-    printf("latency over the first %d systems, one wave, dependent solves (s_memtime cycles per solve), SV_ONESHOT %d:\n", ns,
-           (int)SV_ONESHOT);
+    printf("latency over the first %d systems, one wave, dependent solves (s_memtime cycles per solve):\n", ns);
     printf("  serial  icp_cv_solve_svd6        %9.1f\n", (double)c[0] / N);
     printf("  lanes   icp_cv_solve_svd6_lanes  %9.1f   (%.2fx)\n", (double)c[1] / N, (double)c[0] / (double)c[1]);
     return 0;

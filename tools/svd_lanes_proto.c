@@ -10,7 +10,7 @@
  *   gcc -O2 -ffp-contract=off tools/svd_lanes_proto.c -Loracle -loracle -lm -o tools/_build/svd_proto
  *   LD_LIBRARY_PATH=oracle tools/_build/svd_proto [-oneshot] tools/_build/svd_systems_C2.f32
  *
- * -oneshot: the batched final-sweep test (SV_ONESHOT, icp_sv_oneshot) -- after level 2 of a
+ * -oneshot: the batched final-sweep test (icp_sv_oneshot) -- after level 2 of a
  * period whose head pairs rotated nothing, the other 11 pairs of that sweep tested on the current
  * state; all skip: the sweeps end there.  Prints levels, tries and hits per solve.  (The kernel
  * tests all 15 pairs there, the four head pairs again on the same state: the same outcome.)

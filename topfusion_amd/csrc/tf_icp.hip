@@ -1,7 +1,17 @@
 // tf_icp.hip -- projective point-to-plane ICP for gfx950.
 //
-// ONE launch per ICP iteration and no host round trip (the reference syncs to the host and
-// solves with OpenCV 19 times per frame, projective_icp.cpp:187-210).  k_icp_iter:
+// No host round trip (the reference syncs to the host and solves with OpenCV 19 times per frame,
+// projective_icp.cpp:187-210).  Two kernels run the same iteration, a third its algebra alone:
+//   * k_icp_frame (the product path): ONE persistent launch per frame for all levels and iterations,
+//     256 resident workgroups that exchange their column sums through tagged slots (described above
+//     the kernel).  Taken whenever its grid can be resident and the levels fit its slots
+//     (tfk_icp_persistent_ok).
+//   * k_icp_iter (the fallback, larger images): one launch per iteration.  The last workgroup to
+//     finish (agent-scope ticket, write-through sc1 stores/loads, MI355X_MICROARCH.md "Valid forms"
+//     row 1) runs the final 256-wide tree, the det check (cv::determinant), the 6x6 solve, Rodrigues
+//     and affine = Tinc * affine on one wave.
+//   * k_solve_systems: the iteration's algebra alone on caller systems (tf_icp_solve_systems).
+// k_icp_frame and k_icp_iter share the rows and the reductions:
 //   * find_coresp + row build (proj_icp.cu:80-117,359-377).  A wave64 owns one 32x8
 //     reference CTA, 4 pixels per lane (reference tids l, l+64, l+128, l+192), and reproduces
 //     the reference's 256-wide halving tree (temp_utils.hpp:503-523) bit for bit: two adds
@@ -10,10 +20,8 @@
 //   * workgroup w owns reference CTAs w, w+256, w+512, ... so it produces exactly the
 //     column sum that thread w of icp_final_reduce_kernel computes (proj_icp.cu:389-391),
 //     in the same order; no [27 x #CTA] partial buffer.
-//   * the last workgroup to finish (agent-scope ticket, write-through sc1 stores/loads,
-//     MI355X_MICROARCH.md "Valid forms" row 1) runs the final 256-wide tree, the det check
-//     (cv::determinant), the 6x6 solve, Rodrigues and affine = Tinc * affine with one wave
-//     holding the 6x7 system one element per lane.
+// The OpenCV algebras (ALG != 0) solve with the lane-parallel cv::solve(DECOMP_SVD) of tf_icp_tail.h
+// in all three kernels; the canonical algebra with icp_solve_rodrigues<0>.
 // A failed det check sets state->abort; every later ICP / scene kernel of the frame no-ops.
 #include "tf_internal.h"
 #include <string.h>
@@ -135,9 +143,6 @@ __device__ __forceinline__ void tstep(float* v, int lane)
     }
 }
 
-#ifndef IP_SVD_LANES
-#define IP_SVD_LANES 1         // the OpenCV algebra's cv::solve(DECOMP_SVD): 1 = lane-parallel, 0 = serial (A/B)
-#endif
 #include "tf_icp_tail.h"
 #include "tf_pose.h"
 #include "tf_vis.h"
@@ -287,7 +292,7 @@ k_icp_iter(IcpLevel L, TfDevState* __restrict__ st, float* __restrict__ T, unsig
     }
     float rv[6];
     float R[9], tinc[12], A[12];
-    if constexpr (ALG != 0 && IP_SVD_LANES) {                  // (tot: lane 2q holds sum q)
+    if constexpr (ALG != 0) {                                  // (tot: lane 2q holds sum q)
         icp_cv_solve_svd6_lanes<ALG>(tot, 2, lane, rv);
         icp_cv_rodrigues<ALG>(rv, R);
     } else {
@@ -331,16 +336,8 @@ k_icp_iter(IcpLevel L, TfDevState* __restrict__ st, float* __restrict__ T, unsig
 // error) so no wave can outlive a missing peer.
 // =========================================================================================
 #define IP_WAVES 8
-#ifndef TF_PROJ_DIV
-#define TF_PROJ_DIV 0
-#endif
 #define IP_SREG 1                       // CTA slots kept in registers per wave (8 per WG; larger images use k_icp_iter)
 #define IP_SPIN_LIMIT (1u << 21)
-#ifndef IP_SLEEP
-#define IP_SLEEP 0                      // s_sleep between hand-off polls (x 64 cycles); round 6 A/B under the
-                                        // OpenCV 4 algebra: 0 vs 1 = 2829 / 2825 vs 2816 / 2819 frames/s, ICP
-                                        // 0.304 vs 0.306 ms (profiles/r06/ab_icp_poll_sleep.txt); 2 = as 1
-#endif
 #define IP_PART (2 * ICP_NWG * ICP_T_STRIDE + 16)   // column slots (double-buffered by generation parity), then
                                                  // the 8 residue-class partials, double-buffered
 #define IP_NPART 8                               // residue classes of the final tree's first five steps
@@ -349,9 +346,8 @@ k_icp_iter(IcpLevel L, TfDevState* __restrict__ st, float* __restrict__ T, unsig
 // The window: under the OpenCV algebras an iteration's solve (wave 0) takes about 8 us, during
 // which the workgroup's other waves are parked at a barrier with no hand-off poll in flight -- from
 // the __syncthreads_or that ends the hop-2 gather to the __syncthreads() after the compose.
-#ifndef IP_DET_WINDOW
-#define IP_DET_WINDOW 1                          // the det check of iteration k beside solve k (A/B: 0 = deferred
-#endif                                           // into iteration k + 1's rows, as the canonical instance keeps it)
+// The det check of iteration k runs there, beside solve k (DET_WIN in k_icp_frame); the canonical
+// instance, whose solve leaves no window, keeps it deferred into iteration k + 1's rows.
 // Column sums go to the residue-class leader (workgroup wg % 8).  Each leader publishes its XCD
 // (HW_REG_XCC_ID) at launch; a workgroup that finds its leader on its own XCD publishes its
 // columns with plain stores (kept in the shared L2), any other with write-through sc1 stores.
@@ -361,24 +357,16 @@ k_icp_iter(IcpLevel L, TfDevState* __restrict__ st, float* __restrict__ T, unsig
 #endif
 #define IP_XCC_AT (IP_PART + 2 * IP_NPART * ICP_T_STRIDE)   // the leaders' XCD ids (TF_ICP_TAG_WORDS)
 // Hop 2's readers are all 256 workgroups, polling 8 x 27 granules.  Each leader publishes its
-// partials IP_PCOPY = 8 times, 4 KiB apart, and the workgroups of residue class x (one XCD
+// partials IP_PCOPIES = 8 times, 4 KiB apart, and the workgroups of residue class x (one XCD
 // under round-robin dispatch) poll copy x: 32 pollers per line instead of 256 (ICP -1.5 us per
-// launch, A/B profiles/r05/ab_icp_hop2_copies.txt).
-#ifndef IP_TAIL_ROWS
-#define IP_TAIL_ROWS 0                           // A/B: 1 = the row-layout tail (bit-exact, slower: DESIGN 8)
-#endif
-#ifndef IP_OK_BITWISE
-#define IP_OK_BITWISE 1                          // A/B: 0 = short-circuit correspondence flags
-#endif
-#ifndef IP_PCOPY
-#define IP_PCOPY 8                               // A/B: 1 = one copy polled by every workgroup
-#endif
+// launch against one copy polled by every workgroup, profiles/r05/ab_icp_hop2_copies.txt).
+#define IP_PCOPIES 8                             // copies of a leader's partials (a power of two)
 #define IP_PCOPY_AT (IP_XCC_AT + 16)
 #define IP_PCOPY_STRIDE 512
-static_assert(IP_PCOPY_AT + 8 * IP_PCOPY_STRIDE <= TF_ICP_TAG_WORDS, "TF_ICP_TAG_WORDS");
+static_assert(IP_PCOPY_AT + IP_PCOPIES * IP_PCOPY_STRIDE <= TF_ICP_TAG_WORDS, "TF_ICP_TAG_WORDS");
 __device__ __forceinline__ int ip_part_at(int copy)
 {
-    return IP_PCOPY == 1 ? IP_PART : IP_PCOPY_AT + copy * IP_PCOPY_STRIDE;
+    return IP_PCOPY_AT + copy * IP_PCOPY_STRIDE;
 }
 
 struct IcpFrameArgs {
@@ -512,36 +500,22 @@ __device__ __forceinline__ void ip_project2(const IcpLevel& L, const float* aff,
     sz = kdot2(ip_bc(aff[8]), ip_bc(aff[9]), ip_bc(aff[10]), vx, vy, vz) + ip_bc(aff[11]);
     // __fdividef(p.x, p.z) = p.x times an approximate reciprocal (proj_icp.cu:34-35): canonical
     // p.x * RN(1 / p.z), one reciprocal per pixel for both coordinates, the products packed
-#if TF_PROJ_DIV                                   // A/B only: the IEEE division sequence for RN(1 / z)
-    const ip_f2 rz = { 1.0f / sz.x, 1.0f / sz.y };
-#else
     // (one wave-uniform branch for the pair's rare IEEE fallback, tf_internal.h)
     ip_f2 rz = { tf_rcp_fast(sz.x), tf_rcp_fast(sz.y) };
     const bool slow0 = tf_rcp_slow(sz.x), slow1 = tf_rcp_slow(sz.y);
-#if TF_RCP_BRANCH
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow0 | slow1) != 0, 0)) {
         if (slow0) rz.x = 1.0f / sz.x;
         if (slow1) rz.y = 1.0f / sz.y;
     }
-#else
-    if (slow0) rz.x = 1.0f / sz.x;
-    if (slow1) rz.y = 1.0f / sz.y;
-#endif
-#endif
     const ip_f2 qx = sx * rz, qy = sy * rz;
     const ip_f2 coox = __builtin_elementwise_fma(ip_bc(L.fx), qx, ip_bc(L.cx));
     const ip_f2 cooy = __builtin_elementwise_fma(ip_bc(L.fy), qy, ip_bc(L.cy));
-#if IP_OK_BITWISE            // (bitwise, not short-circuit: no exec-mask branches)
+    // (bitwise, not short-circuit: no exec-mask branches; short-circuit flags were 0.4 us per launch
+    // slower, profiles/r05/ab_icp_r5h.txt)
     ok0 = (xy0 >= 0) & !isnan(vx.x) &
           !((sz.x <= 0) | (coox.x < 0) | (cooy.x < 0) | (coox.x >= (float)L.W) | (cooy.x >= (float)L.H));
     ok1 = (xy1 >= 0) & !isnan(vx.y) &
           !((sz.y <= 0) | (coox.y < 0) | (cooy.y < 0) | (coox.y >= (float)L.W) | (cooy.y >= (float)L.H));
-#else
-    ok0 = xy0 >= 0 && !isnan(vx.x) &&
-          !(sz.x <= 0 || coox.x < 0 || cooy.x < 0 || coox.x >= (float)L.W || cooy.x >= (float)L.H);
-    ok1 = xy1 >= 0 && !isnan(vx.y) &&
-          !(sz.y <= 0 || coox.y < 0 || cooy.y < 0 || coox.y >= (float)L.W || cooy.y >= (float)L.H);
-#endif
     idx0 = ok0 ? (int)floorf(cooy.x) * L.W + (int)floorf(coox.x) : 0;
     idx1 = ok1 ? (int)floorf(cooy.y) * L.W + (int)floorf(coox.y) : 0;
 }
@@ -647,7 +621,7 @@ __device__ __forceinline__ float ip_residue_tree(const float* c)
 // partials, runs the last three tree steps and the solve / Rodrigues / compose itself,
 // redundantly and bit-identically -- two small hops per iteration, no broadcast.  The det check
 // of iteration k (cv::determinant, projective_icp.cpp:197-203) runs on wave IP_DETW.  Under the
-// OpenCV algebras it runs beside solve k, in the window (IP_DET_WINDOW), and is settled at the
+// OpenCV algebras it runs beside solve k, in the window (DET_WIN), and is settled at the
 // iteration's closing barrier: on failure the composed affine is not taken and the loop ends.
 // The canonical instance, whose solve leaves no window, runs it while iteration k+1 computes its
 // rows and settles it before anything of k+1 is published: on failure the affine of k-1 is
@@ -665,9 +639,6 @@ k_icp_frame(IcpFrameArgs a)
     // the det check's sums and the affine it may restore live in LDS, not in registers across the
     // iteration: the serial tail runs in the registers they would hold
     __shared__ float det_sm_s[27], aff_prev_s[12];
-#if IP_TAIL_ROWS
-    __shared__ double xs_s[9];                  // icp_tail_rows' exchange of S (wave 0)
-#endif
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, wg = blockIdx.x;
     TfDevState* st = a.st;
     unsigned long long* tag = a.tag;
@@ -722,7 +693,7 @@ k_icp_frame(IcpFrameArgs a)
     float last_sums = 0.f;
     // det check in the window (the OpenCV algebras): settled at the iteration's closing barrier,
     // nothing is deferred; the canonical instance has no window (its solve takes 0.5 us)
-    constexpr bool DET_WIN = IP_DET_WINDOW && ALG != 0;
+    constexpr bool DET_WIN = ALG != 0;
 
     bool det_pending = false;
 
@@ -859,7 +830,8 @@ k_icp_frame(IcpFrameArgs a)
                     }
                     if (ready) break;
                     if (spins > IP_SPIN_LIMIT) { timeout = true; break; }
-                    __builtin_amdgcn_s_sleep(IP_SLEEP);
+                    // (s_sleep 0 between polls: 1 or 2 (x 64 cycles) were 0.4 % slower, profiles/r06/ab_icp_poll_sleep.txt)
+                    __builtin_amdgcn_s_sleep(0);
                 }
 #pragma unroll
                 for (int k = 0; k < PER; ++k) {
@@ -871,14 +843,14 @@ k_icp_frame(IcpFrameArgs a)
                 if (!lead_timeout && tid < 27) {        // a missing column: publish nothing, WG0 times out
                     const unsigned long long pv = ip_pack(gen, ip_residue_tree(tl[tid]));
 #pragma unroll
-                    for (int c = 0; c < IP_PCOPY; ++c)
+                    for (int c = 0; c < IP_PCOPIES; ++c)
                         ip_store(&tag[ip_part_at(c) + (gen & 1) * IP_NPART * ICP_T_STRIDE + wg * ICP_T_STRIDE + tid], pv);
                 }
             }
             {
                 // ---- gather the 8 x 27 partials, last three tree steps, det / solve / compose
                 // (every workgroup, redundantly and bit-identically -- no broadcast hop)
-                const unsigned long long* parts = &tag[ip_part_at(wg & (IP_PCOPY - 1)) + (gen & 1) * IP_NPART * ICP_T_STRIDE];
+                const unsigned long long* parts = &tag[ip_part_at(wg & (IP_PCOPIES - 1)) + (gen & 1) * IP_NPART * ICP_T_STRIDE];
                 bool timeout = false;
                 if (tid < IP_NPART * 27) {
                     const int x = tid / 27, q = tid - x * 27;
@@ -886,7 +858,7 @@ k_icp_frame(IcpFrameArgs a)
                     unsigned long long v = ip_load(pp);
                     for (unsigned spins = 0; (unsigned)(v >> 32) != gen; ++spins) {
                         if (spins > IP_SPIN_LIMIT) { timeout = true; break; }
-                        __builtin_amdgcn_s_sleep(IP_SLEEP);
+                        __builtin_amdgcn_s_sleep(0);
                         v = ip_load(pp);
                     }
                     tv[q][x] = __uint_as_float((unsigned)v);
@@ -917,25 +889,31 @@ k_icp_frame(IcpFrameArgs a)
                             det_sm_s[lane] = tot;
                         }
                     } else {                                           // solve -> Rodrigues -> compose
-#if IP_TAIL_ROWS
-                      if constexpr (ALG == 0) {                          // row layout (tf_icp_tail.h)
-                        float orow[4], rvr[6];
-                        icp_tail_rows(sm, aff, lane, xs_s, orow, rvr);
-                        IPT_REC_DEP(done, 2 * ICP_NWG + 7, orow[0] + orow[3]);
-                        if (lane < 3) {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) aff_s[4 * lane + c] = orow[c];
-                        }
-                        IPT_REC_DEP(done, 2 * ICP_NWG + 4, orow[1]);
-                        last_sums = tot;
-                      } else
-#endif
-                      {
                         float rv[6], R[9], tinc[12];
+                        if constexpr (ALG != 0) {                       // projective_icp.cpp:206-209
 #ifdef TF_ICP_TIMING
-                        if constexpr (ALG == 0) {                       // the two halves stamped apart
-                            // each half run twice back to back on the shader clock: the second
-                            // run finds its code in the instruction cache (g_icp_tail_cyc)
+                            // solve end and the halves' cycles as on the ALG == 0 path, each half
+                            // run once (g_icp_tail_cyc's "again" columns stay 0)
+                            const long long c0 = IPT_CYC(0.f);
+                            icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, rv);
+                            const long long c1 = IPT_CYC(rv[0] + rv[5]);
+                            IPT_REC_DEP(done, 2 * ICP_NWG + 3, rv[0] + rv[5]);
+                            const long long c3 = IPT_CYC(0.f);
+                            icp_cv_rodrigues<ALG>(rv, R);
+                            const long long c4 = IPT_CYC(R[0] + R[8]);
+                            if (blockIdx.x == 0 && lane == 0 && done < 64) {
+                                g_icp_tail_cyc[4 * done + 0] = c1 - c0; g_icp_tail_cyc[4 * done + 1] = 0;
+                                g_icp_tail_cyc[4 * done + 2] = c4 - c3; g_icp_tail_cyc[4 * done + 3] = 0;
+                            }
+#else
+                            icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, rv);
+                            icp_cv_rodrigues<ALG>(rv, R);
+#endif
+                        } else {
+#ifdef TF_ICP_TIMING
+                            // the two halves stamped apart, each run twice back to back on the shader
+                            // clock: the second run finds its code in the instruction cache
+                            // (g_icp_tail_cyc)
                             const long long c0 = IPT_CYC(0.f);
                             icp_solve6_schur(Am, bv, rv);
                             const long long c1 = IPT_CYC(rv[0] + rv[5]);
@@ -958,29 +936,9 @@ k_icp_frame(IcpFrameArgs a)
                                 g_icp_tail_cyc[4 * done + 2] = c4 - c3; g_icp_tail_cyc[4 * done + 3] = c5 - c4;
                             }
                             R[0] = R[0] + R2[0] * 0.0f;
-                        } else
-#endif
-                        if constexpr (ALG != 0 && IP_SVD_LANES) {       // projective_icp.cpp:206-209
-#ifdef TF_ICP_TIMING
-                            // solve end and the halves' cycles as on the ALG == 0 path, each half
-                            // run once (g_icp_tail_cyc's "again" columns stay 0)
-                            const long long c0 = IPT_CYC(0.f);
-                            icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, rv);
-                            const long long c1 = IPT_CYC(rv[0] + rv[5]);
-                            IPT_REC_DEP(done, 2 * ICP_NWG + 3, rv[0] + rv[5]);
-                            const long long c3 = IPT_CYC(0.f);
-                            icp_cv_rodrigues<ALG>(rv, R);
-                            const long long c4 = IPT_CYC(R[0] + R[8]);
-                            if (blockIdx.x == 0 && lane == 0 && done < 64) {
-                                g_icp_tail_cyc[4 * done + 0] = c1 - c0; g_icp_tail_cyc[4 * done + 1] = 0;
-                                g_icp_tail_cyc[4 * done + 2] = c4 - c3; g_icp_tail_cyc[4 * done + 3] = 0;
-                            }
 #else
-                            icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, rv);
-                            icp_cv_rodrigues<ALG>(rv, R);
-#endif
-                        } else {
                             icp_solve_rodrigues<ALG>(Am, bv, rv, R);
+#endif
                         }
                         IPT_REC_DEP(done, 2 * ICP_NWG + 7, R[0] + R[8]);
 #pragma unroll
@@ -995,7 +953,6 @@ k_icp_frame(IcpFrameArgs a)
                         if (lane < 12) aff_s[lane] = A[lane];
                         IPT_REC_DEP(done, 2 * ICP_NWG + 4, A[0] + A[11]);
                         last_sums = tot;
-                      }
                     }
                 }
                 __syncthreads();
@@ -1228,11 +1185,9 @@ __global__ void __launch_bounds__(64) k_solve_systems(const float* __restrict__ 
         for (int i = 0; i < 27; ++i) sm[i] = sums[27 * (size_t)q + i];
         ip_unpack(sm, Am, bv);
         const double d = icp_det6<ALG>(Am);
-        if constexpr (ALG != 0 && IP_SVD_LANES) {
+        if constexpr (ALG != 0) {
             const float tot = lane < 27 ? sums[27 * (size_t)q + lane] : 0.f;
             icp_cv_solve_svd6_lanes<ALG>(tot, 1, lane, xs);
-        } else if constexpr (ALG != 0) {
-            icp_cv_solve_svd6<ALG>(Am, bv, xs);
         } else {
             icp_solve6_schur(Am, bv, xs);
         }

@@ -40,23 +40,16 @@ __device__ __forceinline__ void icp_sincos(double th, double* s, double* c)
     *c = pc;
 }
 
-// Affine3f(rvec, t) rotation (Rodrigues in double).  Sinc form (default): R = cos t I +
+// Affine3f(rvec, t) rotation (Rodrigues in double).  Sinc form: R = cos t I +
 // ((1 - cos t) / t^2) r r^T + (sin t / t) [r]x with r = rvec unnormalised and the three even
 // functions of t = |rvec| as nested polynomials in t^2 evaluated with fma -- no square root and
 // no division on the iteration's serial path, three short independent chains (the sqrt / divide /
 // two-chain form it replaces was ~40 dependent f64 operations, 0.9 us of every ICP iteration;
 // the CPU restatement computes the same).  t > pi (never for an ICP
-// increment) takes that form.  TF_RODRIGUES_SINC=0: the old form throughout (A/B).
-#ifndef TF_SOLVE_LDL
-#define TF_SOLVE_LDL 0
-#endif
-#ifndef TF_RODRIGUES_SINC
-#define TF_RODRIGUES_SINC 1
-#endif
+// increment) takes that form.
 __device__ __forceinline__ void icp_rodrigues_sqrt(const float* rv, float* R);
 __device__ __forceinline__ void icp_rodrigues(const float* rv, float* R)
 {
-#if TF_RODRIGUES_SINC
     constexpr double inv_sin[14] = { 0.0, 1.0/6.0, 1.0/20.0, 1.0/42.0, 1.0/72.0, 1.0/110.0, 1.0/156.0,
         1.0/210.0, 1.0/272.0, 1.0/342.0, 1.0/420.0, 1.0/506.0, 1.0/600.0, 1.0/702.0 };
     constexpr double inv_cos[15] = { 0.0, 1.0/2.0, 1.0/12.0, 1.0/30.0, 1.0/56.0, 1.0/90.0, 1.0/132.0,
@@ -99,12 +92,9 @@ __device__ __forceinline__ void icp_rodrigues(const float* rv, float* R)
         const double I = (k % 4 == 0) ? 1.0 : 0.0;
         R[k] = (float)((pc * I + b * rrt[k]) + pa * rxm[k]);
     }
-#else
-    icp_rodrigues_sqrt(rv, R);
-#endif
 }
 
-// the sqrt / sincos / divide form (t > pi, or TF_RODRIGUES_SINC=0)
+// the sqrt / sincos / divide form (t > pi)
 __device__ __forceinline__ void icp_rodrigues_sqrt(const float* rv, float* R)
 {
     double rx = rv[0], ry = rv[1], rz = rv[2];
@@ -175,7 +165,8 @@ __device__ __forceinline__ double icp_det6_reg(const float (&A0)[6][6])
 // A = [P Q; Q^T R], T = Q adj(R) / det R, S = P - T Q^T, x1 = adj(S) (b1 - T b2) / det S,
 // x2 = adj(R) (b2 - Q^T x1) / det R.  The serial tail waits on this chain: two 3 x 3 determinants
 // and two divisions deep (~35 dependent operations) against ~110 for the column-by-column LDL^T
-// below, and x1, which Rodrigues needs, comes before x2.
+// of rounds 2-4 (tools/micro/icp_tail.hip keeps that one as its timing baseline), and x1, which
+// Rodrigues needs, comes before x2.
 __device__ __forceinline__ void icp_sym3_adj(const double (&M)[3][3], double (&C)[3][3], double& det)
 {
     C[0][0] = M[1][1] * M[2][2] - M[1][2] * M[2][1];
@@ -232,50 +223,6 @@ __device__ __forceinline__ void icp_solve6_schur(const float (&Af)[6][6], const 
     }
 }
 
-// the previous canonical form (rounds 2-4), kept for tools/micro/icp_tail.hip:
-// LDL^T of the symmetric normal matrix in double with one reciprocal per pivot, then forward,
-// diagonal and backward substitution -- ~270 uniform operations with short dependency chains
-// (the pivoting elimination it replaces issued ~2.5x as many, 21 of them full divisions)
-__device__ __forceinline__ void icp_solve6_ldl(const float (&Af)[6][6], const float (&bf)[6], float (&x)[6])
-{
-    double L[6][6], d[6], r[6], y[6], xs[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double w[6];
-#pragma unroll
-        for (int k = 0; k < j; ++k) w[k] = L[j][k] * d[k];
-        double dj = Af[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) dj = dj - L[j][k] * w[k];
-        d[j] = dj;
-        r[j] = 1.0 / dj;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double sacc = Af[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) sacc = sacc - L[i][k] * w[k];
-            L[i][j] = sacc * r[j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double sacc = bf[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) sacc = sacc - L[i][k] * y[k];
-        y[i] = sacc;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double sacc = y[i] * r[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) sacc = sacc - L[k][i] * xs[k];
-        xs[i] = sacc;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = (float)xs[i];
-}
-
-
 // =============================================================================================
 // The reference's own pose algebra: OpenCV's cv::determinant(Matx66f), cv::solve(A, b, r,
 // DECOMP_SVD) and cv::Affine3f(rvec, t) (projective_icp.cpp:197-209; OpenCV >= 2.4.9,
@@ -284,7 +231,7 @@ __device__ __forceinline__ void icp_solve6_ldl(const float (&Af)[6][6], const fl
 // transcendental functions (icp_sincos, icp_cv_hypot), in the same order: bit for bit the
 // oracle's.  ALG 2: OpenCV 2.4.9 (LU pivot floor FLT_EPSILON, norm(Vec3f) in double); ALG 4:
 // OpenCV 3.x / 4.x (10 FLT_EPSILON, norm in float).  One wave evaluates it on uniform data, like
-// the LDL^T solve; every register array is indexed statically (rotations are template-unrolled).
+// the Schur solve; every register array is indexed statically (rotations are template-unrolled).
 // =============================================================================================
 constexpr float TF_FLT_EPS = 1.19209290e-07f;
 constexpr double TF_FLT_MIN = 1.17549435e-38;
@@ -538,7 +485,7 @@ __device__ __forceinline__ void icp_cv_svd_finish(float (&At)[6][6], float (&Vt)
 }
 
 // =============================================================================================
-// cv::solve(DECOMP_SVD) lane-parallel (round 6; IP_SVD_LANES).  The serial form above runs each
+// cv::solve(DECOMP_SVD) lane-parallel (round 6).  The serial form above runs each
 // sweep's 15 rotations one after another on uniform data.  Here one wave holds the work matrix
 // one element per lane -- lane l = 8 r + k holds At[r][k], Vt[r][k] and |row r|^2 (rows 6, 7 and
 // columns 6, 7 are padding) -- and:
@@ -684,9 +631,6 @@ __device__ __forceinline__ double icp_sv_rowsum(double q, int lane)
 // in [1, 2), relative) from the midpoint pattern (one add and one unsigned compare), and, where
 // the value's range does not already guarantee it (full = true), v must be a normal float.
 #define SV_MARGIN (1u << 16)
-#ifndef SV_WQ_BPERM
-#define SV_WQ_BPERM 0          // 1: |partner row|^2 fetched from the partner's lane 0 (A/B: 0.6% slower)
-#endif
 template <bool full>
 __device__ __forceinline__ bool icp_sv_round_safe(double v)
 {
@@ -716,7 +660,8 @@ __device__ __forceinline__ void icp_sv_cs_exact(double p, double beta, float& c,
 // and one Goldschmidt step (which also refines 1 / (2 U)), 1 / u from that by one Newton step
 // on the rounded u, V = p h / u.
 // V is formed as W0 + W0 t with W0 = (p h) z0 beside the rounding of u and t = 1 - u z0 -- the
-// Newton step z0 (1 + t) for 1 / u multiplied out, one dependent operation fewer (SV_CS_W0).
+// Newton step z0 (1 + t) for 1 / u multiplied out, one dependent operation fewer than V = (p h) z
+// with the step's z formed first.
 // v_rsq_f64 is within 2^-24.2 (relative; sampled, 2^30 inputs over the exponents 2^-300..2^520,
 // tools/micro/f64_approx.hip, profiles/r08/f64_approx.txt), one Goldschmidt step leaves
 // 1.5 (2^-24.2)^2 = 2^-47.8 in U and in z0 and the Newton step as much in h, so U and V are within
@@ -724,17 +669,11 @@ __device__ __forceinline__ void icp_sv_cs_exact(double p, double beta, float& c,
 // from a worse value than this one: U 2^-47.5, V 2^-47.2), 2^10 below the margin
 // icp_sv_round_safe demands: where both pass it, (c, s) are the exact sequence's.
 // The result is the mask of the rotating lanes that fail it; the level gives those
-// icp_sv_cs_exact's (icp_sv_cs_fix, a wave-uniform branch) -- beside the update, not ahead of it
-// (SV_CS_LATE).
-#ifndef SV_CS_W0
-#define SV_CS_W0 1             // 0: V = (p h) z with the Newton step's z formed first
-#endif
-#ifndef SV_CS_LATE
-#define SV_CS_LATE 1           // 0: the margin's ballot and branch before the broadcast and the update
-#endif
-#ifndef SV_CH_MASK
-#define SV_CH_MASK 1           // 0: "a tail / head pair rotated" as booleans formed in every level
-#endif
+// icp_sv_cs_exact's (icp_sv_cs_fix, a wave-uniform branch) -- beside the update, not ahead of it.
+// (Each of the chain's four choices was measured against its other form, round 8,
+// profiles/r08/svd_lanes_micro_cs.txt, cycles per solve it saves: the margin's ballots and branch
+// beside the update 957-1 010, the rotated flags as masks 303, the two-move row broadcast 258,
+// V multiplied out 179-233.)
 __device__ __forceinline__ unsigned long long icp_sv_cs(double p, double beta, unsigned long long m, float& c, float& s)
 {
     const double X = fma(p, p, beta * beta);
@@ -746,24 +685,15 @@ __device__ __forceinline__ unsigned long long icp_sv_cs(double p, double beta, u
     double U = q * y2;
     const double h2 = 0.5 * y2, r2 = fma(-U, h2, 0.5);
     U = fma(U, r2, U);
-#if SV_CS_W0
     const double z0 = fma(y2, r2, y2);                         // 1 / U
     const double W0 = (p * h) * z0;
     const float u = (float)U;
     const double ud = u;
     const double V = fma(W0, fma(-ud, z0, 1.0), W0);           // p h / u
-#else
-    const double z0 = 2.0 * fma(h2, r2, h2);                   // 1 / U
-    const float u = (float)U;
-    const double ud = u;
-    const double z = fma(fma(-ud, z0, 1.0), z0, z0);           // 1 / u
-    const double V = (p * h) * z;
-#endif
     const float v = (float)V;
     const bool neg = beta < 0;
     c = neg ? v : u;
     s = neg ? u : v;
-#if SV_CS_LATE
     // (icp_sv_round_safe<false>(U) and <true>(V), one ballot per compare: each v_cmp writes its
     // wave mask and the masks meet in scalar code)
     const unsigned ve = (unsigned)(__builtin_bit_cast(unsigned long long, V) >> 52) & 0x7ffu;
@@ -771,9 +701,6 @@ __device__ __forceinline__ unsigned long long icp_sv_cs(double p, double beta, u
     const unsigned long long bv = __builtin_amdgcn_ballot_w64(icp_sv_round_safe<false>(V));
     const unsigned long long be = __builtin_amdgcn_ballot_w64(ve - (1023u - 125u) <= 251u);
     return m & ~(bu & bv & be);
-#else
-    return m & ~__builtin_amdgcn_ballot_w64((int)icp_sv_round_safe<false>(U) & (int)icp_sv_round_safe<true>(V));
-#endif
 }
 // the lanes of bad: (c, s) by the exact sequence
 __device__ __forceinline__ void icp_sv_cs_fix(double p, double beta, unsigned long long bad, float& c, float& s)
@@ -811,12 +738,8 @@ __device__ __forceinline__ float icp_dpp_f(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
 }
 // lane 0 of the lane's 8-lane row group (DPP row_newbcast:0 / :8)
-#ifndef SV_BCAST2
-#define SV_BCAST2 1            // 0: both broadcasts everywhere and a select by the lane's half of the DPP row
-#endif
-__device__ __forceinline__ float icp_row_bcast(float v, int lane)
+__device__ __forceinline__ float icp_row_bcast(float v)
 {
-#if SV_BCAST2
     // two moves, no select: bank_mask 0x3 writes lanes 0-7 of each DPP row, 0xc lanes 8-15, and a
     // lane outside the mask keeps the first move's value (the two masks cover every lane, so the
     // register the first move starts from needs no value)
@@ -824,10 +747,6 @@ __device__ __forceinline__ float icp_row_bcast(float v, int lane)
     asm("; sv bcast %0" : "=v"(un));
     const int lo = __builtin_amdgcn_update_dpp(un, __builtin_bit_cast(int, v), 0x150, 0xf, 0x3, false);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(lo, __builtin_bit_cast(int, v), 0x158, 0xf, 0xc, false));
-#else
-    const float b0 = icp_dpp_f<0x150>(v), b8 = icp_dpp_f<0x158>(v);
-    return (lane & 8) ? b8 : b0;
-#endif
 }
 
 #ifdef TF_SV_TIMING                               // (tools/micro/svd_lanes.hip timing build only)
@@ -844,93 +763,27 @@ struct SvTimes { long long t0, acc[9]; };
 #define SV_TARG
 #define SV_T(k, val_) do { } while (0)
 #endif
-// The partner row's element by lane swaps (SV_XOR_PARTNER): in every level each row's partner is
-// its index XOR one or two masks, and a row-index XOR of 1 / 2 / 4 is a lane XOR of 8 / 16 / 32 --
-// DPP row_ror:8, v_permlane16_swap, v_permlane32_swap (+ one v_cndmask each) -- instead of one
-// ds_bpermute round trip.  Rows without a partner (and the padding rows) get some other row's
-// element; nothing of theirs is used.  A/B (round 6, tools/micro/svd_lanes.hip, bit-exact): 21 708
-// against 20 254 cycles per solve -- the swap chains (up to three deep, each with its select) take
-// longer than the one round trip; off.
-#ifndef SV_XOR_PARTNER
-#define SV_XOR_PARTNER 0
-#endif
-__device__ __forceinline__ float icp_x8(float x) { return icp_dpp_f<0x128>(x); }
-__device__ __forceinline__ float icp_x16(float x)
-{
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return icp_lsel(0xffff0000ffff0000ull, __uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float icp_x32(float x)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return icp_lsel(0xffffffff00000000ull, __uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-template <int L>
-__device__ __forceinline__ float icp_sv_partner(float x)
-{
-    // level L's pairs as row-index XOR masks (SV_P): rows of mask A take a, the rest b
-    if constexpr (L == 0) {                 // (0,1) ^1; (2,5) (3,4) ^7
-        const float a1 = icp_x8(x), a7 = icp_x32(icp_x16(a1));
-        return icp_lsel(sv_row_lanes(0x03u), a1, a7);
-    } else if constexpr (L == 1) {          // (0,2) ^2; (3,5) ^6
-        const float a2 = icp_x16(x), a6 = icp_x32(a2);
-        return icp_lsel(sv_row_lanes(0x05u), a2, a6);
-    } else if constexpr (L == 2) {          // (0,3) (1,2) ^3; (4,5) ^1
-        const float a1 = icp_x8(x), a3 = icp_x16(a1);
-        return icp_lsel(sv_row_lanes(0x0fu), a3, a1);
-    } else if constexpr (L == 3) {          // (0,4) ^4; (1,3) ^2
-        const float a4 = icp_x32(x), a2 = icp_x16(x);
-        return icp_lsel(sv_row_lanes(0x11u), a4, a2);
-    } else if constexpr (L == 4) {          // (0,5) (1,4) ^5; (2,3) ^1
-        const float a1 = icp_x8(x), a5 = icp_x32(a1);
-        return icp_lsel(sv_row_lanes(0x33u), a5, a1);
-    } else {                                // (1,5) ^4; (2,4) ^6
-        const float a4 = icp_x32(x), a6 = icp_x16(a4);
-        return icp_lsel(sv_row_lanes(0x22u), a4, a6);
-    }
-}
-// the partner masks above, checked against SV_P at compile time
-constexpr bool sv_xor_ok()
-{
-    const unsigned A[6] = { 0x03u, 0x05u, 0x0fu, 0x11u, 0x33u, 0x22u };
-    const int ma[6] = { 1, 2, 3, 4, 5, 4 }, mb[6] = { 7, 6, 1, 2, 1, 6 };
-    for (int L = 0; L < 6; ++L)
-        for (int r = 0; r < 6; ++r) {
-            if (SV_P[L][r] == 15) continue;
-            const int m = ((A[L] >> r) & 1u) ? ma[L] : mb[L];
-            if ((r ^ m) != SV_P[L][r]) return false;
-        }
-    return true;
-}
-static_assert(sv_xor_ok(), "icp_sv_partner: masks must match SV_P");
-
-// "a pair of the period's tail / head sweep has rotated": the rotating lanes' bits OR-ed over
-// the levels and tested once where the sweeps' control needs it (SV_CH_MASK), or a boolean
-#if SV_CH_MASK
-typedef unsigned long long sv_ch_t;
-#else
-typedef bool sv_ch_t;
-#endif
-// one level of a period: every row with a partner in an enabled sweep rotates with it.  Lane 0
+// One level of a period: every row with a partner in an enabled sweep rotates with it.  Lane 0
 // of each row group gathers its row and the partner row (DPP row_shl) and forms the three sums the
 // rotation needs in the serial order -- p = sum_k At[I][k] At[J][k] and both |row|^2, exact double
 // products added in order (as fma: the products are exact) -- then the test and (c, s); the row's
 // lanes apply (c, s) to their element.  src: the lane holding this lane's element of the partner
 // row (own lane when the row is idle); which pairs are enabled is a template argument.
+// ch_tail / ch_head: "a pair of the period's tail / head sweep has rotated", the rotating lanes'
+// bits OR-ed over the levels and tested once where the sweeps' control needs it.
 template <int L, bool TAIL_ON, bool HEAD_ON>
-__device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int src, sv_ch_t& ch_tail, sv_ch_t& ch_head SV_TPARAM)
+__device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int src, unsigned long long& ch_tail,
+                                             unsigned long long& ch_head SV_TPARAM)
 {
     constexpr unsigned long long ACT = sv_act_base(L, TAIL_ON, HEAD_ON);
     constexpr unsigned long long LOW = sv_lower_lanes(L);
     constexpr unsigned long long TL = sv_row_lanes(SV_TAIL_ROWS[L]);
     if constexpr (ACT == 0) return;
     SV_T(0, a);
-#if SV_XOR_PARTNER
-    const float xa = icp_sv_partner<L>(a), xv = icp_sv_partner<L>(v);
-    (void)src;
-#else
+    // (one ds_bpermute round trip.  The partner by lane swaps instead -- a row-index XOR of 1 / 2 / 4
+    // is a lane XOR of 8 / 16 / 32: DPP row_ror:8, v_permlane16_swap, v_permlane32_swap -- was bit-exact
+    // and slower, 21 708 against 20 254 cycles per solve, round 6: the swap chains run up to three deep)
     const float xa = icp_bperm_f(src, a), xv = icp_bperm_f(src, v);
-#endif
     const float a1 = icp_dpp_f<0x101>(a), a2 = icp_dpp_f<0x102>(a), a3 = icp_dpp_f<0x103>(a);
     const float a4 = icp_dpp_f<0x104>(a), a5 = icp_dpp_f<0x105>(a);
     const double d0 = a, d1 = a1, d2 = a2, d3 = a3, d4 = a4, d5 = a5;
@@ -940,19 +793,14 @@ __device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int s
     const float x1 = icp_dpp_f<0x101>(xa), x2 = icp_dpp_f<0x102>(xa), x3 = icp_dpp_f<0x103>(xa);
     const float x4 = icp_dpp_f<0x104>(xa), x5 = icp_dpp_f<0x105>(xa);
     const double e0 = xa, e1 = x1, e2 = x2, e3 = x3, e4 = x4, e5 = x5;
-#if SV_WQ_BPERM
-    // |partner row|^2: the partner row's lane 0 formed it (its wo), fetched while p is summed
-    const double wq = icp_bperm_d(src & ~7, wo);
-    double p = fma(d0, e0, 0.0);
-    p = fma(d1, e1, p); p = fma(d2, e2, p); p = fma(d3, e3, p); p = fma(d4, e4, p); p = fma(d5, e5, p);
-#else
+    // (|partner row|^2 summed here: fetched from the partner row's lane 0, which formed it as its
+    // wo, it was 17 instructions fewer and 0.6 % slower)
     double wq = fma(e0, e0, 0.0), p = fma(d0, e0, 0.0);
     wq = fma(e1, e1, wq); p = fma(d1, e1, p);
     wq = fma(e2, e2, wq); p = fma(d2, e2, p);
     wq = fma(e3, e3, wq); p = fma(d3, e3, p);
     wq = fma(e4, e4, wq); p = fma(d4, e4, p);
     wq = fma(e5, e5, wq); p = fma(d5, e5, p);
-#endif
     SV_T(2, p + wo + wq);
     // beta = W[I] - W[J] on both rows' lanes (RN(y - x) = -RN(x - y)); ab = W[I] W[J]
     const double dw = wo - wq;
@@ -963,47 +811,36 @@ __device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int s
         float c, s;
         const double p2 = p * 2;
         const unsigned long long bad = icp_sv_cs(p2, beta, m, c, s);
-#if !SV_CS_LATE
-        if (__builtin_expect(bad != 0, 0)) icp_sv_cs_fix(p2, beta, bad, c, s);
-#endif
         SV_T(4, c + s);
-        float cb = icp_row_bcast(c, lane), sb = icp_row_bcast(s, lane);
+        float cb = icp_row_bcast(c), sb = icp_row_bcast(s);
         // row I: c Ai + s Aj, Vi c + Vj s;  row J: -s Ai + c Aj, Vj c - Vi s (the same products and
         // one addition each: a + b == b + a and x - y == x + (-y) bit for bit)
         float sc = icp_lsel(LOW, sb, -sb);
         float na = cb * a + sc * xa;
         float nv = v * cb + xv * sc;
-#if SV_CS_LATE
         // the margin's verdict arrives beside the update: only where a lane failed it (about 1
         // rotation in 2000) are (c, s) formed again, exactly, and the update repeated -- the
         // values committed below are the ones the check ahead of the update would have chosen
         if (__builtin_expect(bad != 0, 0)) {
             icp_sv_cs_fix(p2, beta, bad, c, s);
-            cb = icp_row_bcast(c, lane); sb = icp_row_bcast(s, lane);
+            cb = icp_row_bcast(c); sb = icp_row_bcast(s);
             sc = icp_lsel(LOW, sb, -sb);
             na = cb * a + sc * xa;
             nv = v * cb + xv * sc;
         }
-#endif
         const unsigned long long mr = icp_sv_spread(m);
         a = icp_lsel(mr, na, a);
         v = icp_lsel(mr, nv, v);
         SV_T(5, a + v);
-#if SV_CH_MASK
         if constexpr (TL != 0) ch_tail |= m & TL;
         ch_head |= m & ~TL;
-#endif
     }
 #ifdef TF_SV_STATS                                // (tools/micro/svd_lanes.hip: rotations)
     if (lane == 0) atomicAdd(&g_sv_stats[0], (unsigned long long)__builtin_popcountll(m) / 2);
 #endif
-#if !SV_CH_MASK
-    ch_tail = ch_tail || (m & TL) != 0;
-    ch_head = ch_head || (m & ~TL) != 0;
-#endif
 }
 
-// The final sweep settled by one batched test (SV_ONESHOT).  The serial loop ends after the first
+// The final sweep settled by one batched test.  The serial loop ends after the first
 // sweep that rotates nothing; in the level schedule that sweep costs six levels (3-5 of its head
 // period, 0-2 of the next), each a whole fetch -> gather -> sum -> test chain.  A sweep that
 // rotates nothing never changes At, so all 15 of its tests see one state.  After level 2 of a
@@ -1018,9 +855,9 @@ __device__ __forceinline__ void icp_sv_level(float& a, float& v, int lane, int s
 // icp_sv_test itself.  All skip: sweep s + 1 would run without a rotation and the serial loop
 // would break with this very At and Vt -- true.  Otherwise nothing has been modified and the
 // levels go on.  wo: |own row|^2 of that state (every lane of the row).
-#ifndef SV_ONESHOT
-#define SV_ONESHOT 1           // 0: every sweep through the levels (A/B)
-#endif
+// (Every sweep through the levels instead: 20.3 k against 19.0 k cycles per solve, DESIGN.md §10,
+// profiles/r07/svd_lanes_micro_oneshot.txt.)
+
 // element K of the lane's row, on every lane of the row
 template <int K>
 __device__ __forceinline__ float icp_row_elem(float v, int lane)
@@ -1083,7 +920,7 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
         const int P = (int)((sv_pack(L) >> (4 * r)) & 15u);
         src[L] = P != 15 ? 8 * P + k : lane;
     }
-    sv_ch_t ch_tail = 0, ch_head = 0;
+    unsigned long long ch_tail = 0, ch_head = 0;
 #ifdef TF_SV_TIMING
     SvTimes svt = {};
     svt.t0 = (long long)__builtin_amdgcn_s_memtime();
@@ -1094,9 +931,7 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
     icp_sv_level<2, false, true>(a, v, lane, src[2], ch_tail, ch_head SV_TARG);
     bool done = false, shot = false;            // shot: the sweeps ended through the batched test
     double wsq = 0;                             // then |row|^2 of the final state
-#if SV_ONESHOT
     if (!ch_head && icp_sv_oneshot(a, lane, wsq SV_TARG)) done = shot = true;   // sweep 0 rotates nothing
-#endif
     if (!done) {
         icp_sv_level<3, false, true>(a, v, lane, src[3], ch_tail, ch_head SV_TARG);
         icp_sv_level<4, false, true>(a, v, lane, src[4], ch_tail, ch_head SV_TARG);
@@ -1110,10 +945,8 @@ __device__ __forceinline__ void icp_cv_solve_svd6_lanes(float tot, int stride, i
         icp_sv_level<1, true, true>(a, v, lane, src[1], ch_tail, ch_head SV_TARG);
         icp_sv_level<2, true, true>(a, v, lane, src[2], ch_tail, ch_head SV_TARG);
         if (!ch_tail) { done = true; break; }   // sweep sw changed nothing: the serial loop's exit
-#if SV_ONESHOT
         // sweep sw + 1's head rotated nothing: its other pairs in one batched test (sw + 1 < 30)
         if (!ch_head && icp_sv_oneshot(a, lane, wsq SV_TARG)) { done = shot = true; break; }
-#endif
         icp_sv_level<3, true, true>(a, v, lane, src[3], ch_tail, ch_head SV_TARG);
         icp_sv_level<4, true, true>(a, v, lane, src[4], ch_tail, ch_head SV_TARG);
         icp_sv_level<5, true, true>(a, v, lane, src[5], ch_tail, ch_head SV_TARG);
@@ -1273,169 +1106,15 @@ __device__ __forceinline__ void icp_cv_rodrigues(const float* rv, float* R)
     }
 }
 
-// =============================================================================================
-// The canonical tail in row layout (round 5).  icp_solve6_schur + icp_rodrigues + tf_rigid_mul on
-// one wave issue ~500 instructions, every lane computing every element (the segment is issue-
-// bound: ~300 f64 instructions at 4 cycles each).  Here lane i < 3 computes row i of each 3 x 3
-// intermediate (T, S, adj S, the rotation) and of the new affine, values every row needs are read
-// across with readlane or through LDS, and the uniform parts (adj R, the determinants' sums) run
-// once on every lane.  Each element sees exactly the operations, in the same order, of the scalar
-// functions above -- the results are theirs bit for bit (tools/micro/icp_tail.hip: 0 of 20 000
-// random systems differ; 37 GPU parity tests).  ~280 instructions, and no faster: the tail is a
-// dependency chain, not issue-bound (1545 vs 1585 cycles alone; ICP 124.7 -> 128.3 us in the
-// kernel, profiles/r05/ab_icp_tail_rows.txt), so it stays an A/B build (IP_TAIL_ROWS=1).
-// =============================================================================================
-// sums are indexed as StreamHelper lays them out (projective_icp.cpp:51-61): Am[r][c] (r <= c) is
-// sum {0, 7, 13, 18, 22, 25}[r] + c - r, bv[r] is Am[r][6]
-template <typename T>
-__device__ __forceinline__ T icp_sel3(int i, T a, T b, T c) { return i == 0 ? a : (i == 1 ? b : c); }
-// sm: the 27 sums (uniform); aff: the current affine (uniform); i: the lane (rows 0-2 used);
-// xs: 9 doubles of wave-private LDS.  Out: orow = row i of Tinc * aff, rv = the increment (uniform)
-__device__ __forceinline__ void icp_tail_rows(const float (&sm)[27], const float (&aff)[12], int i, double* xs,
-                                              float (&orow)[4], float (&rv)[6])
-{
-    // (indices written out: icp_smi folded by hand, so every sum is a register, never an indexed one)
-    double R[3][3], Q[3][3], b2[3];
-    R[0][0] = sm[18]; R[0][1] = sm[19]; R[0][2] = sm[20];
-    R[1][0] = sm[19]; R[1][1] = sm[22]; R[1][2] = sm[23];
-    R[2][0] = sm[20]; R[2][1] = sm[23]; R[2][2] = sm[25];
-    Q[0][0] = sm[3]; Q[0][1] = sm[4]; Q[0][2] = sm[5];
-    Q[1][0] = sm[9]; Q[1][1] = sm[10]; Q[1][2] = sm[11];
-    Q[2][0] = sm[14]; Q[2][1] = sm[15]; Q[2][2] = sm[16];
-    b2[0] = sm[21]; b2[1] = sm[24]; b2[2] = sm[26];
-    // adj R (uniform): R is symmetric bit for bit, and so is its adjugate (the mirrored formulas
-    // are the same products, commuted): six cofactors of icp_sym3_adj, det R as there
-    double aR[3][3];
-    aR[0][0] = R[1][1] * R[2][2] - R[1][2] * R[2][1];
-    aR[0][1] = R[0][2] * R[2][1] - R[0][1] * R[2][2];
-    aR[0][2] = R[0][1] * R[1][2] - R[0][2] * R[1][1];
-    aR[1][1] = R[0][0] * R[2][2] - R[0][2] * R[2][0];
-    aR[1][2] = R[0][2] * R[1][0] - R[0][0] * R[1][2];
-    aR[2][2] = R[0][0] * R[1][1] - R[0][1] * R[1][0];
-    aR[1][0] = aR[0][1]; aR[2][0] = aR[0][2]; aR[2][1] = aR[1][2];
-    const double dR = (R[0][0] * aR[0][0] + R[0][1] * aR[1][0]) + R[0][2] * aR[2][0];
-    const double rR = 1.0 / dR;
-    // row i's inputs
-    double Qi[3], Pi[3], Qc[3], aRi[3];
-    Qi[0] = icp_sel3(i, sm[3], sm[9], sm[14]);
-    Pi[0] = icp_sel3(i, sm[0], sm[1], sm[2]);
-    Qc[0] = icp_sel3(i, sm[3], sm[4], sm[5]);
-    aRi[0] = icp_sel3(i, aR[0][0], aR[1][0], aR[2][0]);
-    Qi[1] = icp_sel3(i, sm[4], sm[10], sm[15]);
-    Pi[1] = icp_sel3(i, sm[1], sm[7], sm[8]);
-    Qc[1] = icp_sel3(i, sm[9], sm[10], sm[11]);
-    aRi[1] = icp_sel3(i, aR[0][1], aR[1][1], aR[2][1]);
-    Qi[2] = icp_sel3(i, sm[5], sm[11], sm[16]);
-    Pi[2] = icp_sel3(i, sm[2], sm[8], sm[13]);
-    Qc[2] = icp_sel3(i, sm[14], sm[15], sm[16]);
-    aRi[2] = icp_sel3(i, aR[0][2], aR[1][2], aR[2][2]);
-    const double b1i = icp_sel3(i, sm[6], sm[12], sm[17]);
-    const double b2i = icp_sel3(i, sm[21], sm[24], sm[26]);
-    // T, S, c: row i
-    double Ti[3], Si[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Ti[j] = ((Qi[0] * aR[0][j] + Qi[1] * aR[1][j]) + Qi[2] * aR[2][j]) * rR;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Si[j] = Pi[j] - ((Ti[0] * Q[j][0] + Ti[1] * Q[j][1]) + Ti[2] * Q[j][2]);
-    const double ci = b1i - ((Ti[0] * b2[0] + Ti[1] * b2[1]) + Ti[2] * b2[2]);
-    // S through LDS: row i of adj S = C[i][j] = S[j+1][i+1] S[j+2][i+2] - S[j+1][i+2] S[j+2][i+1]
-    if (i < 3) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) xs[3 * i + j] = Si[j];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int i1 = i == 0 ? 1 : (i == 1 ? 2 : 0), i2 = i == 0 ? 2 : (i == 1 ? 0 : 1);
-    double SA[3], SB[3];                                    // column i+1, column i+2 of S
-#pragma unroll
-    for (int r = 0; r < 3; ++r) { SA[r] = xs[3 * r + i1]; SB[r] = xs[3 * r + i2]; }
-    const double s0i = xs[i < 3 ? i : 0];                   // S[0][i]
-    double aSi[3];
-    aSi[0] = SA[1] * SB[2] - SB[1] * SA[2];
-    aSi[1] = SA[2] * SB[0] - SB[2] * SA[0];
-    aSi[2] = SA[0] * SB[1] - SB[0] * SA[1];
-    // det S = (S00 aS00 + S01 aS10) + S02 aS20: term k on lane k
-    const double tk = s0i * aSi[0];
-    const double dS = (icp_rl_d(tk, 0) + icp_rl_d(tk, 1)) + icp_rl_d(tk, 2);
-    const double rS = 1.0 / dS;
-    const double c0 = icp_rl_d(ci, 0), c1 = icp_rl_d(ci, 1), c2 = icp_rl_d(ci, 2);
-    const double x1i = ((aSi[0] * c0 + aSi[1] * c1) + aSi[2] * c2) * rS;
-    const double x10 = icp_rl_d(x1i, 0), x11 = icp_rl_d(x1i, 1), x12 = icp_rl_d(x1i, 2);
-    const double ei = b2i - ((Qc[0] * x10 + Qc[1] * x11) + Qc[2] * x12);
-    const double e0 = icp_rl_d(ei, 0), e1 = icp_rl_d(ei, 1), e2 = icp_rl_d(ei, 2);
-    const float x2f = (float)(((aRi[0] * e0 + aRi[1] * e1) + aRi[2] * e2) * rR);
-    rv[0] = (float)x10; rv[1] = (float)x11; rv[2] = (float)x12;
-    rv[3] = icp_rl_f(x2f, 0); rv[4] = icp_rl_f(x2f, 1); rv[5] = icp_rl_f(x2f, 2);
-    // Rodrigues, row i (icp_rodrigues' operations per element)
-    float Ri[3];
-    {
-        constexpr double inv_sin[14] = { 0.0, 1.0/6.0, 1.0/20.0, 1.0/42.0, 1.0/72.0, 1.0/110.0, 1.0/156.0,
-            1.0/210.0, 1.0/272.0, 1.0/342.0, 1.0/420.0, 1.0/506.0, 1.0/600.0, 1.0/702.0 };
-        constexpr double inv_cos[15] = { 0.0, 1.0/2.0, 1.0/12.0, 1.0/30.0, 1.0/56.0, 1.0/90.0, 1.0/132.0,
-            1.0/182.0, 1.0/240.0, 1.0/306.0, 1.0/380.0, 1.0/462.0, 1.0/552.0, 1.0/650.0, 1.0/756.0 };
-        const double rx = rv[0], ry = rv[1], rz = rv[2];
-        const double t2 = (rx * rx + ry * ry) + rz * rz;
-        if (t2 < 4.930380657631324e-32) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Ri[j] = (i == j) ? 1.0f : 0.0f;
-        } else if (t2 > 9.869604401089358) {
-            float Rf[9];
-            icp_rodrigues_sqrt(rv, Rf);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Ri[j] = icp_sel3(i, Rf[j], Rf[3 + j], Rf[6 + j]);
-        } else {
-            double pc = 1.0, pa = 1.0, pb = 1.0;
-            if (t2 < 0.000244140625) {
-#pragma unroll
-                for (int n = 4; n >= 1; --n) {
-                    pc = fma(-(t2 * inv_cos[n]), pc, 1.0);
-                    pa = fma(-(t2 * inv_sin[n]), pa, 1.0);
-                    pb = fma(-(t2 * inv_cos[n + 1]), pb, 1.0);
-                }
-            } else if (t2 < 0.015625) {
-#pragma unroll
-                for (int n = 6; n >= 1; --n) {
-                    pc = fma(-(t2 * inv_cos[n]), pc, 1.0);
-                    pa = fma(-(t2 * inv_sin[n]), pa, 1.0);
-                    pb = fma(-(t2 * inv_cos[n + 1]), pb, 1.0);
-                }
-            } else {
-#pragma unroll
-                for (int n = 13; n >= 1; --n) {
-                    pc = fma(-(t2 * inv_cos[n]), pc, 1.0);
-                    pa = fma(-(t2 * inv_sin[n]), pa, 1.0);
-                    pb = fma(-(t2 * inv_cos[n + 1]), pb, 1.0);
-                }
-            }
-            const double b = 0.5 * pb;
-            const double ri = icp_sel3(i, rx, ry, rz);
-            const double rj[3] = { rx, ry, rz };
-            // [r]x row i: (0, -rz, ry), (rz, 0, -rx), (-ry, rx, 0)
-            const double m[3] = { icp_sel3(i, 0.0, rz, -ry), icp_sel3(i, -rz, 0.0, rx), icp_sel3(i, ry, -rx, 0.0) };
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double I = (i == j) ? 1.0 : 0.0;
-                Ri[j] = (float)((pc * I + b * (ri * rj[j])) + pa * m[j]);
-            }
-        }
-    }
-    // row i of Tinc * aff (tf_rigid_mul)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) orow[c] = (Ri[0] * aff[0 * 4 + c] + Ri[1] * aff[1 * 4 + c]) + Ri[2] * aff[2 * 4 + c];
-    orow[3] = ((Ri[0] * aff[3] + Ri[1] * aff[7]) + Ri[2] * aff[11]) + x2f;
-}
-
-// the iteration's solve + Rodrigues under pose algebra ALG
+// the iteration's solve + Rodrigues under pose algebra ALG.  (Round 5 tried the canonical tail in row
+// layout -- lane i < 3 computing row i of each 3 x 3 intermediate, ~280 instructions instead of ~500,
+// bit-exact -- and it was no faster: the tail is a dependency chain, not issue-bound; 1545 vs 1585
+// cycles alone, ICP 124.7 -> 128.3 us in the kernel, profiles/r05/ab_icp_tail_rows.txt.)
 template <int ALG>
 __device__ __forceinline__ void icp_solve_rodrigues(const float (&Am)[6][6], const float (&bv)[6], float (&rv)[6], float* R)
 {
     if constexpr (ALG == 0) {
-#if TF_SOLVE_LDL                                  // A/B only: the rounds 2-4 form (not the oracle's)
-        icp_solve6_ldl(Am, bv, rv);
-#else
         icp_solve6_schur(Am, bv, rv);
-#endif
         icp_rodrigues(rv, R);
     } else {
         icp_cv_solve_svd6<ALG>(Am, bv, rv);

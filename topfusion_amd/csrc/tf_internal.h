@@ -102,9 +102,6 @@ struct TfDevState {
 // subnormal, |z| >= 2^126) takes the IEEE division behind a wave-uniform branch that no wave
 // takes on real depth data -- as a select, the division sequence cost ~12 instructions per
 // reciprocal on the ICP rows' critical SIMD.
-#ifndef TF_RCP_BRANCH
-#define TF_RCP_BRANCH 1          // A/B only: 0 = the division computed for every lane and selected
-#endif
 __device__ __forceinline__ float tf_rcp_fast(float z)
 {
     const float r0 = __builtin_amdgcn_rcpf(z);
@@ -120,13 +117,9 @@ __device__ __forceinline__ float tf_rcp_rn(float z)
 {
     float r = tf_rcp_fast(z);
     const bool slow = tf_rcp_slow(z);
-#if TF_RCP_BRANCH
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow) != 0, 0)) {
         if (slow) r = 1.0f / z;
     }
-#else
-    if (slow) r = 1.0f / z;
-#endif
     return r;
 }
 

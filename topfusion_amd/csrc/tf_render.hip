@@ -431,9 +431,6 @@ __device__ __forceinline__ float ray_march(const RayArgs& a, const float* invM, 
 // vtab: this thread's 8-entry slot in LDS (VTAB_STRIDE ints): the 2x2x2 block offsets, so each
 // of the 32 reads finds its block with one LDS load instead of an 8-way select.
 #define VTAB_STRIDE 9
-#ifndef TF_NORMAL_PHASES
-#define TF_NORMAL_PHASES 1
-#endif
 __device__ void sdf_normal(const SceneView& s, const float* pt, float* ret, int* vtab)
 {
     float ffx = floorf(pt[0]), ffy = floorf(pt[1]), ffz = floorf(pt[2]);
@@ -466,12 +463,10 @@ __device__ void sdf_normal(const SceneView& s, const float* pt, float* ret, int*
     t0 = RV(2, 0, 0); t1 = RV(2, 1, 0); t2 = RV(2, 0, 1); t3 = RV(2, 1, 1);
     p2 = t0 * ny * nz + t1 * cy * nz + t2 * ny * cz + t3 * cy * cz;
     ret[0] = tf_div32767(p1 * nx + p2 * cx - v1);
-#if TF_NORMAL_PHASES
     // the y and z reads after the x derivative: 16 + 16 loads in flight instead of 32, so the
     // raycast kernels that end in this gradient keep their register budget (one more round trip
     // per pixel, once, against the march's many)
     __builtin_amdgcn_sched_barrier(0);
-#endif
     p1 = f0 * nx * nz + f1 * cx * nz + b0 * nx * cz + b1 * cx * cz;
     t0 = RV(0, -1, 0); t1 = RV(1, -1, 0); t2 = RV(0, -1, 1); t3 = RV(1, -1, 1);
     p2 = t0 * nx * nz + t1 * cx * nz + t2 * nx * cz + t3 * cx * cz;

@@ -19,9 +19,6 @@
 #ifndef TF_INTEG_STREAM_BLOCKS
 #define TF_INTEG_STREAM_BLOCKS 16384   // 32 MiB of voxels
 #endif
-#ifndef TF_INTEG_NT_STORES
-#define TF_INTEG_NT_STORES 0
-#endif
 #define CHUNK 4096          // hash entries per workgroup in the scan passes (256 thr x 16)
 
 // byte i (0..15) of a 16-byte group held as two 64-bit words (no dynamic register indexing)
@@ -778,9 +775,6 @@ hipError_t tfk_alloc(tf_ctx* c, int snapshot, TfAhead bil, size_t pitch, int onl
 // computeUpdatedVoxelDepthInfo (SceneReconstructionEngine.hpp:23-71).
 // 128 lanes per 8^3 block, 4 consecutive voxels (16 B) per lane; blocks grid-strided.
 // ---------------------------------------------------------------------------------------
-#ifndef TF_INTEG_DIV
-#define TF_INTEG_DIV 0
-#endif
 struct IntegArgs {
     const float* dists;
     int W, H;
@@ -820,14 +814,9 @@ __device__ __forceinline__ bool integ_project(float px, float py, float pz, cons
     // projParams_d.x * pt_camera.x / pt_camera.z (SceneReconstructionEngine.hpp:35-36), built with
     // --prec-div=false (CMakeLists.txt:1): the quotient as a product with the reciprocal -- canonical
     // (fx x) RN(1/z), one reciprocal per voxel for both coordinates (round 5; it was (fx x) / z)
-#if TF_INTEG_DIV                                   // A/B only: the IEEE quotients (not the oracle's)
-    float ix = a.fx * pc[0] / pc[2] + a.cx;
-    float iy = a.fy * pc[1] / pc[2] + a.cy;
-#else
     const float rz = tf_rcp_rn(pc[2]);
     float ix = (a.fx * pc[0]) * rz + a.cx;
     float iy = (a.fy * pc[1]) * rz + a.cy;
-#endif
     if ((ix < 1) || (ix > (float)(a.W - 2)) || (iy < 1) || (iy > (float)(a.H - 2))) return false;
     *idx = (int)(ix + 0.5f) + (int)(iy + 0.5f) * a.W;
     return true;
@@ -963,9 +952,6 @@ __device__ __forceinline__ void integ_proj_pair(const TfHashEntry& e, const TfHa
 // (each lane starts from an empty voxel); bits 2 / 3 -- samples rounded down to 16 B / 128 B.  C3I's reads split by source with PMC FETCH_SIZE.
 #ifndef TF_C3X
 #define TF_C3X 0
-#endif
-#ifndef TF_INTEG_LANEMAP
-#define TF_INTEG_LANEMAP 1
 #endif
 __device__ __forceinline__ float integ_sample(const float* dists, int di)
 {
@@ -1145,16 +1131,11 @@ __device__ __forceinline__ void integ_body(IntegArgs a, TfDevState* __restrict__
     }
     const int half = threadIdx.x >> 7, t = threadIdx.x & 127;
     // a lane's four voxels: x in {0..3} or {4..7} of one (y, z) row of the block.  Each wave takes
-    // four y rows of all eight z layers (TF_INTEG_LANEMAP 1) -- not eight y rows of four layers: a
+    // four y rows of all eight z layers -- not eight y rows of four layers: a
     // depth-sample instruction then spans half the image rows, and the samples' L1 -> L2 line
     // fetches, not the voxel stream, are what the pass waits on (profiles/r05/c3i_read_attribution.json)
-#if TF_INTEG_LANEMAP
     const int vx = (t & 1) * 4, vy = ((t >> 1) & 3) | ((t >> 6) << 2), vz = (t >> 3) & 7;
     const int lin = vx + 8 * vy + 64 * vz;
-#else
-    const int lin = t * 4;                       // first voxel of this lane: x in {0,4}
-    const int vx = lin & 7, vy = (lin >> 3) & 7, vz = lin >> 6;
-#endif
     // two blocks per half-workgroup per pass, their id / entry / voxel loads issued before
     // either is computed: twice the bytes in flight per wave (at C3 scale, 2^21 blocks, the
     // pass is a stream over 8.6 GB)
@@ -1211,7 +1192,7 @@ __device__ __forceinline__ void integ_body(IntegArgs a, TfDevState* __restrict__
             const TfHashEntry nne = hash[nid1], nne2 = hash[nid2];
             const int nn1 = visibleIds[min(i + 3 * step, n - 1)], nn2 = visibleIds[min(i + 3 * step + stride, n - 1)];
             // pass k: update
-            integ_apply_pair<RGB>(v, v2, dm, z, ok, e, e2, vx, vy, vz, a, p, p2, rw, stream || TF_INTEG_NT_STORES, Mr, lin, &n_rd, &n_wr);
+            integ_apply_pair<RGB>(v, v2, dm, z, ok, e, e2, vx, vy, vz, a, p, p2, rw, stream, Mr, lin, &n_rd, &n_wr);
             e = ne; e2 = ne2; ne = nne; ne2 = nne2; nid1 = nn1; nid2 = nn2;
             v = vn; v2 = vn2; p = pn; p2 = pn2;
 #pragma unroll
