@@ -14,6 +14,10 @@
 //   ... --save-scene F : write the checkpoint F after the last frame (TopFu::saveScene)
 //   ... --load-scene F --capacity BUCKETS,EXCESS,BLOCKS : resume in tables of these sizes, whatever F was saved
 //                        with (TopFu::loadMapResized: the map is re-hashed on the way in)
+//   ... --view-out F.ppm --view-pose tx,ty,tz,rx,ry,rz [--view-size CxR] : the final map from that camera -> world
+//                        pose (translation in metres, rotation as a Rodrigues vector) at that size (default: the
+//                        frames'), through a free view (TopFu::renderView), as a binary PPM.  With 0 frames and
+//                        --load-scene: a saved map's picture and nothing else.
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -33,7 +37,7 @@ using namespace tfusion;
 
 int main(int argc, char** argv)
 {
-    std::string pgm, ppm, mesh, load_scene, save_scene, capacity;
+    std::string pgm, ppm, mesh, load_scene, save_scene, capacity, view_out, view_pose, view_size;
     bool mesh_normals = false, mesh_indexed = false;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
@@ -43,6 +47,9 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--load-scene") && i + 1 < argc) load_scene = argv[++i];
         else if (!std::strcmp(argv[i], "--save-scene") && i + 1 < argc) save_scene = argv[++i];
         else if (!std::strcmp(argv[i], "--capacity") && i + 1 < argc) capacity = argv[++i];
+        else if (!std::strcmp(argv[i], "--view-out") && i + 1 < argc) view_out = argv[++i];
+        else if (!std::strcmp(argv[i], "--view-pose") && i + 1 < argc) view_pose = argv[++i];
+        else if (!std::strcmp(argv[i], "--view-size") && i + 1 < argc) view_size = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
         else if (!std::strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
         else pos.push_back(argv[i]);
@@ -145,6 +152,24 @@ int main(int argc, char** argv)
         else if (mesh_normals) topfu->saveMesh(mesh, TF_MESH_NORMALS);
         else topfu->saveMesh(mesh);
         std::printf("mesh written to %s\n", mesh.c_str());
+    }
+    if (!view_out.empty()) {
+        float p[6] = { 0, 0, 0, 0, 0, 0 };
+        int vc = cols, vr = rows;
+        if ((!view_pose.empty() && std::sscanf(view_pose.c_str(), "%f,%f,%f,%f,%f,%f", &p[0], &p[1], &p[2], &p[3], &p[4], &p[5]) != 6) ||
+            (!view_size.empty() && std::sscanf(view_size.c_str(), "%dx%d", &vc, &vr) != 2)) {
+            std::fprintf(stderr, "--view-pose tx,ty,tz,rx,ry,rz  --view-size CxR\n");
+            return 1;
+        }
+        cuda::image4u free_view;
+        topfu->renderView(free_view, Affine3f(Vec3f(p[3], p[4], p[5]), Vec3f(p[0], p[1], p[2])), TopFu::RENDER_SHADED_GREYSCALE, vc, vr);
+        std::vector<unsigned char> px((size_t)vc * vr * 4);
+        free_view.download(px.data(), (size_t)vc * 4);
+        io::writePPM(view_out, px.data(), vc, vr);
+        long view_lit = 0;
+        for (size_t k = 0; k < px.size(); k += 4) view_lit += px[k] > 0;
+        std::printf("free view %dx%d written to %s: %ld pixels lit\n", vc, vr, view_out.c_str(), view_lit);
+        if (frames == 0) return 0;
     }
     long lit = 0;
     for (size_t k = 0; k < view_host.size(); k += 4) lit += view_host[k] > 0;

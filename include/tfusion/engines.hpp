@@ -11,12 +11,19 @@
 //                                           tfusion/include/tfusion/cuda/imgproc.hpp:9-31
 //
 // One difference of structure: a Scene owns one libtfusion_hip context, which holds the scene
-// (hash, voxel blocks, block grid) AND the render state it is rendered with (visible list and
-// types, range image, raycast result).  A RenderState object is therefore a handle that the
-// engines accept for source compatibility; everything goes to the scene's context, so a scene
-// has exactly one render state.  The context is sized at construction: the image size and the
-// capacities come from the TopFuParams the Scene is given (defaults: the reference's
-// default_params, VoxelBlockHash.hpp:10-27).
+// (hash, voxel blocks, block grid) AND the render state the tracker works with (visible list and
+// types, range image, raycast result), sized at construction: the image size and the capacities
+// come from the TopFuParams the Scene is given (defaults: the reference's default_params,
+// VoxelBlockHash.hpp:10-27).  The engines take that state when they are given no RenderState
+// (nullptr) or one that was never bound.
+//
+// A RenderState / RenderState_VH passed to VisualisationEngine_CUDA::FindVisibleBlocks becomes a
+// render state of its own: on first use it binds a free view (tf_view, include/tfusion_hip.h) of
+// its imgSize on that scene's context -- its own visible list, range image, raycast result and
+// image -- and releases it in its destructor.  CreateExpectedDepths, RenderImage and CreateICPMaps
+// given a bound render state work on that view and size their outputs by it, and leave the
+// scene's own render state (the tracker's) untouched.  A bound render state is destroyed before
+// its scene (the scene's destructor releases the views still bound to it).
 #pragma once
 #include "../tfusion_hip.h"
 #include "topfu.hpp"
@@ -237,17 +244,35 @@ namespace tfusion
         Intr intr_;
     };
 
-    // RenderState (RenderState.hpp:12-88) / RenderState_VH (RenderState_VH.hpp:15-61): handles
-    // (the state itself lives in the scene's context, see the header comment)
+    // RenderState (RenderState.hpp:12-88) / RenderState_VH (RenderState_VH.hpp:15-61): unbound, a handle
+    // for the scene's own render state; bound by FindVisibleBlocks, a free view of imgSize (see the
+    // header comment)
     class RenderState
     {
     public:
         RenderState(const Vector2i& imgSize, float vf_min, float vf_max) : imgSize_(imgSize), vf_min_(vf_min), vf_max_(vf_max) {}
-        virtual ~RenderState() {}
+        virtual ~RenderState() { tf_view_destroy(view_); }
+        RenderState(const RenderState&) = delete;
+        RenderState& operator=(const RenderState&) = delete;
         const Vector2i& imgSize() const { return imgSize_; }
+        // the free view this state is bound to (nullptr: never bound)
+        tf_view* view() const { return view_; }
+        // binds a view of imgSize on `ctx` (the first use; again when given another scene's context)
+        tf_view* bind(tf_ctx* ctx)
+        {
+            if (view_ && ctx_ == ctx) return view_;
+            tf_view_destroy(view_);
+            view_ = nullptr;
+            const tf_view_params vp = { imgSize_.x, imgSize_.y, 0, 0 };
+            tf_engine_check(tf_view_create(ctx, &vp, &view_), "RenderState: tf_view_create");
+            ctx_ = ctx;
+            return view_;
+        }
     private:
         Vector2i imgSize_;
         float vf_min_, vf_max_;
+        tf_view* view_ = nullptr;
+        tf_ctx* ctx_ = nullptr;
     };
     class RenderState_VH : public RenderState
     {
@@ -332,14 +357,33 @@ namespace tfusion
     class VisualisationEngine_CUDA
     {
     public:
+        // FindVisibleBlocks (the reference's declaration is commented out, VisualisationEngine_CUDA.cu:43-73; its
+        // kernel buildCompleteVisibleList_device is live): every allocated block of the scene that projects into
+        // renderState's image from `pose` (world -> camera), in ascending entry order, into renderState's own
+        // visible list.  Binds renderState to a free view of its imgSize on first use.  Returns the count; throws
+        // with TF_CAPACITY's text when the list is too short.  On a swapping scene: the resident blocks only.
+        int FindVisibleBlocks(const Scene<TVoxel, TIndex>* scene, const Matrix4f pose, const Vector4f intrinsics,
+                              RenderState* renderState) const
+        {
+            if (!renderState) throw std::invalid_argument("FindVisibleBlocks: a RenderState is needed");
+            const float in[4] = { intrinsics.x, intrinsics.y, intrinsics.z, intrinsics.w };
+            float rt[12];
+            detail::rt_of(pose, rt);
+            int n = 0;
+            tf_engine_check(tf_view_find_visible(renderState->bind(scene->context()), in, rt, &n), "FindVisibleBlocks");
+            return n;
+        }
         // CreateExpectedDepths (VisualisationEngine_CUDA.cu:119-173); pose is world -> camera
         void CreateExpectedDepths(const Scene<TVoxel, TIndex>* scene, const Affine3f pose, const Intr intrinsics,
-                                  RenderState* = nullptr) const
+                                  RenderState* renderState = nullptr) const
         {
             float in[4], rt[12];
             detail::intr4(intrinsics, in);
             detail::rt_of(pose, rt);
-            tf_engine_check(tf_vis_expected_depths(scene->context(), in, rt), "CreateExpectedDepths");
+            if (renderState && renderState->view())
+                tf_engine_check(tf_view_expected_depths(renderState->view(), in, rt), "CreateExpectedDepths (view)");
+            else
+                tf_engine_check(tf_vis_expected_depths(scene->context(), in, rt), "CreateExpectedDepths");
         }
         // RenderImage (:220-291, 423-429); pose is camera -> world (TopFu's Matrix4f(poses_.back()))
         void RenderImage(const Scene<TVoxel, TIndex>* scene, Matrix4f pose, const Vector4f intrinsics, RenderState* renderState,
@@ -350,9 +394,17 @@ namespace tfusion
         {
             if (raycastType == IVisualisationEngine::RENDER_FROM_OLD_FORWARDPROJ)
                 throw std::invalid_argument("RenderImage: RENDER_FROM_OLD_FORWARDPROJ is not on this path");
-            (void)renderState;
             float in[4] = { intrinsics.x, intrinsics.y, intrinsics.z, intrinsics.w }, rt[12];
             detail::rt_of(pose, rt);
+            if (renderState && renderState->view()) {      // a bound render state: its own raycast result and size
+                tf_view* v = renderState->view();
+                outputImage.create(renderState->imgSize().y, renderState->imgSize().x);
+                if (raycastType == IVisualisationEngine::RENDER_FROM_NEW_RAYCAST)
+                    tf_engine_check(tf_view_raycast(v, in, rt), "RenderImage (view raycast)");
+                tf_engine_check(tf_view_shade(v, in, rt, (int)type, reinterpret_cast<uint8_t*>(outputImage.ptr()),
+                                              outputImage.step()), "RenderImage (view)");
+                return;
+            }
             tf_params p;
             tf_engine_check(tf_get_params(scene->context(), &p), "tf_get_params");
             outputImage.create(p.rows, p.cols);
@@ -362,12 +414,22 @@ namespace tfusion
                             "RenderImage");
         }
         // CreateICPMaps (:473-493 -> 323-360); pose is camera -> world
+        // (a bound render state has no visibility types to mark: its raycast is castRay<false>)
         void CreateICPMaps(const Scene<TVoxel, TIndex>* scene, const Matrix4f pose, const Intr intr, cuda::Cloud& points,
-                           cuda::Normals& normals, RenderState* = nullptr) const
+                           cuda::Normals& normals, RenderState* renderState = nullptr) const
         {
             float in[4], rt[12];
             detail::intr4(intr, in);
             detail::rt_of(pose, rt);
+            if (renderState && renderState->view()) {
+                tf_view* v = renderState->view();
+                points.create(renderState->imgSize().y, renderState->imgSize().x);
+                normals.create(renderState->imgSize().y, renderState->imgSize().x);
+                tf_engine_check(tf_view_raycast(v, in, rt), "CreateICPMaps (view raycast)");
+                tf_engine_check(tf_view_icp_maps(v, in, rt, points.ptr(), points.step(), normals.ptr(), normals.step()),
+                                "CreateICPMaps (view)");
+                return;
+            }
             tf_params p;
             tf_engine_check(tf_get_params(scene->context(), &p), "tf_get_params");
             points.create(p.rows, p.cols);

@@ -97,6 +97,26 @@ inline void readPPM(const std::string& path, std::vector<uint8_t>& bgr, int& col
     for (size_t i = 0; i < n; i += 3) std::swap(bgr[i], bgr[i + 2]);      // RGB -> BGR
 }
 
+// an RGBA image (4 bytes per pixel, rows `step` bytes apart; 0: cols * 4) as a binary P6 PPM: R, G, B of every
+// pixel, alpha dropped
+inline void writePPM(const std::string& path, const uint8_t* rgba, int cols, int rows, size_t step = 0)
+{
+    if (!rgba || cols <= 0 || rows <= 0 || (step != 0 && step < (size_t)cols * 4)) throw std::runtime_error("writePPM: bad image for " + path);
+    if (step == 0) step = (size_t)cols * 4;
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + path);
+    std::fprintf(f, "P6\n%d %d\n255\n", cols, rows);
+    std::vector<unsigned char> row((size_t)cols * 3);
+    bool ok = true;
+    for (int y = 0; y < rows && ok; ++y) {
+        const uint8_t* src = rgba + (size_t)y * step;
+        for (int x = 0; x < cols; ++x) { row[3 * x] = src[4 * x]; row[3 * x + 1] = src[4 * x + 1]; row[3 * x + 2] = src[4 * x + 2]; }
+        ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) throw std::runtime_error("short write " + path);
+}
+
 inline void writePGM16(const std::string& path, const uint16_t* px, int cols, int rows)
 {
     std::FILE* f = std::fopen(path.c_str(), "wb");

@@ -233,6 +233,34 @@ namespace tfusion
                   "tf_render_image_type");
         }
 
+        // renderView (an addition: tf_view_render): the map from any camera -> world pose at any size, through a
+        // free view of that size (created on first use, released with the TopFu).  The tracker's state and output
+        // are untouched, so it may be called between frames.  cols / rows 0: the tracker's; at another size the
+        // tracker's intrinsics are scaled with the image (the same field of view).  On a swapping map the
+        // resident blocks only.
+        void renderView(cuda::image4u& image, const Affine3f& cam_to_world, RenderImageType type = RENDER_SHADED_GREYSCALE,
+                        int cols = 0, int rows = 0)
+        {
+            if (cols <= 0) cols = params_.cols;
+            if (rows <= 0) rows = params_.rows;
+            tf_view* v = nullptr;
+            for (const SizedView& e : views_)
+                if (e.cols == cols && e.rows == rows) v = e.view;
+            if (!v) {
+                const tf_view_params vp = { cols, rows, 0, 0 };
+                check(tf_view_create(ctx_, &vp, &v), "tf_view_create");
+                views_.push_back(SizedView{ cols, rows, v });
+            }
+            float rt[12], in[4];
+            affine_to_rt(cam_to_world, rt);
+            const tf_params c = params_.to_c();
+            const float sx = (float)cols / (float)c.cols, sy = (float)rows / (float)c.rows;
+            in[0] = c.fx * sx; in[1] = c.fy * sy; in[2] = c.cx * sx; in[3] = c.cy * sy;
+            image.create(rows, cols);
+            check(tf_view_render(v, cols == c.cols && rows == c.rows ? nullptr : in, rt, (int)type,
+                                 reinterpret_cast<uint8_t*>(image.ptr()), image.step()), "tf_view_render");
+        }
+
         Affine3f getCameraPose(int time = -1) const   // topfu.cpp:154-159
         {
             if (time > (int)poses_.size() || time < 0) time = (int)poses_.size() - 1;
@@ -381,8 +409,10 @@ namespace tfusion
             poses_.clear();
             poses_.push_back(affine_from_rt(rt));
         }
+        struct SizedView { int cols, rows; tf_view* view; };
         TopFuParams params_;
         tf_ctx* ctx_ = nullptr;
+        std::vector<SizedView> views_;    // renderView's free views, one per size (tf_destroy releases them)
         cuda::ProjectiveICP icp_;
         int frame_counter_ = 0;
         std::vector<Affine3f> poses_;

@@ -94,6 +94,26 @@ namespace tfusion
         Matx44f matrix;
         Affine3f() { *this = Identity(); }
         explicit Affine3f(const Matx44f& m) : matrix(m) {}
+        // cv::Affine3f(rvec, t): the rotation of a Rodrigues vector (axis * angle, radians) as cv::Rodrigues
+        // forms it -- R = cos(a) I + (1 - cos(a)) r r^T + sin(a) [r]x for the unit axis r, in double, then
+        // rounded to float -- and the translation t
+        Affine3f(const Vec3f& rvec, const Vec3f& t)
+        {
+            *this = Identity();
+            const double rx = rvec[0], ry = rvec[1], rz = rvec[2];
+            const double theta = std::sqrt(rx * rx + ry * ry + rz * rz);
+            if (theta >= 2.220446049250313e-16) {
+                const double c = std::cos(theta), s = std::sin(theta), c1 = 1.0 - c;
+                const double r[3] = { rx / theta, ry / theta, rz / theta };
+                const double rrt[9] = { r[0] * r[0], r[0] * r[1], r[0] * r[2], r[0] * r[1], r[1] * r[1], r[1] * r[2],
+                                        r[0] * r[2], r[1] * r[2], r[2] * r[2] };
+                const double r_x[9] = { 0, -r[2], r[1], r[2], 0, -r[0], -r[1], r[0], 0 };
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j)
+                        matrix(i, j) = (float)(c * (i == j ? 1.0 : 0.0) + c1 * rrt[3 * i + j] + s * r_x[3 * i + j]);
+            }
+            matrix(0, 3) = t[0]; matrix(1, 3) = t[1]; matrix(2, 3) = t[2];
+        }
         static Affine3f Identity()
         {
             Affine3f a(0);

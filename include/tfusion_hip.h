@@ -46,7 +46,9 @@ typedef enum tf_status {
     TF_HIP_ERROR = 4,
     TF_NO_DEVICE = 5,
     TF_INDEX_RANGE = 6,     /* tf_mesh_extract_indexed: the mesh has more than 2^32 - 1 vertices, nothing written */
-    TF_CAPACITY = 7         /* tf_map_load_resized: the file's live content does not fit the context's tables; context untouched */
+    TF_CAPACITY = 7         /* tf_map_load_resized: the file's live content does not fit the context's tables; context untouched.
+                               tf_view_find_visible / tf_view_render: more visible entries than the view's vis_capacity;
+                               the view's buffers untouched, the number needed reported */
 } tf_status;
 
 /* TopFuParams (tfusion/include/tfusion/topfu.hpp:28-60) restricted to the fields the
@@ -695,6 +697,63 @@ struct tf_resize_report {
  * reports the call as tf_map_load's, the placement kernels in ms[0].  Continuing a sequence after a resized load
  * reproduces the saving context's frames when n_buckets is the file's. */
 tf_status tf_map_load_resized(tf_ctx* ctx, const char* path, struct tf_resize_report* report);
+
+/* ---- free views (addition; DESIGN.md §5 Free views) -------------------------------------------------------
+ * A tf_view is a second render state bound to a context: its own image size, visible list, range image, raycast
+ * result, output image, expected-depth scratch and device state block.  It owns no scene data: it reads the
+ * context's hash, VBA and colour plane where they lie.  With it the map is rendered from any pose at any size
+ * (a thumbnail, a 1280x960 still from a 640x480 tracker) and the tracker does not notice: no view call changes a
+ * TF_BUF_* buffer of the context, its counters, its pose, its device state or the raycast pair's tile order, so
+ * a context with view calls between its frames produces, bit for bit, the frames of one without.
+ *
+ * tf_view_find_visible is VisualisationEngine::FindVisibleBlocks (buildCompleteVisibleList_device,
+ * VisualisationHelper.cu:17-50): the list holds every entry index i in [0, n_buckets + n_excess) with
+ * hash[i].ptr >= 0 and checkBlockVisibility<false> true for the view's cols, rows, the call's intrinsics and the
+ * context's voxelSize -- the plain frustum, never the enlarged one, also on a swapping context -- in ascending i
+ * (the reference's order is an atomic race; with a binding max_render_blocks the order decides which blocks
+ * CreateExpectedDepths drops).  If more entries qualify than vis_capacity the call returns TF_CAPACITY, *n_visible
+ * holds the number needed and the view's buffers stay as they were.
+ *
+ * On a swapping context a view sees the resident tier only (ptr >= 0): blocks held in the GlobalCache are not
+ * raycast.  Every call flushes a pending per-call frame, runs on the context stream after the caller's work on the
+ * default stream, and returns when done.  View memory is the context's: tf_destroy releases the views still alive
+ * (their handles are dead afterwards), tf_view_destroy releases one early.  tf_reset, the scene / map loads and
+ * tf_map_load_resized leave a view valid: it keeps nothing of the map between calls but what its last
+ * tf_view_find_visible wrote, and tf_view_render rebuilds that every time. */
+typedef struct tf_view tf_view;
+typedef struct tf_view_params {
+    int cols, rows;             /* positive multiples of 4 as tf_create demands, independent of the context's */
+    int vis_capacity;           /* 0: n_buckets + n_excess */
+    int max_render_blocks;      /* 0: the context's */
+} tf_view_params;
+tf_status tf_view_create(tf_ctx* ctx, const tf_view_params* params, tf_view** out);
+void      tf_view_destroy(tf_view* view);
+tf_status tf_view_get_params(tf_view* view, tf_view_params* params);    /* with the zeros resolved */
+/* FindVisibleBlocks; pose world -> camera; intr NULL: the context's.  *n_visible = entries found (may be NULL) */
+tf_status tf_view_find_visible(tf_view* view, const float intr[4], const float pose_rt[12], int* n_visible);
+/* CreateExpectedDepths over the view's list into the view's range image; pose world -> camera */
+tf_status tf_view_expected_depths(tf_view* view, const float intr[4], const float pose_rt[12]);
+/* castRay<false> over the view's range image into its raycast result; pose camera -> world */
+tf_status tf_view_raycast(tf_view* view, const float intr[4], const float invM_rt[12]);
+/* RenderImage's pixel stage (tf_render_type) on the view's raycast result into its image, and into dev_rgba
+ * (device, rows step bytes apart, 0: cols * 4; may be NULL); pose camera -> world */
+tf_status tf_view_shade(tf_view* view, const float intr[4], const float invM_rt[12], int type, uint8_t* dev_rgba, size_t step);
+/* renderICP on the view's raycast result (no new raycast, no visibility marks) into the caller's level-0 maps
+ * (device float4, steps in bytes, 0: cols * 16; either may be NULL); pose camera -> world */
+tf_status tf_view_icp_maps(tf_view* view, const float intr[4], const float invM_rt[12], void* points, size_t points_step,
+                           void* normals, size_t normals_step);
+/* find_visible, expected_depths, raycast and shade in one call from a camera -> world pose; world -> camera is
+ * the rigid inverse of it as the frame path inverts poses_.back() (topfu.cpp:281, 306).  TF_CAPACITY as above. */
+tf_status tf_view_render(tf_view* view, const float intr[4], const float c2w_rt[12], int type, uint8_t* dev_rgba, size_t step);
+typedef enum tf_view_buffer {
+    TF_VIEW_VISIBLE_IDS = 0,  /* int[vis_capacity]; the first n_visible are the list */
+    TF_VIEW_RANGE = 1,        /* float2[rows*cols] */
+    TF_VIEW_RAYCAST = 2,      /* float4[rows*cols] */
+    TF_VIEW_IMAGE = 3         /* uchar4[rows*cols] */
+} tf_view_buffer;
+tf_status tf_view_download(tf_view* view, int which, void* host, size_t bytes);
+/* the last find_visible's count and the last expected_depths' tile total (noTotalBlocks) */
+tf_status tf_view_stats(tf_view* view, int* n_visible, int* n_render_blocks);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tfusion_hip.h")
 
 TF_OK, TF_ICP_FAIL, TF_INVALID_ARG, TF_OOM, TF_HIP_ERROR, TF_NO_DEVICE = range(6)
 TF_INDEX_RANGE = 6                             # tf_mesh_extract_indexed: more vertices than a u32 numbers
-TF_CAPACITY = 7                                # tf_map_load_resized: the map does not fit the context's tables
+TF_CAPACITY = 7                                # tf_map_load_resized: the map does not fit the context's tables;
+                                               # tf_view_find_visible / tf_view_render: the view's list is too short
+TF_VIEW_VISIBLE_IDS, TF_VIEW_RANGE, TF_VIEW_RAYCAST, TF_VIEW_IMAGE = range(4)   # tf_view_download
 TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2       # tf_mesh_save_ply_attr's attrs
 TF_MESH_INDEXED = 4
 TF_MESH_WHOLE = 8                              # the reading over both tiers of a swapping scene (tf_mesh_extract_whole)
@@ -74,6 +76,11 @@ class TfResizeReport(ctypes.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
+
+
+class TfViewParams(ctypes.Structure):
+    """tf_view_params: a free view's size and capacities (0: n_buckets + n_excess / the context's)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("cols", "rows", "vis_capacity", "max_render_blocks")]
 
 
 class TfTotals(ctypes.Structure):
@@ -224,6 +231,17 @@ def load():
         "tf_map_load": ([P, ctypes.c_char_p], I),
         "tf_map_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfMapFileInfo)], I),
         "tf_map_load_resized": ([P, ctypes.c_char_p, ctypes.POINTER(TfResizeReport)], I),
+        "tf_view_create": ([P, ctypes.POINTER(TfViewParams), ctypes.POINTER(P)], I),
+        "tf_view_destroy": ([P], None),
+        "tf_view_get_params": ([P, ctypes.POINTER(TfViewParams)], I),
+        "tf_view_find_visible": ([P, P, P, ctypes.POINTER(I)], I),
+        "tf_view_expected_depths": ([P, P, P], I),
+        "tf_view_raycast": ([P, P, P], I),
+        "tf_view_shade": ([P, P, P, I, P, S], I),
+        "tf_view_icp_maps": ([P, P, P, P, S, P, S], I),
+        "tf_view_render": ([P, P, P, I, P, S], I),
+        "tf_view_download": ([P, I, P, S], I),
+        "tf_view_stats": ([P, ctypes.POINTER(I), ctypes.POINTER(I)], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():

@@ -23,7 +23,7 @@ extern "C" const char* tf_status_string(tf_status s)
     case TF_HIP_ERROR: return "HIP error";
     case TF_NO_DEVICE: return "no HIP device";
     case TF_INDEX_RANGE: return "more mesh vertices than a 32-bit index can number";
-    case TF_CAPACITY: return "the map's live content does not fit the context's tables";
+    case TF_CAPACITY: return "the content does not fit: a map's live content the context's tables, a view's visible entries its list";
     }
     return "unknown";
 }

@@ -4,6 +4,8 @@
 // where the caller keeps them, so pointers may be exchanged among members (swap_pyramids, the fused batch's
 // two dists buffers).  Three operations: one buffer, a group all or none, one buffer released early;
 // destruction frees what is still recorded.  A scoped temporary is a local TfCtxMem of the same functions.
+// Beside it TfCtxViews: the free views (tf_view.hip) alive on a context, so that the context can drop the host
+// part of those its caller never destroyed (their buffers are the registry's like any other).
 #pragma once
 #include <stddef.h>
 #include <initializer_list>
@@ -87,5 +89,49 @@ private:
     };
     int free_rec(const Rec& r) { return r.pinned ? fns_.pin_free(r.p) : fns_.dev_free(r.p); }
     TfMemFns fns_;
+    std::vector<Rec> recs_;
+};
+
+// The free views alive on a context.  A view's buffers come from the context's TfCtxMem; this records the host
+// objects: add at tf_view_create, remove at tf_view_destroy (false: not a live view of this context, nothing
+// to destroy), and at destruction `drop` for each one still recorded, newest first.  Declared after the
+// TfCtxMem in tf_ctx, so it goes first.
+class TfCtxViews {
+public:
+    typedef void (*Drop)(void* view);
+    TfCtxViews() {}
+    TfCtxViews(const TfCtxViews&) = delete;
+    TfCtxViews& operator=(const TfCtxViews&) = delete;
+    ~TfCtxViews()
+    {
+        for (size_t i = recs_.size(); i-- > 0;) recs_[i].drop(recs_[i].view);
+    }
+    // 0, or `oom` when the record could not grow (the view is then not recorded)
+    int add(void* view, Drop drop, int oom)
+    {
+        try { recs_.push_back(Rec{ view, drop }); } catch (const std::bad_alloc&) { return oom; }
+        return 0;
+    }
+    bool remove(const void* view)
+    {
+        for (size_t i = recs_.size(); view && i-- > 0;)
+            if (recs_[i].view == view) {
+                recs_.erase(recs_.begin() + (ptrdiff_t)i);
+                return true;
+            }
+        return false;
+    }
+    bool live(const void* view) const
+    {
+        for (const Rec& r : recs_) if (r.view == view) return true;
+        return false;
+    }
+    size_t count() const { return recs_.size(); }
+
+private:
+    struct Rec {
+        void* view;
+        Drop drop;
+    };
     std::vector<Rec> recs_;
 };

@@ -314,6 +314,7 @@ static __device__ __forceinline__ void render_snapshot(TfDevState* st, const flo
 // ---------------------------------------------------------------------------------------
 struct tf_ctx {
     TfCtxMem mem;            // owns every device and pinned buffer below (first: tf_create constructs it, the rest is zero)
+    TfCtxViews views;        // the free views alive on this context (tf_view.hip); destroyed before mem
     tf_params p;
     int device;
     hipStream_t stream;
@@ -489,6 +490,28 @@ struct tf_ctx {
     double ckpt_ms[8];                   // the last save / load: see tf_scene_ckpt_times
     int ckpt_timing;                     // TFUSION_CKPT_TIMING=1: the kernels are timed by events (and waited for)
 };
+// What the raycasting side (tf_render.hip) renders into: a render state -- the context's own (tf_ctx_target), or a
+// free view's (tf_view.hip) with its own size, intrinsics, buffers and device state block.  The scene (hash, VBA,
+// block grid, colour plane) is always the context's.
+struct TfTarget {
+    int W, H;
+    float fx, fy, cx, cy;
+    int vis_capacity, max_render_blocks;
+    int ed_lds_max_n;        // k_ed_fill reduces in LDS per /8 row up to this many visible entries (0: no bins)
+    int* visibleIds;
+    float* range;            // float2
+    float* raycast;          // float4
+    uchar4* image;
+    uint4* blockRec; int* blockTiles; int* blockOff; int* edChunk;   // expected-depths scratch, as in tf_ctx
+    uint4* edBins; int* edBinCnt; int2* edSpill;
+    TfDevState* st;          // the matrices, noVisibleEntries, mode / abort, noTotalBlocks the kernels exchange
+};
+static inline TfTarget tf_ctx_target(const tf_ctx* c)
+{
+    return TfTarget{ c->W, c->H, c->p.fx, c->p.fy, c->p.cx, c->p.cy, c->p.vis_capacity, c->p.max_render_blocks, c->ed_lds_max_n,
+                     c->visibleIds, c->range, c->raycast, c->grey, c->blockRec, c->blockTiles, c->blockOff, c->edChunk,
+                     c->edBins, c->edBinCnt, c->edSpill, c->st };
+}
 // the registry's status (tf_ctx_mem.h: the allocator's own code, unchanged) as the HIP error it is
 static inline hipError_t tf_mem_hip(int e) { return (hipError_t)e; }
 #define TF_CKPT_CHUNK_BLOCKS 4096        // 8 MiB of voxels (16 MiB with colour) per chunk, whatever n_blocks is
@@ -546,6 +569,14 @@ hipError_t tfk_fuse_tail(tf_ctx* c, const float* pose, int* rec, const uint16_t*
                          float* next_dists, const float* next_pose);
 hipError_t tfk_raycast(tf_ctx* c, int update_visible);
 hipError_t tfk_render_type(tf_ctx* c, int type);   // RenderImage pixel stage (tf_render_type) on raycast
+// the same stages over a render state that need not be the context's (a free view): castRay<false>, the pixel
+// stage, renderICP into the three levels pts / nrm (W x H, then halved twice), CreateExpectedDepths, and the mark
+// that makes the next projection pass clear the whole range buffer
+hipError_t tfk_raycast(tf_ctx* c, const TfTarget& t, unsigned char* visType);   // visType non-null: castRay<true>
+hipError_t tfk_render_type(tf_ctx* c, const TfTarget& t, int type);
+hipError_t tfk_icp_maps(tf_ctx* c, const TfTarget& t, float4* const pts[TF_LEVELS], float4* const nrm[TF_LEVELS]);
+hipError_t tfk_expected_depths(tf_ctx* c, const TfTarget& t, int project_done, int keep_bins);
+hipError_t ed_spill_all(tf_ctx* c, const TfTarget& t);
 // CreateICPMaps raycast + renderImage, one launch (frame path); next: + that frame's dists/pyramid/normals
 // + dists/pyramid/normals of pyr, bilateral of bil; fuse_ed: CreateExpectedDepths' fill in the same
 // grid (frame path, when tfk_ed_fused: then no separate tfk_expected_depths launch)

@@ -567,32 +567,34 @@ k_raycast(RayArgs a, const TfDevState* __restrict__ st, int tiles_x, int n_tiles
     raycast_tile<MODE>(a, st, tile, tiles_x, nullptr);
 }
 
-static void ray_args(tf_ctx* c, RayArgs& a)
+// the scene is the context's; the range image, the output, the size and the intrinsics the render state's
+static void ray_args(tf_ctx* c, const TfTarget& t, RayArgs& a)
 {
     a.s.hash = c->hash; a.s.vba = c->vba_guard; a.s.grid = c->bgrid; a.s.mask = (unsigned)(c->p.n_buckets - 1); a.s.n_buckets = c->p.n_buckets;
-    a.range = (const float2*)c->range; a.out = (float4*)c->raycast;
+    a.range = (const float2*)t.range; a.out = (float4*)t.raycast;
     a.visType = nullptr;
     a.grey = nullptr;
-    a.W = c->W; a.H = c->H;
-    a.invfx = 1.0f / c->p.fx; a.invfy = 1.0f / c->p.fy; a.ncx = -c->p.cx; a.ncy = -c->p.cy;
+    a.W = t.W; a.H = t.H;
+    a.invfx = 1.0f / t.fx; a.invfy = 1.0f / t.fy; a.ncx = -t.cx; a.ncy = -t.cy;
     a.oneOverVoxelSize = 1.0f / c->p.voxelSize; a.mu = c->p.mu;
 }
+static void ray_args(tf_ctx* c, RayArgs& a) { ray_args(c, tf_ctx_target(c), a); }
 
-static hipError_t launch_ray(tf_ctx* c, const RayArgs& a, int mode)
+hipError_t tfk_raycast(tf_ctx* c, const TfTarget& t, unsigned char* visType)
 {
-    const int tx = (c->W + 15) / 16, ty = (c->H + 15) / 16, n = tx * ty;
+    RayArgs a;
+    ray_args(c, t, a);
+    a.visType = visType;
+    const int tx = (t.W + 15) / 16, ty = (t.H + 15) / 16, n = tx * ty;
     const dim3 grid((n + 7) / 8 * 8);
-    if (mode == 0) hipLaunchKernelGGL(k_raycast<0>, grid, dim3(256), 0, c->stream, a, c->st, tx, n);
-    else hipLaunchKernelGGL(k_raycast<1>, grid, dim3(256), 0, c->stream, a, c->st, tx, n);
+    if (!visType) hipLaunchKernelGGL(k_raycast<0>, grid, dim3(256), 0, c->stream, a, t.st, tx, n);
+    else hipLaunchKernelGGL(k_raycast<1>, grid, dim3(256), 0, c->stream, a, t.st, tx, n);
     return hipGetLastError();
 }
 
 hipError_t tfk_raycast(tf_ctx* c, int update_visible)
 {
-    RayArgs a;
-    ray_args(c, a);
-    a.visType = update_visible ? c->visType : nullptr;
-    return launch_ray(c, a, update_visible ? 1 : 0);
+    return tfk_raycast(c, tf_ctx_target(c), update_visible ? c->visType : nullptr);
 }
 
 // the renderImage snapshot outside a frame (measurement: tf_time_stage of the raycast pair)
@@ -746,27 +748,29 @@ k_render_type(SceneView s, const float4* __restrict__ ray, int W, int H, float v
     }
 }
 
-hipError_t tfk_render_type(tf_ctx* c, int type)
+hipError_t tfk_render_type(tf_ctx* c, int type) { return tfk_render_type(c, tf_ctx_target(c), type); }
+
+hipError_t tfk_render_type(tf_ctx* c, const TfTarget& t, int type)
 {
     SceneView s; s.hash = c->hash; s.vba = c->vba_guard; s.grid = c->bgrid; s.mask = (unsigned)(c->p.n_buckets - 1); s.n_buckets = c->p.n_buckets;
-    const int n = c->W * c->H;
+    const int n = t.W * t.H;
     const dim3 g((n + 255) / 256), b(256);
-    const float4* ray = (const float4*)c->raycast;
+    const float4* ray = (const float4*)t.raycast;
     const float vs = c->p.voxelSize;
     const unsigned* cg = c->vba_rgb_guard;
     // RENDER_COLOUR_FROM_VOLUME without colour information: greyscale (VisualisationEngine_CUDA.cu:251-252)
     if (type == TF_RENDER_COLOUR_FROM_VOLUME && !c->p.voxel_rgb) type = TF_RENDER_SHADED_GREYSCALE;
     switch (type) {
     case TF_RENDER_COLOUR_FROM_VOLUME:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_VOLUME>, g, b, 0, c->stream, s, ray, c->W, c->H, vs, c->st, c->grey, cg); break;
+        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_VOLUME>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     case TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS>, g, b, 0, c->stream, s, ray, c->W, c->H, vs, c->st, c->grey, cg); break;
+        hipLaunchKernelGGL(k_render_type<TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     case TF_RENDER_COLOUR_FROM_NORMAL:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_NORMAL>, g, b, 0, c->stream, s, ray, c->W, c->H, vs, c->st, c->grey, cg); break;
+        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_NORMAL>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     case TF_RENDER_COLOUR_FROM_CONFIDENCE:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_CONFIDENCE>, g, b, 0, c->stream, s, ray, c->W, c->H, vs, c->st, c->grey, cg); break;
+        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_CONFIDENCE>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     default:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_SHADED_GREYSCALE>, g, b, 0, c->stream, s, ray, c->W, c->H, vs, c->st, c->grey, cg); break;
+        hipLaunchKernelGGL(k_render_type<TF_RENDER_SHADED_GREYSCALE>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     }
     return hipGetLastError();
 }
@@ -981,15 +985,17 @@ hipError_t tfk_tile_order_init(tf_ctx* c)
     return e;
 }
 
-hipError_t tfk_icp_maps(tf_ctx* c)
+hipError_t tfk_icp_maps(tf_ctx* c, const TfTarget& t, float4* const pts[TF_LEVELS], float4* const nrm[TF_LEVELS])
 {
     IcpMapArgs a;
-    a.ray = (const float4*)c->raycast;
-    for (int l = 0; l < TF_LEVELS; ++l) { a.pts[l] = c->prev_pts[l]; a.nrm[l] = c->prev_nrm[l]; }
-    a.W = c->W; a.H = c->H; a.voxelSize = c->p.voxelSize;
-    hipLaunchKernelGGL(k_icp_maps, dim3((c->W + 31) / 32, (c->H + 31) / 32), dim3(256), 0, c->stream, a, c->st);
+    a.ray = (const float4*)t.raycast;
+    for (int l = 0; l < TF_LEVELS; ++l) { a.pts[l] = pts[l]; a.nrm[l] = nrm[l]; }
+    a.W = t.W; a.H = t.H; a.voxelSize = c->p.voxelSize;
+    hipLaunchKernelGGL(k_icp_maps, dim3((t.W + 31) / 32, (t.H + 31) / 32), dim3(256), 0, c->stream, a, t.st);
     return hipGetLastError();
 }
+
+hipError_t tfk_icp_maps(tf_ctx* c) { return tfk_icp_maps(c, tf_ctx_target(c), c->prev_pts, c->prev_nrm); }
 
 hipError_t tfk_icp_maps_end(tf_ctx* c, int slot, TfAhead pyr, size_t pitch)
 {
@@ -1243,42 +1249,48 @@ k_ed_fill(EdArgs a, TfDevState* __restrict__ st)
     ed_fill_block<ED_MAX_W>(a, st, blockIdx.x, gridDim.x, L, !a.keep_bins);
 }
 
-hipError_t ed_spill_all(tf_ctx* c)
+hipError_t ed_spill_all(tf_ctx* c, const TfTarget& t)
 {
-    hipError_t e = hipMemsetAsync(c->edSpill, 0, sizeof(int2) * ed_nrows(c->H), c->stream);
-    const int2 all = make_int2(c->W, c->H);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->edSpill, &all, sizeof(int2), hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemsetAsync(t.edSpill, 0, sizeof(int2) * ed_nrows(t.H), c->stream);
+    const int2 all = make_int2(t.W, t.H);
+    if (e == hipSuccess) e = hipMemcpyAsync(t.edSpill, &all, sizeof(int2), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return e;
 }
+hipError_t ed_spill_all(tf_ctx* c) { return ed_spill_all(c, tf_ctx_target(c)); }
 
-void tf_ed_args(tf_ctx* c, EdArgs* out)
+// the hash and the voxel size are the context's, everything else the render state's
+static void ed_args(tf_ctx* c, const TfTarget& t, EdArgs& a)
 {
-    EdArgs& a = *out;
-    a.hash = c->hash; a.visibleIds = c->visibleIds; a.range = (float2*)c->range;
-    a.rec = c->blockRec; a.tiles = c->blockTiles; a.off = c->blockOff; a.chunk = c->edChunk;
-    a.spill = c->edSpill;
-    a.bins = c->edBins; a.bin_cnt = c->edBinCnt; a.keep_bins = 0; a.done = nullptr; a.fault = 0;
-    a.W = c->W; a.H = c->H;
-    a.rc = (c->W - 1) / TF_SUBSAMPLE + 1; a.rr = (c->H - 1) / TF_SUBSAMPLE + 1;
-    a.nrows = ed_nrows(c->H);
-    a.lds_max_n = c->ed_lds_max_n;
-    a.vcap = c->p.vis_capacity;
-    a.nchunk_max = c->p.vis_capacity / ED_CHUNK + 1;
-    a.fx = c->p.fx; a.fy = c->p.fy; a.cx = c->p.cx; a.cy = c->p.cy; a.voxelSize = c->p.voxelSize;
-    a.cap = (unsigned)c->p.max_render_blocks;
+    a.hash = c->hash; a.visibleIds = t.visibleIds; a.range = (float2*)t.range;
+    a.rec = t.blockRec; a.tiles = t.blockTiles; a.off = t.blockOff; a.chunk = t.edChunk;
+    a.spill = t.edSpill;
+    a.bins = t.edBins; a.bin_cnt = t.edBinCnt; a.keep_bins = 0; a.done = nullptr; a.fault = 0;
+    a.W = t.W; a.H = t.H;
+    a.rc = (t.W - 1) / TF_SUBSAMPLE + 1; a.rr = (t.H - 1) / TF_SUBSAMPLE + 1;
+    a.nrows = ed_nrows(t.H);
+    a.lds_max_n = t.ed_lds_max_n;
+    a.vcap = t.vis_capacity;
+    a.nchunk_max = t.vis_capacity / ED_CHUNK + 1;
+    a.fx = t.fx; a.fy = t.fy; a.cx = t.cx; a.cy = t.cy; a.voxelSize = c->p.voxelSize;
+    a.cap = (unsigned)t.max_render_blocks;
 }
+void tf_ed_args(tf_ctx* c, EdArgs* out) { ed_args(c, tf_ctx_target(c), *out); }
 
 // project_done: k_ed_project's pass already ran in the frame's k_integrate grid (frame path)
-hipError_t tfk_expected_depths(tf_ctx* c, int project_done, int keep_bins)
+hipError_t tfk_expected_depths(tf_ctx* c, const TfTarget& t, int project_done, int keep_bins)
 {
     EdArgs a;
-    tf_ed_args(c, &a);
+    ed_args(c, t, a);
     a.keep_bins = keep_bins;
-    if (!project_done) hipLaunchKernelGGL(k_ed_project, dim3(TF_ED_BLOCKS), dim3(256), 0, c->stream, a, c->st);
+    if (!project_done) hipLaunchKernelGGL(k_ed_project, dim3(TF_ED_BLOCKS), dim3(256), 0, c->stream, a, t.st);
     // one workgroup per LDS row (the atomic path grid-strides the same grid)
-    tf_launch(c, k_ed_fill, dim3(a.nrows), dim3(ED_THREADS), 0, a, c->st);
+    tf_launch(c, k_ed_fill, dim3(a.nrows), dim3(ED_THREADS), 0, a, t.st);
     return hipGetLastError();
+}
+hipError_t tfk_expected_depths(tf_ctx* c, int project_done, int keep_bins)
+{
+    return tfk_expected_depths(c, tf_ctx_target(c), project_done, keep_bins);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 // DESIGN.md §5 Scene checkpoints / Map checkpoints / Resized load, the file in tf_scene_file.h).  Everything that
 // is written in order here -- the records in hash-entry order, the lists the block copies walk, the re-hashed
 // placement, the visible list -- is made by one ordered compaction, the scheme the mesh passes use: a count per
-// 256 items, a prefix, an emit pass, as plain launches on the context stream:
+// 256 items, a prefix, an emit pass, as plain launches on the context stream (the skeleton: tf_compact.h, shared
+// with a free view's visible list, tf_view.hip):
 //
 //   k_ck_pass<false, P> : per 256-item group how many items take a place in each of pass P's (up to three) lists
 //   k_ck_prefix         : exclusive scan of the group counts (one workgroup: a count per 256 items) + the totals
@@ -26,6 +27,7 @@
 // A swapping context (tf_map_save / tf_map_load) differs by a uniform `sw`: the GlobalCache's swap state and stored
 // flag in the record predicate and in every record (version 2 of the file), the stored blocks as a second payload.
 #include "tf_host.h"
+#include "tf_compact.h"
 #include "tf_scene_file.h"
 
 #include <chrono>
@@ -33,7 +35,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#define CK_WG 256
 typedef unsigned ck_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned ck_u2 __attribute__((ext_vector_type(2)));
 
@@ -64,63 +65,6 @@ __device__ __forceinline__ void ck_tail_apply(unsigned tail, int at, int sw, uns
         swapState[at] = (unsigned char)(tail >> 8);
         swapFlags[at] = (unsigned char)(tail >> 16);
     }
-}
-
-// ---- the ordered compaction.  A pass P names its items 0 .. n - 1 and gives
-//   unsigned P::classify(i, i < n, item) : bit q set -- item i takes a place in list q (0 for i >= n); `item` is what
-//                                          emit needs of it again
-//   void P::emit(i, item, bits, at0, at1, at2) : for every i < n; at_q is the number of items below i with bit q
-// The skeleton owns the ballots, the per-wave tally in LDS and its two barriers (the first ends the previous group's
-// reads of the tally), the group count (count mode: grp[g]) and base + waves before + lanes below (emit mode: the
-// bases stand behind the counts, grp[ng + g]).  All 256 threads of a group reach both barriers.
-__device__ __forceinline__ void ck_add(int4& s, const int4 v) { s.x += v.x; s.y += v.y; s.z += v.z; }
-
-template <bool EMIT, class Pass>
-__global__ __launch_bounds__(CK_WG) void k_ck_pass(const Pass p, int n, int4* __restrict__ grp)
-{
-    __shared__ int4 wcnt[CK_WG / 64];
-    const int t = threadIdx.x, ng = (n + CK_WG - 1) / CK_WG, lane = t & 63, w = t >> 6;
-    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
-        const int i = g * CK_WG + t;
-        typename Pass::Item item;
-        const unsigned bits = p.classify(i, i < n, item);
-        const unsigned long long m0 = __ballot(bits & 1u), m1 = __ballot(bits & 2u), m2 = __ballot(bits & 4u);
-        __syncthreads();
-        if (lane == 0) wcnt[w] = make_int4(__popcll(m0), __popcll(m1), __popcll(m2), 0);
-        __syncthreads();
-        if (!EMIT) {
-            if (t == 0) {
-                int4 s = make_int4(0, 0, 0, 0);
-                for (int k = 0; k < CK_WG / 64; ++k) ck_add(s, wcnt[k]);
-                grp[g] = s;
-            }
-        } else {
-            int4 b = grp[ng + g];
-            for (int k = 0; k < w; ++k) ck_add(b, wcnt[k]);
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (i < n) p.emit(i, item, bits, b.x + __popcll(m0 & below), b.y + __popcll(m1 & below), b.z + __popcll(m2 & below));
-        }
-    }
-}
-
-// base[g] = sum of cnt[0, g), base[ng] = the totals.  One workgroup: thread t owns a contiguous slice.
-__global__ __launch_bounds__(CK_WG) void k_ck_prefix(const int4* __restrict__ cnt, int ng, int4* __restrict__ base)
-{
-    __shared__ int4 part[CK_WG];
-    const int t = threadIdx.x, per = (ng + CK_WG - 1) / CK_WG;
-    const int first = min(t * per, ng), last = min(first + per, ng);
-    int4 s = make_int4(0, 0, 0, 0);
-    for (int g = first; g < last; ++g) ck_add(s, cnt[g]);
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int4 run = make_int4(0, 0, 0, 0);
-        for (int k = 0; k < CK_WG; ++k) { const int4 v = part[k]; part[k] = run; ck_add(run, v); }
-        base[ng] = run;
-    }
-    __syncthreads();
-    s = part[t];
-    for (int g = first; g < last; ++g) { base[g] = s; ck_add(s, cnt[g]); }
 }
 
 // save: entry idx gets a record (HashEntry not ResetScene's, or visType or a cache byte != 0), the record carries a
@@ -338,10 +282,7 @@ struct CkVisPass {
     }
 };
 
-// ---- the launchers -----------------------------------------------------------------------------------
-static int ck_groups(int n) { return (n + CK_WG - 1) / CK_WG; }
-static int ck_grid(size_t items) { const size_t g = (items + CK_WG - 1) / CK_WG; return (int)(g < 1 ? 1 : g > 2048 ? 2048 : g); }
-
+// ---- the launchers (ck_groups, ck_grid, tfk_ck_count, tfk_ck_emit: tf_compact.h) ---------------------
 // what the staging buffer and its pinned twin hold: ckpt_chunk_blocks blocks (with their colour)
 static size_t ck_stage_bytes(const tf_ctx* c)
 {
@@ -357,23 +298,6 @@ static hipError_t tfk_ckpt_scratch(tf_ctx* c)
     return tf_mem_hip(c->mem.alloc_group({ TfCtxMem::dev(&c->ckptGroup, sizeof(int4) * (2 * ng + 2)),
                                            TfCtxMem::dev(&c->ckptStage, ck_stage_bytes(c)),
                                            TfCtxMem::pin(&c->ckptPinned, ck_stage_bytes(c), hipHostMallocDefault) }));
-}
-
-// a pass over n items with its scratch grp: [0, ng) the group counts, [ng, 2 ng] their bases and the totals.
-// count + prefix (nothing but grp is written); then, once the caller has seen the totals, emit
-template <class Pass>
-static hipError_t tfk_ck_count(tf_ctx* c, const Pass& p, int n, int4* grp)
-{
-    hipLaunchKernelGGL((k_ck_pass<false, Pass>), dim3(ck_grid((size_t)n)), dim3(CK_WG), 0, c->stream, p, n, grp);
-    hipLaunchKernelGGL(k_ck_prefix, dim3(1), dim3(CK_WG), 0, c->stream, (const int4*)grp, ck_groups(n), grp + ck_groups(n));
-    return hipGetLastError();
-}
-
-template <class Pass>
-static hipError_t tfk_ck_emit(tf_ctx* c, const Pass& p, int n, int4* grp)
-{
-    hipLaunchKernelGGL((k_ck_pass<true, Pass>), dim3(ck_grid((size_t)n)), dim3(CK_WG), 0, c->stream, p, n, grp);
-    return hipGetLastError();
 }
 
 static CkSavePass ck_save_pass(const tf_ctx* c)

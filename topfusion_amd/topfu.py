@@ -38,6 +38,129 @@ def _rt(m):
     return a.reshape(12)
 
 
+class View:
+    """A free view of a TopFu's map (tf_view, include/tfusion_hip.h): its own size, visible list, range image,
+    raycast result and image.  Rendering through it leaves the tracker's state and output untouched.  Poses are
+    3x4 / 4x4 [R|t]: `c2w` camera -> world, `w2c` world -> camera; `intr` (fx, fy, cx, cy), None: the context's.
+    Created by TopFu.view(); close() (or the with statement) releases it early, the TopFu's close() at the latest."""
+
+    def __init__(self, owner, cols, rows, vis_capacity=0, max_render_blocks=0):
+        self._owner = owner
+        self._h = None
+        vp = L.TfViewParams(int(cols), int(rows), int(vis_capacity), int(max_render_blocks))
+        h = ctypes.c_void_p()
+        L.check(L.load().tf_view_create(owner._h, ctypes.byref(vp), ctypes.byref(h)), "tf_view_create")
+        self._h = h
+        L.check(L.load().tf_view_get_params(h, ctypes.byref(vp)), "tf_view_get_params")
+        self.W, self.H = vp.cols, vp.rows
+        self.vis_capacity, self.max_render_blocks = vp.vis_capacity, vp.max_render_blocks
+        self.needed = 0               # entries the last find_visible found (also when it raised TF_CAPACITY)
+        owner._views.append(self)
+
+    def close(self):
+        if self._h and self._owner._h:          # (a closed TopFu has released its views already)
+            L.load().tf_view_destroy(self._h)
+        self._h = None
+        if self in self._owner._views:
+            self._owner._views.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _intr(intr):
+        return None if intr is None else np.ascontiguousarray(intr, np.float32).reshape(4)
+
+    def _handle(self):
+        if not self._h or not self._owner._h:
+            raise RuntimeError("the view (or its TopFu) is closed")
+        return self._h
+
+    def find_visible(self, w2c, intr=None):
+        """FindVisibleBlocks: the number of entries in the view's list.  TfError(TF_CAPACITY) when more qualify
+        than vis_capacity (`needed` then holds the number)."""
+        i, n = self._intr(intr), ctypes.c_int(0)
+        s = L.load().tf_view_find_visible(self._handle(), None if i is None else _ptr(i), _ptr(_rt(w2c)), ctypes.byref(n))
+        self.needed = n.value
+        L.check(s, "tf_view_find_visible")
+        return n.value
+
+    def expected_depths(self, w2c, intr=None):
+        i = self._intr(intr)
+        L.check(L.load().tf_view_expected_depths(self._handle(), None if i is None else _ptr(i), _ptr(_rt(w2c))),
+                "tf_view_expected_depths")
+
+    def raycast(self, c2w, intr=None):
+        i = self._intr(intr)
+        L.check(L.load().tf_view_raycast(self._handle(), None if i is None else _ptr(i), _ptr(_rt(c2w))), "tf_view_raycast")
+
+    def shade(self, c2w, type=0, intr=None):
+        """The pixel stage of `type` on the view's raycast result: (rows, cols, 4) uint8."""
+        i = self._intr(intr)
+        L.check(L.load().tf_view_shade(self._handle(), None if i is None else _ptr(i), _ptr(_rt(c2w)), int(type), None, 0),
+                "tf_view_shade")
+        return self.image()
+
+    def render(self, c2w, type=0, intr=None):
+        """The map from camera -> world pose `c2w`: (rows, cols, 4) uint8."""
+        i = self._intr(intr)
+        L.check(L.load().tf_view_render(self._handle(), None if i is None else _ptr(i), _ptr(_rt(c2w)), int(type), None, 0),
+                "tf_view_render")
+        return self.image()
+
+    def icp_maps(self, c2w, intr=None):
+        """renderICP on the view's raycast result: (points, normals), (rows, cols, 4) float32 each."""
+        out = [np.empty((self.H, self.W, 4), np.float32) for _ in range(2)]
+        hip = L.hip_runtime()
+        devs = [ctypes.c_void_p() for _ in range(2)]
+        try:
+            for d, o in zip(devs, out):
+                if hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(o.nbytes)) != 0:
+                    raise L.TfError(L.TF_OOM, "hipMalloc (view maps)")
+            i = self._intr(intr)
+            L.check(L.load().tf_view_icp_maps(self._handle(), None if i is None else _ptr(i), _ptr(_rt(c2w)), devs[0], 0,
+                                              devs[1], 0), "tf_view_icp_maps")
+            for d, o in zip(devs, out):
+                if hip.hipMemcpy(_ptr(o), d, ctypes.c_size_t(o.nbytes), 2) != 0:      # hipMemcpyDeviceToHost
+                    raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (view maps)")
+        finally:
+            for d in devs:
+                if d:
+                    hip.hipFree(d)
+        return out[0], out[1]
+
+    def _download(self, which, dtype, shape):
+        buf = np.empty(shape, dtype)
+        L.check(L.load().tf_view_download(self._handle(), which, _ptr(buf), buf.nbytes), "tf_view_download")
+        return buf
+
+    def stats(self):
+        nv, nb = ctypes.c_int(0), ctypes.c_int(0)
+        L.check(L.load().tf_view_stats(self._handle(), ctypes.byref(nv), ctypes.byref(nb)), "tf_view_stats")
+        return {"noVisibleEntries": nv.value, "noTotalBlocks": nb.value}
+
+    def visible_ids(self):
+        return self._download(L.TF_VIEW_VISIBLE_IDS, np.int32, (self.vis_capacity,))[:self.stats()["noVisibleEntries"]]
+
+    def range_image(self):
+        return self._download(L.TF_VIEW_RANGE, np.float32, (self.H, self.W, 2))
+
+    def raycast_result(self):
+        return self._download(L.TF_VIEW_RAYCAST, np.float32, (self.H, self.W, 4))
+
+    def image(self):
+        return self._download(L.TF_VIEW_IMAGE, np.uint8, (self.H, self.W, 4))
+
+
 class TopFu:
     """tfusion::TopFu on one MI355X (one HIP stream per instance)."""
 
@@ -52,11 +175,20 @@ class TopFu:
         self.W, self.H = self.params_.cols, self.params_.rows
         self.n_total = self.params_.n_buckets + self.params_.n_excess
         self._framed = False
+        self._views = []
 
     def close(self):
         if getattr(self, "_h", None):
-            L.load().tf_destroy(self._h)
+            L.load().tf_destroy(self._h)      # releases the views still alive
             self._h = None
+            for v in list(getattr(self, "_views", [])):
+                v._h = None
+            self._views = []
+
+    def view(self, cols=None, rows=None, vis_capacity=0, max_render_blocks=0):
+        """A free view of the map (View): cols x rows (None: the context's), a visible list of vis_capacity entries
+        (0: n_buckets + n_excess) and a tile cap of max_render_blocks (0: the context's)."""
+        return View(self, self.W if cols is None else cols, self.H if rows is None else rows, vis_capacity, max_render_blocks)
 
     def __del__(self):
         try:
