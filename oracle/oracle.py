@@ -69,6 +69,7 @@ def lib(omp=False):
         L.tfo_points_normals.argtypes = [P, ctypes.c_int, ctypes.c_int] + [ctypes.c_float] * 4 + [P, P]
         L.tfo_resize_points_normals.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P, P]
         L.tfo_icp_reduce.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int] + [ctypes.c_float] * 6 + [P, P]
+        L.tfo_test_icp_rows.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int] + [ctypes.c_float] * 6 + [P, P, P]
         L.tfo_icp_step.argtypes = [P, P, ctypes.POINTER(ctypes.c_double)]; L.tfo_icp_step.restype = ctypes.c_int
         L.tfo_rigid_mul.argtypes = [P, P, P]
         L.tfo_rigid_inv.argtypes = [P, P]
@@ -228,6 +229,16 @@ def icp_reduce(vcurr, ncurr, vprev, nprev, fx, fy, cx, cy, min_cosine, dist2_thr
     lib().tfo_icp_reduce(ptr(vcurr), ptr(ncurr), ptr(vprev), ptr(nprev), W, H, fx, fy, cx, cy,
                          min_cosine, dist2_thres, ptr(a), ptr(out))
     return out
+
+
+def icp_rows(vcurr, ncurr, vprev, nprev, fx, fy, cx, cy, min_cosine, dist2_thres, aff):
+    """Test-only: (find_coresp's return code per pixel u8[H, W], the row per pixel f32[H, W, 7])."""
+    H, W = vcurr.shape[:2]
+    codes, rows = np.empty((H, W), np.uint8), np.empty((H, W, 7), np.float32)
+    a = np.ascontiguousarray(aff, np.float32).reshape(12)
+    lib().tfo_test_icp_rows(ptr(np.ascontiguousarray(vcurr)), ptr(np.ascontiguousarray(ncurr)), ptr(np.ascontiguousarray(vprev)),
+                            ptr(np.ascontiguousarray(nprev)), W, H, fx, fy, cx, cy, min_cosine, dist2_thres, ptr(a), ptr(codes), ptr(rows))
+    return codes, rows
 
 
 def icp_step(sums27, affine):

@@ -473,6 +473,22 @@ void tfo_icp_reduce(const float* vcurr, const float* ncurr, const float* vprev, 
     free(partial);
 }
 
+/* test-only: icp_row per pixel in raster order -- the return code of find_coresp (0 found, 40, 80, 120, 160,
+   200: the five rejection tests in their order) and the 7-vector row (zeros where rejected), the same
+   function tfo_icp_reduce sums (tests/test_oracle_front_pin.py) */
+void tfo_test_icp_rows(const float* vcurr, const float* ncurr, const float* vprev, const float* nprev,
+                       int W, int H, float fx, float fy, float cx, float cy,
+                       float min_cosine, float dist2_thres, const float aff[12], uint8_t* codes, float* rows)
+{
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            float* row = rows + 7 * ((size_t)y * W + x);
+            const int code = icp_row(vcurr, ncurr, vprev, nprev, W, H, x, y, fx, fy, cx, cy, min_cosine, dist2_thres, aff, row);
+            if (code) for (int k = 0; k < 7; ++k) row[k] = 0.f;
+            codes[(size_t)y * W + x] = (uint8_t)code;
+        }
+}
+
 /* cv::determinant(Matx66f): LU with partial pivoting in float (eps 10*FLT_EPSILON), pivot product in double */
 static double cv_det6(const float Ain[36])
 {

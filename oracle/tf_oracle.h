@@ -18,7 +18,11 @@
  * the per-pixel allocation walk, block visibility, block projection into rendering blocks, the pixel shaders) are compiled
  * for the host by oracle/ref_pin/ref_pin_stages.cpp behind declaration-only OpenCV / CUDA
  * stand-ins and pin the stage functions here (tests/golden/stage_pin_*.bin,
- * tests/test_oracle_stage_pin.py).  Everything else (imgproc.cu, proj_icp.cu, the allocation-list and visible-list kernels, the OpenCV algebra) is
+ * tests/test_oracle_stage_pin.py).  The per-pixel kernels of imgproc.cu and find_coresp of proj_icp.cu run on
+ * the host over the executing stand-ins of oracle/ref_pin/cuda_exec (the canonical numerics below, as code) and
+ * pin the stateless stage functions and the ICP row (oracle/ref_pin/ref_pin_front.cpp, tests/golden/front_pin_*.bin,
+ * tests/test_oracle_front_pin.py).  Everything else (the two ICP reduction trees, the allocation-list and
+ * visible-list kernels, the OpenCV algebra) is
  * "parity unpinned": restated from the cited reference lines under the canonical numerics below.
  *
  * Canonical numerics (the reference's CUDA build uses --ftz --prec-div=false
@@ -117,6 +121,11 @@ void tfo_resize_points_normals(const float* vsrc, const float* nsrc, int W, int 
 void tfo_icp_reduce(const float* vcurr, const float* ncurr, const float* vprev, const float* nprev,
                     int W, int H, float fx, float fy, float cx, float cy,
                     float min_cosine, float dist2_thres, const float aff[12], float out27[27]);
+/* test-only: find_coresp's return code and the row per pixel, as tfo_icp_reduce forms them (rows: 7 floats
+   per pixel, zeros where the code is not 0) */
+void tfo_test_icp_rows(const float* vcurr, const float* ncurr, const float* vprev, const float* nprev,
+                       int W, int H, float fx, float fy, float cx, float cy,
+                       float min_cosine, float dist2_thres, const float aff[12], uint8_t* codes, float* rows);
 /* det check + solve + Rodrigues + compose (projective_icp.cpp:190-210); returns 1 ok, 0 fail */
 int tfo_icp_step(const float sums27[27], float affine_rt[12], double* det_out);
 /* test-only: the pose algebra tfo_icp_step uses (canonical = the GPU's default; OpenCV 2.4.9 or

@@ -15,6 +15,11 @@ container, where /root/reference exists; the GPU box only reads the committed fi
      conditions (pin_scenes.check_coverage) are asserted before a file is put here (layouts in
      tests/test_oracle_stage_pin.py).
 
+  4. The same make target compiles oracle/ref_pin/ref_pin_front.cpp: the reference's imgproc.cu and proj_icp.cu
+     themselves, for the host, over the executing CUDA stand-ins of oracle/ref_pin/cuda_exec.  For every case of
+     tests/front_pin_cases.py it writes front_pin_<case>_p<k>.bin (layouts there); the coverage conditions are
+     asserted before a file is put here, and stale parts of a case are removed.
+
     python tests/golden/make_golden.py
 """
 import os
@@ -45,6 +50,27 @@ def run_stage_pin(exe, out_dir):
             assert os.path.getsize(path) <= P.MAX_GOLDEN_BYTES, (path, os.path.getsize(path))
 
 
+def run_front_pin(exe, out_dir):
+    """Runs the front pin program over every case into out_dir and checks the coverage conditions."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import front_pin_cases as F
+    import pin_scenes as P
+    from oracle import oracle as O
+    jobs = [(F.front_case(W, H), lambda W=W, H=H: F.front_inputs(W, H)) for W, H in F.FRONT_SIZES]
+    jobs += [(F.icp_case(W, H), lambda W=W, H=H: F.icp_inputs(O, W, H)) for W, H in F.ICP_SIZES]
+    for case, inputs in jobs:
+        src = os.path.join(out_dir, case + ".in")
+        P.write_pin(src, inputs())
+        subprocess.run([exe, src, out_dir, case], check=True, stdout=subprocess.DEVNULL)
+        os.remove(src)
+        for path in F.golden_parts(case, out_dir):
+            assert os.path.getsize(path) <= P.MAX_GOLDEN_BYTES, (path, os.path.getsize(path))
+    for W, H in F.FRONT_SIZES:
+        F.check_front_coverage(W, H)
+    for W, H in F.ICP_SIZES:
+        F.check_icp_coverage(F.golden(F.icp_case(W, H), out_dir), W, H)
+
+
 def main():
     if not os.path.isdir("/root/reference/tfusion/include"):
         sys.exit("reference tree absent: the committed goldens stay as they are")
@@ -55,6 +81,14 @@ def main():
         sys.exit("oracle/_ref/ref_pin_stages was not built: the stage_pin goldens stay as they are")
     with tempfile.TemporaryDirectory() as tmp:
         run_stage_pin(exe, tmp)
+        front = os.path.join(ROOT, "oracle", "_ref", "ref_pin_front")
+        if os.path.exists(front):
+            run_front_pin(front, tmp)
+            for name in os.listdir(HERE):
+                if name.startswith("front_pin_") and name.endswith(".bin"):
+                    os.remove(os.path.join(HERE, name))
+        else:
+            print("oracle/_ref/ref_pin_front was not built: the front_pin goldens stay as they are")
         for name in sorted(os.listdir(tmp)):
             shutil.copyfile(os.path.join(tmp, name), os.path.join(HERE, name))
             print("wrote", name)
