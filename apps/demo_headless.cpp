@@ -18,6 +18,7 @@
 //                        pose (translation in metres, rotation as a Rodrigues vector) at that size (default: the
 //                        frames'), through a free view (TopFu::renderView), as a binary PPM.  With 0 frames and
 //                        --load-scene: a saved map's picture and nothing else.
+//   ... --view-whole   : that view reads the GlobalCache of a swapping map as well as the resident blocks
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -38,7 +39,7 @@ using namespace tfusion;
 int main(int argc, char** argv)
 {
     std::string pgm, ppm, mesh, load_scene, save_scene, capacity, view_out, view_pose, view_size;
-    bool mesh_normals = false, mesh_indexed = false;
+    bool mesh_normals = false, mesh_indexed = false, view_whole = false;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--pgm") && i + 1 < argc) pgm = argv[++i];
@@ -52,6 +53,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--view-size") && i + 1 < argc) view_size = argv[++i];
         else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
         else if (!std::strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
+        else if (!std::strcmp(argv[i], "--view-whole")) view_whole = true;
         else pos.push_back(argv[i]);
     }
     int frames = pos.size() > 0 ? std::atoi(pos[0]) : (pgm.empty() ? 100 : 1 << 30);
@@ -162,7 +164,8 @@ int main(int argc, char** argv)
             return 1;
         }
         cuda::image4u free_view;
-        topfu->renderView(free_view, Affine3f(Vec3f(p[3], p[4], p[5]), Vec3f(p[0], p[1], p[2])), TopFu::RENDER_SHADED_GREYSCALE, vc, vr);
+        topfu->renderView(free_view, Affine3f(Vec3f(p[3], p[4], p[5]), Vec3f(p[0], p[1], p[2])), TopFu::RENDER_SHADED_GREYSCALE, vc, vr,
+                          view_whole);
         std::vector<unsigned char> px((size_t)vc * vr * 4);
         free_view.download(px.data(), (size_t)vc * 4);
         io::writePPM(view_out, px.data(), vc, vr);

@@ -257,6 +257,15 @@ namespace tfusion
         const Vector2i& imgSize() const { return imgSize_; }
         // the free view this state is bound to (nullptr: never bound)
         tf_view* view() const { return view_; }
+        // the reading of a bound state (an addition: tf_set_view_reading): on a swapping scene FindVisibleBlocks,
+        // CreateExpectedDepths, RenderImage and CreateICPMaps given this state then see the blocks held in the
+        // GlobalCache as well as the resident ones.  Kept across a re-binding; no effect on an unbound state.
+        void setWhole(bool whole)
+        {
+            whole_ = whole;
+            if (view_) tf_engine_check(tf_set_view_reading(view_, whole_ ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT), "RenderState: tf_set_view_reading");
+        }
+        bool whole() const { return whole_; }
         // binds a view of imgSize on `ctx` (the first use; again when given another scene's context)
         tf_view* bind(tf_ctx* ctx)
         {
@@ -265,6 +274,7 @@ namespace tfusion
             view_ = nullptr;
             const tf_view_params vp = { imgSize_.x, imgSize_.y, 0, 0 };
             tf_engine_check(tf_view_create(ctx, &vp, &view_), "RenderState: tf_view_create");
+            tf_engine_check(tf_set_view_reading(view_, whole_ ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT), "RenderState: tf_set_view_reading");
             ctx_ = ctx;
             return view_;
         }
@@ -273,6 +283,7 @@ namespace tfusion
         float vf_min_, vf_max_;
         tf_view* view_ = nullptr;
         tf_ctx* ctx_ = nullptr;
+        bool whole_ = false;
     };
     class RenderState_VH : public RenderState
     {

@@ -236,10 +236,11 @@ namespace tfusion
         // renderView (an addition: tf_view_render): the map from any camera -> world pose at any size, through a
         // free view of that size (created on first use, released with the TopFu).  The tracker's state and output
         // are untouched, so it may be called between frames.  cols / rows 0: the tracker's; at another size the
-        // tracker's intrinsics are scaled with the image (the same field of view).  On a swapping map the
-        // resident blocks only.
+        // tracker's intrinsics are scaled with the image (the same field of view).  whole: on a swapping map the
+        // blocks held in the GlobalCache as well as the resident ones (tf_set_view_reading; set before every call, so
+        // one view per size serves both readings).
         void renderView(cuda::image4u& image, const Affine3f& cam_to_world, RenderImageType type = RENDER_SHADED_GREYSCALE,
-                        int cols = 0, int rows = 0)
+                        int cols = 0, int rows = 0, bool whole = false)
         {
             if (cols <= 0) cols = params_.cols;
             if (rows <= 0) rows = params_.rows;
@@ -251,6 +252,7 @@ namespace tfusion
                 check(tf_view_create(ctx_, &vp, &v), "tf_view_create");
                 views_.push_back(SizedView{ cols, rows, v });
             }
+            check(tf_set_view_reading(v, whole ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT), "tf_set_view_reading");
             float rt[12], in[4];
             affine_to_rt(cam_to_world, rt);
             const tf_params c = params_.to_c();

@@ -714,8 +714,20 @@ tf_status tf_map_load_resized(tf_ctx* ctx, const char* path, struct tf_resize_re
  * CreateExpectedDepths drops).  If more entries qualify than vis_capacity the call returns TF_CAPACITY, *n_visible
  * holds the number needed and the view's buffers stay as they were.
  *
- * On a swapping context a view sees the resident tier only (ptr >= 0): blocks held in the GlobalCache are not
- * raycast.  Every call flushes a pending per-call frame, runs on the context stream after the caller's work on the
+ * A view has a reading of the scene (tf_set_view_reading).  TF_VIEW_RESIDENT, the default: the blocks in the VBA
+ * (ptr >= 0), as the tracker sees them; on a swapping context the blocks held in the GlobalCache are not raycast.
+ * TF_VIEW_WHOLE: both tiers of a swapping context -- every stage behaves as the resident stage would on the scene
+ * resolved by the table above (the mesher's, TF_MESH_WHOLE): an entry holds its active block, per voxel
+ * CombineVoxelInformation(stored, active, maxW) while a merge is pending, or its stored block, and the block at a
+ * position is the first entry of its chain that resolves.  tf_view_find_visible then lists the entries that resolve
+ * (ptr >= 0, or ptr == -1 with stored data), CreateExpectedDepths projects each of them, and every voxel read of the
+ * raycast and of the pixel stages (the uninterpolated read, the interpolation corners, the confidence, the SDF
+ * gradient) goes through the resolution.  Nothing but the view's own buffers is written: hash, VBA, swap state, flags,
+ * stored blocks and counters stay bit-identical.  Without stored data -- a context without swapping, where the
+ * reading is accepted and runs the resident kernels, or a swapping one before its first eviction -- the whole
+ * reading equals the resident one byte for byte in every view buffer.
+ *
+ * Every call flushes a pending per-call frame, runs on the context stream after the caller's work on the
  * default stream, and returns when done.  View memory is the context's: tf_destroy releases the views still alive
  * (their handles are dead afterwards), tf_view_destroy releases one early.  tf_reset, the scene / map loads and
  * tf_map_load_resized leave a view valid: it keeps nothing of the map between calls but what its last
@@ -729,6 +741,15 @@ typedef struct tf_view_params {
 tf_status tf_view_create(tf_ctx* ctx, const tf_view_params* params, tf_view** out);
 void      tf_view_destroy(tf_view* view);
 tf_status tf_view_get_params(tf_view* view, tf_view_params* params);    /* with the zeros resolved */
+typedef enum tf_view_reading {
+    TF_VIEW_RESIDENT = 0,       /* the VBA's blocks (the default) */
+    TF_VIEW_WHOLE = 1           /* the VBA's and the GlobalCache's */
+} tf_view_reading;
+/* the reading of every later call on the view; any other value: TF_INVALID_ARG.  tf_view_params keeps its layout.
+ * (Named beside the tf_view_* family, not in it: that family is the eleven calls above, and its list is pinned by
+ * tests/test_view_host.py.) */
+tf_status tf_set_view_reading(tf_view* view, int reading);
+tf_status tf_get_view_reading(tf_view* view, int* reading);
 /* FindVisibleBlocks; pose world -> camera; intr NULL: the context's.  *n_visible = entries found (may be NULL) */
 tf_status tf_view_find_visible(tf_view* view, const float intr[4], const float pose_rt[12], int* n_visible);
 /* CreateExpectedDepths over the view's list into the view's range image; pose world -> camera */

@@ -18,6 +18,7 @@ TF_INDEX_RANGE = 6                             # tf_mesh_extract_indexed: more v
 TF_CAPACITY = 7                                # tf_map_load_resized: the map does not fit the context's tables;
                                                # tf_view_find_visible / tf_view_render: the view's list is too short
 TF_VIEW_VISIBLE_IDS, TF_VIEW_RANGE, TF_VIEW_RAYCAST, TF_VIEW_IMAGE = range(4)   # tf_view_download
+TF_VIEW_RESIDENT, TF_VIEW_WHOLE = 0, 1      # tf_set_view_reading
 TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2       # tf_mesh_save_ply_attr's attrs
 TF_MESH_INDEXED = 4
 TF_MESH_WHOLE = 8                              # the reading over both tiers of a swapping scene (tf_mesh_extract_whole)
@@ -234,6 +235,8 @@ def load():
         "tf_view_create": ([P, ctypes.POINTER(TfViewParams), ctypes.POINTER(P)], I),
         "tf_view_destroy": ([P], None),
         "tf_view_get_params": ([P, ctypes.POINTER(TfViewParams)], I),
+        "tf_set_view_reading": ([P, I], I),
+        "tf_get_view_reading": ([P, ctypes.POINTER(I)], I),
         "tf_view_find_visible": ([P, P, P, ctypes.POINTER(I)], I),
         "tf_view_expected_depths": ([P, P, P], I),
         "tf_view_raycast": ([P, P, P], I),

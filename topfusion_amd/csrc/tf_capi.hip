@@ -86,7 +86,7 @@ static bool params_valid(const tf_params* p)
     if ((double)p->cols * p->rows * 64.0 > 2147483000.0) return false;
     if (p->cols > 65535 || p->rows > 65535) return false;               // k_ed_fill's 16-bit box records
     if (p->use_swapping && (p->swap_transfer_blocks <= 0 || p->swap_transfer_blocks > p->n_buckets + p->n_excess)) return false;
-    // the mesher's whole reading addresses a stored voxel as entry * 512 + lin in an int (tf_mesh_dev.h, MeshBlk):
+    // the mesher's whole reading addresses a stored voxel as entry * 512 + lin in an int (tf_tier.h, TierBlk):
     // the table must stay below 2^22 entries (the reference's has 1.18 M; 2^22 would be 8 GiB of GlobalCache)
     if (p->use_swapping && (long long)p->n_buckets + p->n_excess > (1 << 22) - 1) return false;
     // the GlobalCache holds Voxel_s blocks: a swapping colour scene would need the colour half

@@ -44,6 +44,11 @@ __device__ __forceinline__ uint4 ed_bin_pack(unsigned ulx, unsigned uly, unsigne
 // by k_ed_fill from plain prefix sums: no counter atomics, no last-workgroup ticket, no fence.
 // Runs as workgroup `bid` of `nblk`: its own launch (k_ed_project) or the leading workgroups
 // of k_integrate's grid (the stages share no data: both only read the visible list).
+// PTR_MIN: the block pointer from which a listed entry has a block to project -- 0, as the reference's
+// `ptr >= 0`; -1 for a free view's whole reading, whose list holds only entries that resolve in either tier
+// (tf_view.hip), a swapped-out one with stored data (ptr -1) among them.  Nothing else of the entry but its
+// position is read.
+template <int PTR_MIN = 0>
 __device__ __forceinline__ void ed_project_block(const EdArgs& a, const TfDevState* __restrict__ st, int bid, int nblk)
 {
     if (st->abort || st->mode == 0) return;          // ICP failed, or frame 0 (no rendering)
@@ -106,7 +111,7 @@ __device__ __forceinline__ void ed_project_block(const EdArgs& a, const TfDevSta
         if (i < n) {
             TfHashEntry e = a.hash[a.visibleIds[i]];
             uint4 rec = make_uint4(0xffffffffu, 0xffffffffu, 0u, 0u);
-            if (e.ptr >= 0) {
+            if (e.ptr >= PTR_MIN) {
                 int ulx = a.W / TF_SUBSAMPLE, uly = a.H / TF_SUBSAMPLE, lrx = -1, lry = -1;
                 float zmin = TF_FAR_AWAY, zmax = TF_VERY_CLOSE;
                 for (int corner = 0; corner < 8; ++corner) {

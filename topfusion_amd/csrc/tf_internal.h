@@ -505,12 +505,14 @@ struct TfTarget {
     uint4* blockRec; int* blockTiles; int* blockOff; int* edChunk;   // expected-depths scratch, as in tf_ctx
     uint4* edBins; int* edBinCnt; int2* edSpill;
     TfDevState* st;          // the matrices, noVisibleEntries, mode / abort, noTotalBlocks the kernels exchange
+    int whole;               // a free view's reading (TF_VIEW_WHOLE): the scene over both tiers of a swapping context;
+                             // 0 for the context's own render state
 };
 static inline TfTarget tf_ctx_target(const tf_ctx* c)
 {
     return TfTarget{ c->W, c->H, c->p.fx, c->p.fy, c->p.cx, c->p.cy, c->p.vis_capacity, c->p.max_render_blocks, c->ed_lds_max_n,
                      c->visibleIds, c->range, c->raycast, c->grey, c->blockRec, c->blockTiles, c->blockOff, c->edChunk,
-                     c->edBins, c->edBinCnt, c->edSpill, c->st };
+                     c->edBins, c->edBinCnt, c->edSpill, c->st, 0 };
 }
 // the registry's status (tf_ctx_mem.h: the allocator's own code, unchanged) as the HIP error it is
 static inline hipError_t tf_mem_hip(int e) { return (hipError_t)e; }

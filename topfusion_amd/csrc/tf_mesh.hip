@@ -63,13 +63,13 @@ struct MeshHasBlock {
         return false;
     }
 };
-// ... the whole reading's: entries whose block resolves in either tier (mesh_entry_resolves)
+// ... the whole reading's: entries whose block resolves in either tier (tier_entry_resolves)
 struct MeshHasData {
     MeshSceneWhole s;
     long long* count;
     __device__ __forceinline__ bool operator()(int idx) const
     {
-        if (mesh_entry_resolves(s, idx)) return true;
+        if (tier_entry_resolves(s, idx)) return true;
         if (count) count[idx] = 0;
         return false;
     }
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_slot_count(MeshSceneWhole s, in
     const int ngroups = (s.n_total + TFM_WG - 1) / TFM_WG;
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         const int idx = g * TFM_WG + t;
-        const bool r = idx < s.n_total && mesh_entry_resolves(s, idx);
+        const bool r = idx < s.n_total && tier_entry_resolves(s, idx);
         const int c = __popcll(__ballot(r));
         __syncthreads();             // the previous group's reads of wsum
         if ((t & 63) == 0) wsum[t >> 6] = c;
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(TFM_WG) void k_mesh_slot_assign(MeshSceneWhole s, c
         for (int i = t; i < g; i += TFM_WG) below += gcount[i];
         below = wave_sum(below);
         const int idx = g * TFM_WG + t;
-        const bool r = idx < s.n_total && mesh_entry_resolves(s, idx);
+        const bool r = idx < s.n_total && tier_entry_resolves(s, idx);
         const unsigned long long bal = __ballot(r);
         __syncthreads();             // the previous group's reads of wsum / red
         if (lane == 0) { wsum[wave] = __popcll(bal); red[wave] = below; }

@@ -3,15 +3,16 @@
 // LDS tiles of a hash entry's corner voxels with their gradient fill and cube read, the stores and the
 // <NORMALS, COLOURS> dispatch.  Every piece that holds a barrier says so, and says what its caller may
 // assume before and after.  The pieces that look at a block take the reading of the scene -- resident, or
-// whole: both tiers of a swapping scene -- as the scene's type; the whole reading's resolution of a block
-// (mesh_resolve_entry, mesh_block_resolve, mesh_voxel_whole) stands once, beside mesh_block_look.
+// whole: both tiers of a swapping scene -- as the scene's type; the rule of what an entry holds across the tiers
+// is tf_tier.h's (shared with the free views), the mesher's look-up and voxel read over it (mesh_block_resolve,
+// mesh_voxel_whole) stand once, beside mesh_block_look.
 #pragma once
 
 #include <type_traits>
 
 #include "tf_internal.h"
 #include "tf_mesh.h"
-#include "tf_swap_combine.h"
+#include "tf_tier.h"
 
 #define TFM_WG 512               // threads per workgroup = voxels per block = entries per group
 #define TFM_TILE 9
@@ -35,15 +36,6 @@ struct MeshSceneWhole {
     const unsigned char* state;  // HashSwapState::state per entry
     const unsigned char* flags;  // hasStoredData per entry
     const TfVoxel* store;        // storedVoxelBlocks: 512 voxels per entry
-};
-
-// A resolved block: where its voxels lie.  act = the VBA voxel offset (ptr * 512) or TF_VOFF_NONE, sto = the
-// GlobalCache voxel offset (entry * 512; tf_create bounds the table so it fits an int) or TFM_STO_NONE.
-// Both: the voxel is CombineVoxelInformation(stored, active); neither: the block is missing.  ent = the hash
-// entry the block was found at (-1: missing) -- what the indexed form keys a block's edge bits by.
-#define TFM_STO_NONE (-1)
-struct MeshBlk {
-    int act, sto, ent;
 };
 
 // The entries of group g that pred(idx) accepts, into live[] (any order); returns their number.  pred
@@ -101,59 +93,18 @@ __device__ __forceinline__ int2 mesh_block_look(const MeshScene& s, int bx, int 
     return blk_walk(s.v, bx, by, bz);
 }
 
-// ---- the whole reading's resolution (DESIGN.md §Mesh extraction, the whole map), written once ----
-// Entry ei with the block pointer ptr, by the table: a block and no store, or a store left behind by a
-// finished merge (state 2: k_swap_in never clears the flag) -> the active block; a block and a store not
-// yet merged -> both; swapped out with a store -> the store; anything else is missing.
-__device__ __forceinline__ MeshBlk mesh_resolve_entry(const MeshSceneWhole& s, int ei, int ptr)
+// ---- the whole reading's resolution (DESIGN.md §Mesh extraction, the whole map) ----
+// The rule itself -- what an entry holds across the two tiers (tier_resolve_entry, tier_entry_resolves) and the
+// walk over both (tier_walk) -- is tf_tier.h's, shared with the free views' whole reading.
+// mesh_block_look for the whole reading: tf_tier.h's look-up (the grid, then the walk over both tiers -- inside the
+// grid too), behind mesh_block_look's check of the short range for a block outside the grid
+__device__ __forceinline__ TierBlk mesh_block_resolve(const MeshSceneWhole& s, int bx, int by, int bz)
 {
-    const bool stored = s.flags[ei] != 0;
-    MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE, -1 };
-    if (ptr >= 0) {
-        d.act = ptr * TF_BLK3;
-        d.ent = ei;
-        if (stored && s.state[ei] != 2) d.sto = ei * TF_BLK3;
-    } else if (ptr == -1 && stored) {
-        d.sto = ei * TF_BLK3;
-        d.ent = ei;
-    }
-    return d;
-}
-
-// does entry idx hold voxel data in either tier
-__device__ __forceinline__ bool mesh_entry_resolves(const MeshSceneWhole& s, int idx)
-{
-    const int ptr = s.v.hash[idx].ptr;
-    return ptr >= 0 || (ptr == -1 && s.flags[idx] != 0);
-}
-
-// blk_walk over both tiers: the first entry at the block that resolves (ptr >= 0, or swapped out -- ptr -1 --
-// with stored data), or -1
-__device__ __forceinline__ int mesh_walk_whole(const MeshSceneWhole& s, int bx, int by, int bz)
-{
-    int hi = tf_hash_index(bx, by, bz, s.v.mask);
-    while (true) {
-        const TfHashEntry e = s.v.hash[hi];
-        if (e.x == (short)bx && e.y == (short)by && e.z == (short)bz && (e.ptr >= 0 || (e.ptr == -1 && s.flags[hi] != 0))) return hi;
-        if (e.offset < 1) return -1;
-        hi = s.v.n_buckets + e.offset - 1;
-    }
-}
-
-// mesh_block_look for the whole reading.  The block grid first: a hit is a block in the VBA, whose entry's
-// flag and state say whether a merge is pending.  A miss inside the grid is not the end -- swap-out clears
-// the cell, so a stored block is never in the grid -- and takes the hash walk, as a block outside the grid does.
-__device__ __forceinline__ MeshBlk mesh_block_resolve(const MeshSceneWhole& s, int bx, int by, int bz)
-{
-    const MeshBlk none = { TF_VOFF_NONE, TFM_STO_NONE, -1 };
-    if (tf_grid_in(bx, by, bz)) {
-        const int2 b = s.v.grid[tf_grid_cell(bx, by, bz)];
-        if (b.x >= 0) return mesh_resolve_entry(s, b.x, b.y >> 9);
-    } else if (bx > 32767 || by > 32767 || bz > 32767 || bx < -32768 || by < -32768 || bz < -32768) {
+    if (!tf_grid_in(bx, by, bz) && (bx > 32767 || by > 32767 || bz > 32767 || bx < -32768 || by < -32768 || bz < -32768)) {
+        const TierBlk none = { TF_VOFF_NONE, TIER_STO_NONE, -1 };
         return none;
     }
-    const int hi = mesh_walk_whole(s, bx, by, bz);
-    return hi < 0 ? none : mesh_resolve_entry(s, hi, s.v.hash[hi].ptr);
+    return tier_block_find(s, bx, by, bz);
 }
 
 // one voxel of a resolved block as the tiles hold it (sdf | w << 16): the active voxel (the guard's
@@ -191,7 +142,7 @@ __device__ __forceinline__ void mesh_stage(const Scene& s, int ei, const TfHashE
     int2 b = make_int2(-1, TF_VOFF_NONE);
     if (t < 8) {
         if constexpr (Scene::whole) {
-            const MeshBlk d = t == 0 ? mesh_resolve_entry(s, ei, e.ptr) : mesh_block_resolve(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
+            const TierBlk d = t == 0 ? tier_resolve_entry(s, ei, e.ptr) : mesh_block_resolve(s, e.x + (t & 1), e.y + (t >> 1 & 1), e.z + (t >> 2));
             b = make_int2(d.ent, d.act);
             nvoff[8 + t] = d.sto;
         } else {
@@ -257,8 +208,8 @@ __device__ __forceinline__ void mesh_stage_attr(const Scene& s, const unsigned* 
         const int down = (ox < 0) + (oy < 0) + (oz < 0);
         int voff = TF_VOFF_NONE;
         if constexpr (Scene::whole) {
-            MeshBlk d = { TF_VOFF_NONE, TFM_STO_NONE, -1 };
-            if (t == 13) d = mesh_resolve_entry(s, ei, e.ptr);
+            TierBlk d = { TF_VOFF_NONE, TIER_STO_NONE, -1 };
+            if (t == 13) d = tier_resolve_entry(s, ei, e.ptr);
             else if (down <= (NORMALS ? 1 : 0)) d = mesh_block_resolve(s, e.x + ox, e.y + oy, e.z + oz);
             voff = d.act;
             nvoff[27 + t] = d.sto;

@@ -1,5 +1,7 @@
 // tf_render.hip -- raycasting side of the hot path for gfx950.
 //
+//   k_raycast_whole, k_render_type<T, SceneViewWhole> : castRay<false> and the pixel stages of a free view's whole
+//                   reading -- every voxel read resolved over the VBA and the GlobalCache (tf_tier.h)
 //   k_raycast     : genericRaycast_device / castRay (VisualisationHelper.hpp:33-46,
 //                   VisualisationEngine_Shared.hpp:99-172), incl. the IndexCache behaviour
 //                   that decides which entries castRay<true> marks visible
@@ -12,6 +14,9 @@
 #include "tf_internal.h"
 #include "tf_preproc.h"
 #include "tf_reset.h"
+#include "tf_tier.h"
+
+#include <type_traits>
 
 // SceneView, blk_walk (the hash walk for a block outside the block grid): tf_internal.h, shared with tf_mesh.hip
 
@@ -232,8 +237,9 @@ __device__ __forceinline__ float interp_sdf_conf(const Corners& q, float* conf)
 }
 
 
-struct RayArgs {
-    SceneView s;
+template <class S>
+struct RayArgsT {
+    S s;
     const float2* range;
     float4* out;
     unsigned char* visType;      // non-null: castRay<true>
@@ -242,6 +248,7 @@ struct RayArgs {
     float invfx, invfy, ncx, ncy; // InvertProjectionParams (VisualisationEngine_Shared.hpp:28-31)
     float oneOverVoxelSize, mu;
 };
+typedef RayArgsT<SceneView> RayArgs;
 
 // castRay's state (VisualisationEngine_Shared.hpp:99-172): ray_init, the march loop
 // (ray_march_lite), ray_refine at the surface.
@@ -253,7 +260,8 @@ struct Ray {
 };
 
 // vf: the range image at the ray's /8 pixel (renderingRangeImage[locId2], :104-106)
-__device__ __forceinline__ void ray_init(const RayArgs& a, const float* invM, int x, int y, float2 vf, Ray& R)
+template <class A>
+__device__ __forceinline__ void ray_init(const A& a, const float* invM, int x, int y, float2 vf, Ray& R)
 {
     float r[3], ps[3], pe[3];
     float pz = vf.x;
@@ -279,7 +287,8 @@ __device__ __forceinline__ void ray_init(const RayArgs& a, const float* invM, in
 
 // castRay's refinement at the surface: the step back onto it; true when there is one (then the
 // confidence read at the new pt completes it, ray_march_lite)
-__device__ __forceinline__ bool ray_refine(const RayArgs& a, Ray& R)
+template <class A>
+__device__ __forceinline__ bool ray_refine(const A& a, Ray& R)
 {
     if (!(R.sdfValue <= 0.0f)) return false;
     const float stepLength = R.sdfValue * (a.mu * a.oneOverVoxelSize);
@@ -309,6 +318,175 @@ __device__ __forceinline__ int2 blk_one(const SceneView& s, int bx, int by, int 
         if (!in) g = blk_walk(s, bx, by, bz);
     }
     return g;
+}
+
+// what the march asks of blk_one's answer, whatever the scene's reading
+__device__ __forceinline__ bool blk_found(int2 g) { return g.y >= 0; }
+__device__ __forceinline__ int blk_ent(int2 g) { return g.x; }
+__device__ __forceinline__ unsigned vox_blk(const SceneView& s, int2 g, int lin_g) { return vox_at(s, g.y, lin_g); }
+
+// ---------------------------------------------------------------------------------------
+// The whole reading (a free view with TF_VIEW_WHOLE on a swapping context): every
+// voxel read goes through the resolution of its block over the VBA and the GlobalCache.  The rule
+// is tf_tier.h's (the mesher's); what stands here is the raycasting side's shape of it.  A lookup
+// yields a TierBlk: the entry, the active offset or none, the store offset or none.
+//  - a grid hit is a block in the VBA: its entry's flag and state say whether a merge is pending;
+//  - a grid miss inside the grid is not the end -- swap-out clears the cell, so a stored block is
+//    never in the grid -- and takes the walk over both tiers, as a block outside the grid does
+//    (blk_walk's range: block coordinates are compared as shorts, as on the resident path);
+//  - a stored voxel is word sto + lin of the store: a scaled 32-bit index (tf_create bounds the
+//    table so that it fits), not ld_off's byte offset, which would pass 2^32.
+// Branches are the wave's: a wave whose blocks are all active-only issues the resident loads plus
+// the flag bytes; only one that meets a stored or pending block loads from the store, and a
+// pending voxel costs both loads and sw_combine.
+// ---------------------------------------------------------------------------------------
+struct SceneViewWhole {
+    SceneView v;
+    int maxW;                    // CombineVoxelInformation's clamp (tf_params::maxW)
+    const unsigned char* state;  // HashSwapState::state per entry
+    const unsigned char* flags;  // hasStoredData per entry
+    const TfVoxel* store;        // storedVoxelBlocks: 512 voxels per entry
+};
+
+// blk_one over both tiers: the cell's load stays unbranched; the flag bytes of the hits and the walk of
+// the misses are taken by the wave together
+__device__ __forceinline__ TierBlk blk_one(const SceneViewWhole& s, int bx, int by, int bz)
+{
+    const bool in = tf_grid_in(bx, by, bz);
+    const unsigned off = in ? (unsigned)tf_grid_cell(bx, by, bz) * 8u : 0u;
+    const int2 g = ld_off<int2>(s.v.grid, off);
+    const bool hit = in && g.x >= 0;
+    TierBlk d = { TF_VOFF_NONE, TIER_STO_NONE, -1 };
+    if (wave_any(hit)) {
+        if (hit) d = tier_resolve_entry(s, g.x, g.y >> 9);
+    }
+    if (wave_any(!hit)) {
+        if (!hit) {
+            const int hi = tier_walk(s, bx, by, bz);
+            if (hi >= 0) d = tier_resolve_entry(s, hi, s.v.hash[hi].ptr);
+        }
+    }
+    return d;
+}
+__device__ __forceinline__ bool blk_found(const TierBlk& d) { return d.ent >= 0; }
+__device__ __forceinline__ int blk_ent(const TierBlk& d) { return d.ent; }
+
+// the stored voxel of a block with stored data (sto >= 0) merged into the active word a: the stored one as it
+// is where there is no active block, else CombineVoxelInformation(stored, active)
+__device__ __forceinline__ unsigned vox_merge(const SceneViewWhole& s, unsigned a, int act, int sto, int lin_g)
+{
+    const unsigned st = reinterpret_cast<const unsigned*>(s.store)[(unsigned)(sto + lin_g - TF_BLK3)];
+    return act == TF_VOFF_NONE ? st : sw_combine(st, a, s.maxW);
+}
+// vox_at over both tiers: the active load as the resident one (the guard's (32767, 0) where there is no
+// active block), the store's behind the wave's branch
+__device__ __forceinline__ unsigned vox_at(const SceneViewWhole& s, int act, int sto, int lin_g)
+{
+    unsigned a = vox_at(s.v, act, lin_g);
+    if (wave_any(sto >= 0)) {
+        if (sto >= 0) a = vox_merge(s, a, act, sto, lin_g);
+    }
+    return a;
+}
+__device__ __forceinline__ unsigned vox_blk(const SceneViewWhole& s, const TierBlk& d, int lin_g) { return vox_at(s, d.act, d.sto, lin_g); }
+
+// the 2x2x2 block set {X} x {Y} x {Z} (o, in: blk_offsets8's): per corner the active and the store offset.
+// A wave whose corners are all grid hits loads the eight cells together, as the resident path does, and
+// then their flag bytes; any other wave looks its distinct blocks up one after the other (one rolled loop
+// with a single walk in it, as blk_lookup_slow; a corner whose block is a lower corner's copies it).
+__device__ __forceinline__ void wblk_find8(const SceneViewWhole& s, const int (&X)[2], const int (&Y)[2], const int (&Z)[2],
+                                           const unsigned (&o)[8], bool in, int (&act)[8], int (&sto)[8])
+{
+    int2 g[8];
+    bool fast = in;
+    if (!wave_any(!in)) {
+        blk_load8(s.v, o, g);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) fast = fast && g[c].x >= 0;
+    }
+    if (!wave_any(!fast)) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const TierBlk d = tier_resolve_entry(s, g[c].x, g[c].y >> 9);
+            act[c] = d.act; sto[c] = d.sto;
+        }
+        return;
+    }
+    int x0 = X[0], x1 = X[1], y0 = Y[0], y1 = Y[1], z0 = Z[0], z1 = Z[1];
+    // (kept in VGPRs: left alone the optimiser turns the selects below into a private array in scratch)
+    asm volatile("" : "+v"(x0), "+v"(x1), "+v"(y0), "+v"(y1), "+v"(z0), "+v"(z1));
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { act[c] = TF_VOFF_NONE; sto[c] = TIER_STO_NONE; }
+#pragma unroll 1
+    for (int c = 0; c < 8; ++c) {
+        const bool dup = ((c & 1) && x1 == x0) || ((c & 2) && y1 == y0) || ((c & 4) && z1 == z0);
+        TierBlk d = { TF_VOFF_NONE, TIER_STO_NONE, -1 };
+        if (!dup) d = tier_block_find(s, (c & 1) ? x1 : x0, (c & 2) ? y1 : y0, (c & 4) ? z1 : z0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (k == c) { act[k] = d.act; sto[k] = d.sto; }
+    }
+#pragma unroll
+    for (int c = 1; c < 8; ++c) {
+        // (ascending: the lower corner already holds its block; constant indices, selects and no indexed array)
+        if ((c & 1) && x1 == x0) { act[c] = act[c & 6]; sto[c] = sto[c & 6]; }
+        else if ((c & 2) && y1 == y0) { act[c] = act[c & 5]; sto[c] = sto[c & 5]; }
+        else if ((c & 4) && z1 == z0) { act[c] = act[c & 3]; sto[c] = sto[c & 3]; }
+    }
+}
+
+// the eight voxel words of a corner set: the active loads together, then -- for a wave that holds a stored
+// or pending corner -- the store's
+__device__ __forceinline__ void wvox8(const SceneViewWhole& s, const int (&act)[8], const int (&sto)[8], const int (&lin)[8],
+                                      unsigned (&raw)[8])
+{
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { raw[c] = vox_at(s.v, act[c], lin[c]); any = any || sto[c] >= 0; }
+    if (wave_any(any)) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            if (sto[c] >= 0) raw[c] = vox_merge(s, raw[c], act[c], sto[c], lin[c]);
+    }
+}
+
+// interp_at over both tiers: the same corners, IndexCache update and arithmetic; a corner's block exists when
+// it resolves in either tier
+__device__ __forceinline__ float interp_at(const SceneViewWhole& s, const float* pt, RCache* k, float* conf)
+{
+    Corners q;
+    unsigned o[8];
+    const bool in = corners_prep(pt, q, o);
+    const int X[2] = { q.bx, q.bx + q.sx }, Y[2] = { q.by, q.by + q.sy }, Z[2] = { q.bz, q.bz + q.sz };
+    int sto[8];
+    wblk_find8(s, X, Y, Z, o, in, q.voff, sto);
+    q.valid = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) q.valid |= ((q.voff[c] >= 0 || sto[c] >= 0) ? 1u : 0u) << c;
+    if (k) corners_cache(q, k);
+    const int lx[2] = { lin_x(q.fx), lin_x(q.fx + 1) }, ly[2] = { lin_y(q.fy), lin_y(q.fy + 1) };
+    const int lz[2] = { lin_zg(q.fz), lin_zg(q.fz + 1) };
+    int lin[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) lin[c] = lx[c & 1] + ly[(c >> 1) & 1] + lz[c >> 2];
+    wvox8(s, q.voff, sto, lin, q.raw);
+    return conf ? interp_sdf_conf(q, conf) : interp_sdf(q);
+}
+
+// the gradient's 2x2x2 blocks: the thread's LDS slot holds the active offsets, then the store offsets
+#define VTAB_STRIDE_WHOLE 17
+__device__ __forceinline__ void normal_blocks(const SceneViewWhole& s, const int (&X)[2], const int (&Y)[2], const int (&Z)[2], int* vtab)
+{
+    unsigned o[8];
+    int act[8], sto[8];
+    const bool in = blk_offsets8(X, Y, Z, o);
+    wblk_find8(s, X, Y, Z, o, in, act, sto);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { vtab[c] = act[c]; vtab[8 + c] = sto[c]; }
+}
+__device__ __forceinline__ unsigned vox_tab(const SceneViewWhole& s, const int* vtab, int i, int lin_g)
+{
+    return vox_at(s, vtab[i], vtab[8 + i], lin_g);
 }
 
 // readFromSDF_float_interpolated at pt (RepresentationAccess.hpp:137-162) with the IndexCache
@@ -348,8 +526,8 @@ __device__ __forceinline__ float interp_at(const SceneView& s, const float* pt, 
 // round trips more per band step, and holds far fewer registers across the loop (the ray state
 // only): more waves resident to hide the dependent loads.  Values, visibility marks and the
 // IndexCache follow castRay's serial reads exactly (VisualisationEngine_Shared.hpp:117-160).
-template <bool MARK>
-__device__ __forceinline__ float ray_march_lite(const RayArgs& a, const float* invM, int x, int y, float2 vf, float* pt)
+template <bool MARK, class A>
+__device__ __forceinline__ float ray_march_lite(const A& a, const float* invM, int x, int y, float2 vf, float* pt)
 {
     Ray R;
     ray_init(a, invM, x, y, vf, R);
@@ -360,19 +538,19 @@ __device__ __forceinline__ float ray_march_lite(const RayArgs& a, const float* i
     while (R.active) {
         const int rx = tf_round(R.pt[0]), ry = tf_round(R.pt[1]), rz = tf_round(R.pt[2]);
         const int bx = vblk(rx), by = vblk(ry), bz = vblk(rz);
-        const int2 g = blk_one(a.s, bx, by, bz);
-        const bool found = g.y >= 0;
+        const auto g = blk_one(a.s, bx, by, bz);
+        const bool found = blk_found(g);
         int vmIndex = 0;
         if (found) {
             const bool hit = bx == R.k.bx && by == R.k.by && bz == R.k.bz;
-            vmIndex = hit ? 1 : g.x + 1;
+            vmIndex = hit ? 1 : blk_ent(g) + 1;
             R.k.bx = bx; R.k.by = by; R.k.bz = bz;
         }
 #ifdef TF_RAY_STATS
         if (found) ++n_found; else ++n_free;
 #endif
         unsigned raw = 0;
-        if (wave_any(found)) raw = vox_at(a.s, g.y, lin_x(rx) + lin_y(ry) + lin_zg(rz));
+        if (wave_any(found)) raw = vox_blk(a.s, g, lin_x(rx) + lin_y(ry) + lin_zg(rz));
         // a missing block reads Voxel_s(): 32767 / 32767 = 1
         float sdfValue = found ? tf_short_to_float((short)(raw & 0xffffu)) : 1.0f;
 #ifdef TF_RAY_STATS
@@ -417,8 +595,8 @@ __device__ __forceinline__ float ray_march_lite(const RayArgs& a, const float* i
     return w;
 }
 
-template <bool MARK>
-__device__ __forceinline__ float ray_march(const RayArgs& a, const float* invM, int x, int y, float2 vf, float* pt)
+template <bool MARK, class A>
+__device__ __forceinline__ float ray_march(const A& a, const float* invM, int x, int y, float2 vf, float* pt)
 {
     return ray_march_lite<MARK>(a, invM, x, y, vf, pt);
 }
@@ -486,9 +664,65 @@ __device__ void sdf_normal(const SceneView& s, const float* pt, float* ret, int*
 #undef RV
 }
 
+// ... under the whole reading: the same reads and arithmetic over normal_blocks' 16-entry slot and vox_tab.  (A copy,
+// not a template over both scenes: with sdf_normal as a template the resident k_render_type kernels came out of the
+// register allocator with other VGPR counts, and the resident path must compile to what it was.)
+__device__ void sdf_normal(const SceneViewWhole& s, const float* pt, float* ret, int* vtab)
+{
+    float ffx = floorf(pt[0]), ffy = floorf(pt[1]), ffz = floorf(pt[2]);
+    int px = (int)ffx, py = (int)ffy, pz = (int)ffz;
+    float cx = pt[0] - ffx, cy = pt[1] - ffy, cz = pt[2] - ffz;
+    float nx = 1.0f - cx, ny = 1.0f - cy, nz = 1.0f - cz;
+    const int bx = vblk(px - 1), by = vblk(py - 1), bz = vblk(pz - 1);
+    const int sx = vblk(px + 2) - bx, sy = vblk(py + 2) - by, sz = vblk(pz + 2) - bz;
+    const int X[2] = { bx, bx + sx }, Y[2] = { by, by + sy }, Z[2] = { bz, bz + sz };
+    normal_blocks(s, X, Y, Z, vtab);
+    int tx[4], ty[4], tz[4], lx[4], ly[4], lz[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        tx[d] = vblk(px - 1 + d) - bx; ty[d] = 2 * (vblk(py - 1 + d) - by); tz[d] = 4 * (vblk(pz - 1 + d) - bz);
+        lx[d] = lin_x(px - 1 + d); ly[d] = lin_y(py - 1 + d); lz[d] = lin_zg(pz - 1 + d);
+    }
+#define RVW(dx, dy, dz) raw_sdf(vox_tab(s, vtab, tx[(dx) + 1] + ty[(dy) + 1] + tz[(dz) + 1], \
+                                       lx[(dx) + 1] + ly[(dy) + 1] + lz[(dz) + 1]))
+    float f0 = RVW(0, 0, 0), f1 = RVW(1, 0, 0), f2 = RVW(0, 1, 0), f3 = RVW(1, 1, 0);
+    float b0 = RVW(0, 0, 1), b1 = RVW(1, 0, 1), b2 = RVW(0, 1, 1), b3 = RVW(1, 1, 1);
+    float t0, t1, t2, t3, p1, p2, v1;
+    p1 = f0 * ny * nz + f2 * cy * nz + b0 * ny * cz + b2 * cy * cz;
+    t0 = RVW(-1, 0, 0); t1 = RVW(-1, 1, 0); t2 = RVW(-1, 0, 1); t3 = RVW(-1, 1, 1);
+    p2 = t0 * ny * nz + t1 * cy * nz + t2 * ny * cz + t3 * cy * cz;
+    v1 = p1 * cx + p2 * nx;
+    p1 = f1 * ny * nz + f3 * cy * nz + b1 * ny * cz + b3 * cy * cz;
+    t0 = RVW(2, 0, 0); t1 = RVW(2, 1, 0); t2 = RVW(2, 0, 1); t3 = RVW(2, 1, 1);
+    p2 = t0 * ny * nz + t1 * cy * nz + t2 * ny * cz + t3 * cy * cz;
+    ret[0] = tf_div32767(p1 * nx + p2 * cx - v1);
+    // the y and z reads after the x derivative: 16 + 16 loads in flight instead of 32, so the
+    // raycast kernels that end in this gradient keep their register budget (one more round trip
+    // per pixel, once, against the march's many)
+    __builtin_amdgcn_sched_barrier(0);
+    p1 = f0 * nx * nz + f1 * cx * nz + b0 * nx * cz + b1 * cx * cz;
+    t0 = RVW(0, -1, 0); t1 = RVW(1, -1, 0); t2 = RVW(0, -1, 1); t3 = RVW(1, -1, 1);
+    p2 = t0 * nx * nz + t1 * cx * nz + t2 * nx * cz + t3 * cx * cz;
+    v1 = p1 * cy + p2 * ny;
+    p1 = f2 * nx * nz + f3 * cx * nz + b2 * nx * cz + b3 * cx * cz;
+    t0 = RVW(0, 2, 0); t1 = RVW(1, 2, 0); t2 = RVW(0, 2, 1); t3 = RVW(1, 2, 1);
+    p2 = t0 * nx * nz + t1 * cx * nz + t2 * nx * cz + t3 * cx * cz;
+    ret[1] = tf_div32767(p1 * ny + p2 * cy - v1);
+    p1 = f0 * nx * ny + f1 * cx * ny + f2 * nx * cy + f3 * cx * cy;
+    t0 = RVW(0, 0, -1); t1 = RVW(1, 0, -1); t2 = RVW(0, 1, -1); t3 = RVW(1, 1, -1);
+    p2 = t0 * nx * ny + t1 * cx * ny + t2 * nx * cy + t3 * cx * cy;
+    v1 = p1 * cz + p2 * nz;
+    p1 = b0 * nx * ny + b1 * cx * ny + b2 * nx * cy + b3 * cx * cy;
+    t0 = RVW(0, 0, 2); t1 = RVW(1, 0, 2); t2 = RVW(0, 1, 2); t3 = RVW(1, 1, 2);
+    p2 = t0 * nx * ny + t1 * cx * ny + t2 * nx * cy + t3 * cx * cy;
+    ret[2] = tf_div32767(p1 * nz + p2 * cz - v1);
+#undef RVW
+}
+
 // computeNormalAndAngle<TVoxel,TIndex> (VisualisationEngine_Shared.hpp:189-203): the SDF-gradient
 // normal at pt, normalised, and its angle to the light; false when the angle is not positive
-__device__ __forceinline__ bool sdf_normal_angle(const SceneView& s, const float* pt, float lx, float ly, float lz,
+template <class S>
+__device__ __forceinline__ bool sdf_normal_angle(const S& s, const float* pt, float lx, float ly, float lz,
                                                  float* nn, float* angle, int* vtab)
 {
     sdf_normal(s, pt, nn, vtab);
@@ -501,7 +735,8 @@ __device__ __forceinline__ bool sdf_normal_angle(const SceneView& s, const float
 // drawPixelGrey (VisualisationEngine_Shared.hpp:272-276)
 __device__ __forceinline__ unsigned char grey_of(float angle) { return (unsigned char)((0.8f * angle + 0.2f) * 255.0f); }
 
-__device__ __forceinline__ unsigned char grey_pixel(const SceneView& s, const float* pt, float lx, float ly, float lz,
+template <class S>
+__device__ __forceinline__ unsigned char grey_pixel(const S& s, const float* pt, float lx, float ly, float lz,
                                                     int* vtab)
 {
     float nn[3], angle;
@@ -521,8 +756,8 @@ __device__ __forceinline__ int xcd_tile(int bid, int n)
 // vtab: the caller's LDS for MODE 2's gradient (256 * VTAB_STRIDE ints).  rng (the frame kernel's
 // CreateICPMaps rays with CreateExpectedDepths' fill fused in): the tile's four /8 range pixels,
 // computed by the caller; else the range image is read.
-template <int MODE, bool RNG_LDS = false>
-__device__ __forceinline__ void raycast_tile(const RayArgs& a, const TfDevState* __restrict__ st, int tile,
+template <int MODE, bool RNG_LDS = false, class A = RayArgs>
+__device__ __forceinline__ void raycast_tile(const A& a, const TfDevState* __restrict__ st, int tile,
                                              int tiles_x, int* vtab, const float2* rng = nullptr)
 {
     const int tx = tile % tiles_x, ty = tile / tiles_x;
@@ -567,10 +802,36 @@ k_raycast(RayArgs a, const TfDevState* __restrict__ st, int tiles_x, int n_tiles
     raycast_tile<MODE>(a, st, tile, tiles_x, nullptr);
 }
 
-// the scene is the context's; the range image, the output, the size and the intrinsics the render state's
-static void ray_args(tf_ctx* c, const TfTarget& t, RayArgs& a)
+// castRay<false> under the whole reading (a free view's, tf_view.hip): the same tiles over both tiers
+__global__ void __launch_bounds__(256)
+k_raycast_whole(RayArgsT<SceneViewWhole> a, const TfDevState* __restrict__ st, int tiles_x, int n_tiles)
 {
-    a.s.hash = c->hash; a.s.vba = c->vba_guard; a.s.grid = c->bgrid; a.s.mask = (unsigned)(c->p.n_buckets - 1); a.s.n_buckets = c->p.n_buckets;
+    if (!raycast_go<0>(st)) return;
+    const int tile = xcd_tile(blockIdx.x, n_tiles);
+    if (tile < 0) return;
+    raycast_tile<0>(a, st, tile, tiles_x, nullptr);
+}
+
+static SceneView scene_view(const tf_ctx* c)
+{
+    SceneView s; s.hash = c->hash; s.vba = c->vba_guard; s.grid = c->bgrid; s.mask = (unsigned)(c->p.n_buckets - 1); s.n_buckets = c->p.n_buckets;
+    return s;
+}
+// ... of a swapping context (the others have no GlobalCache: their whole reading is the resident one)
+static SceneViewWhole scene_view_whole(const tf_ctx* c)
+{
+    SceneViewWhole s;
+    s.v = scene_view(c); s.maxW = c->p.maxW;
+    s.state = c->swapState; s.flags = c->swapFlags; s.store = c->swapStore;
+    return s;
+}
+static bool target_whole(const tf_ctx* c, const TfTarget& t) { return t.whole && c->p.use_swapping; }
+
+// the scene is the context's; the range image, the output, the size and the intrinsics the render state's
+template <class S>
+static void ray_args(tf_ctx* c, const TfTarget& t, const S& scene, RayArgsT<S>& a)
+{
+    a.s = scene;
     a.range = (const float2*)t.range; a.out = (float4*)t.raycast;
     a.visType = nullptr;
     a.grey = nullptr;
@@ -578,15 +839,23 @@ static void ray_args(tf_ctx* c, const TfTarget& t, RayArgs& a)
     a.invfx = 1.0f / t.fx; a.invfy = 1.0f / t.fy; a.ncx = -t.cx; a.ncy = -t.cy;
     a.oneOverVoxelSize = 1.0f / c->p.voxelSize; a.mu = c->p.mu;
 }
+static void ray_args(tf_ctx* c, const TfTarget& t, RayArgs& a) { ray_args(c, t, scene_view(c), a); }
 static void ray_args(tf_ctx* c, RayArgs& a) { ray_args(c, tf_ctx_target(c), a); }
 
 hipError_t tfk_raycast(tf_ctx* c, const TfTarget& t, unsigned char* visType)
 {
+    const int tx = (t.W + 15) / 16, ty = (t.H + 15) / 16, n = tx * ty;
+    const dim3 grid((n + 7) / 8 * 8);
+    if (target_whole(c, t)) {
+        if (visType) return hipErrorInvalidValue;            // castRay<true> marks the tracker's list: resident only
+        RayArgsT<SceneViewWhole> w;
+        ray_args(c, t, scene_view_whole(c), w);
+        hipLaunchKernelGGL(k_raycast_whole, grid, dim3(256), 0, c->stream, w, t.st, tx, n);
+        return hipGetLastError();
+    }
     RayArgs a;
     ray_args(c, t, a);
     a.visType = visType;
-    const int tx = (t.W + 15) / 16, ty = (t.H + 15) / 16, n = tx * ty;
-    const dim3 grid((n + 7) / 8 * 8);
     if (!visType) hipLaunchKernelGGL(k_raycast<0>, grid, dim3(256), 0, c->stream, a, t.st, tx, n);
     else hipLaunchKernelGGL(k_raycast<1>, grid, dim3(256), 0, c->stream, a, t.st, tx, n);
     return hipGetLastError();
@@ -689,12 +958,17 @@ __device__ __forceinline__ uchar4 colour_at(const SceneView& s, const unsigned* 
                        (unsigned char)((ret[2] / 255.0f) * 255.0f), 255);
 }
 
-template <int TYPE>
+// S: the scene's reading -- SceneView, or SceneViewWhole for the types that read the SDF (image normals read the
+// raycast result alone, and a swapping scene has no colour plane)
+template <int TYPE, class S>
 __global__ void __launch_bounds__(256)
-k_render_type(SceneView s, const float4* __restrict__ ray, int W, int H, float voxelSize,
+k_render_type(S s, const float4* __restrict__ ray, int W, int H, float voxelSize,
               const TfDevState* __restrict__ st, uchar4* __restrict__ out, const unsigned* __restrict__ rgb_guard)
 {
-    __shared__ int vtab[256 * VTAB_STRIDE];
+    constexpr bool WHOLE = std::is_same<S, SceneViewWhole>::value;
+    static_assert(!WHOLE || (TYPE != TF_RENDER_COLOUR_FROM_VOLUME && TYPE != TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS), "resident kernels");
+    constexpr int VSTRIDE = WHOLE ? VTAB_STRIDE_WHOLE : VTAB_STRIDE;
+    __shared__ int vtab[256 * VSTRIDE];
     if (st->abort || st->mode == 0) return;          // ICP failed, or frame 0 (no rendering)
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= W * H) return;
@@ -706,7 +980,8 @@ k_render_type(SceneView s, const float4* __restrict__ ray, int W, int H, float v
     float nn[3], angle = 0.f;
     if (TYPE == TF_RENDER_COLOUR_FROM_VOLUME) {                      // renderColour_device / processPixelColour
         const float pt[3] = { p.x, p.y, p.z };
-        out[i] = found ? colour_at(s, rgb_guard, pt) : make_uchar4(0, 0, 0, 0);
+        if constexpr (!WHOLE)
+            out[i] = found ? colour_at(s, rgb_guard, pt) : make_uchar4(0, 0, 0, 0);
         return;
     }
     if (TYPE == TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS) {           // processPixelGrey_ImageNormals<true,false>
@@ -717,7 +992,7 @@ k_render_type(SceneView s, const float4* __restrict__ ray, int W, int H, float v
     }
     if (found) {
         const float pt[3] = { p.x, p.y, p.z };
-        found = sdf_normal_angle(s, pt, lx, ly, lz, nn, &angle, &vtab[threadIdx.x * VTAB_STRIDE]);
+        found = sdf_normal_angle(s, pt, lx, ly, lz, nn, &angle, &vtab[threadIdx.x * VSTRIDE]);
     }
     if (TYPE == TF_RENDER_COLOUR_FROM_NORMAL) {                      // processPixelNormal / drawPixelNormal
         if (found) {                                                 // r, g, b; alpha is left as it was (:305-310)
@@ -752,7 +1027,7 @@ hipError_t tfk_render_type(tf_ctx* c, int type) { return tfk_render_type(c, tf_c
 
 hipError_t tfk_render_type(tf_ctx* c, const TfTarget& t, int type)
 {
-    SceneView s; s.hash = c->hash; s.vba = c->vba_guard; s.grid = c->bgrid; s.mask = (unsigned)(c->p.n_buckets - 1); s.n_buckets = c->p.n_buckets;
+    const SceneView s = scene_view(c);
     const int n = t.W * t.H;
     const dim3 g((n + 255) / 256), b(256);
     const float4* ray = (const float4*)t.raycast;
@@ -760,17 +1035,31 @@ hipError_t tfk_render_type(tf_ctx* c, const TfTarget& t, int type)
     const unsigned* cg = c->vba_rgb_guard;
     // RENDER_COLOUR_FROM_VOLUME without colour information: greyscale (VisualisationEngine_CUDA.cu:251-252)
     if (type == TF_RENDER_COLOUR_FROM_VOLUME && !c->p.voxel_rgb) type = TF_RENDER_SHADED_GREYSCALE;
+    // the whole reading: the three types that read the SDF (image normals read the raycast result alone, and
+    // tf_create refuses colour with swapping)
+    if (target_whole(c, t) && type != TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS) {
+        const SceneViewWhole w = scene_view_whole(c);
+        switch (type) {
+        case TF_RENDER_COLOUR_FROM_NORMAL:
+            hipLaunchKernelGGL((k_render_type<TF_RENDER_COLOUR_FROM_NORMAL, SceneViewWhole>), g, b, 0, c->stream, w, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        case TF_RENDER_COLOUR_FROM_CONFIDENCE:
+            hipLaunchKernelGGL((k_render_type<TF_RENDER_COLOUR_FROM_CONFIDENCE, SceneViewWhole>), g, b, 0, c->stream, w, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        default:
+            hipLaunchKernelGGL((k_render_type<TF_RENDER_SHADED_GREYSCALE, SceneViewWhole>), g, b, 0, c->stream, w, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        }
+        return hipGetLastError();
+    }
     switch (type) {
     case TF_RENDER_COLOUR_FROM_VOLUME:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_VOLUME>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        hipLaunchKernelGGL((k_render_type<TF_RENDER_COLOUR_FROM_VOLUME, SceneView>), g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     case TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        hipLaunchKernelGGL((k_render_type<TF_RENDER_SHADED_GREYSCALE_IMAGENORMALS, SceneView>), g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     case TF_RENDER_COLOUR_FROM_NORMAL:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_NORMAL>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        hipLaunchKernelGGL((k_render_type<TF_RENDER_COLOUR_FROM_NORMAL, SceneView>), g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     case TF_RENDER_COLOUR_FROM_CONFIDENCE:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_COLOUR_FROM_CONFIDENCE>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        hipLaunchKernelGGL((k_render_type<TF_RENDER_COLOUR_FROM_CONFIDENCE, SceneView>), g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     default:
-        hipLaunchKernelGGL(k_render_type<TF_RENDER_SHADED_GREYSCALE>, g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
+        hipLaunchKernelGGL((k_render_type<TF_RENDER_SHADED_GREYSCALE, SceneView>), g, b, 0, c->stream, s, ray, t.W, t.H, vs, t.st, t.image, cg); break;
     }
     return hipGetLastError();
 }
@@ -1039,6 +1328,13 @@ k_ed_project(EdArgs a, const TfDevState* __restrict__ st)
     ed_project_block(a, st, blockIdx.x, gridDim.x);
 }
 
+// ... of a free view's whole list: an entry swapped out with stored data has a block to project (tf_ed.h)
+__global__ void __launch_bounds__(256)
+k_ed_project_whole(EdArgs a, const TfDevState* __restrict__ st)
+{
+    ed_project_block<-1>(a, st, blockIdx.x, gridDim.x);
+}
+
 // fillBlocks_device (VisualisationHelper.cu:105-121): per-pixel min/max of the block z-ranges.
 // The tile total is the sum of the chunk totals; past MAX_RENDERING_BLOCKS, blocks whose tiles do
 // not fit are dropped in visible-list order (the serial semantics of the reference's atomicAdd
@@ -1283,7 +1579,10 @@ hipError_t tfk_expected_depths(tf_ctx* c, const TfTarget& t, int project_done, i
     EdArgs a;
     ed_args(c, t, a);
     a.keep_bins = keep_bins;
-    if (!project_done) hipLaunchKernelGGL(k_ed_project, dim3(TF_ED_BLOCKS), dim3(256), 0, c->stream, a, t.st);
+    if (!project_done) {
+        if (target_whole(c, t)) hipLaunchKernelGGL(k_ed_project_whole, dim3(TF_ED_BLOCKS), dim3(256), 0, c->stream, a, t.st);
+        else hipLaunchKernelGGL(k_ed_project, dim3(TF_ED_BLOCKS), dim3(256), 0, c->stream, a, t.st);
+    }
     // one workgroup per LDS row (the atomic path grid-strides the same grid)
     tf_launch(c, k_ed_fill, dim3(a.nrows), dim3(ED_THREADS), 0, a, t.st);
     return hipGetLastError();

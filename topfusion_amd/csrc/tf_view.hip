@@ -21,6 +21,11 @@
 // the table's size.  No atomics.  Expected depths, the raycast, the pixel stages and renderICP are tf_render.hip's
 // kernels over the view's buffers (TfTarget) and the view's state block.
 //
+// A view has a reading (tf_set_view_reading, kept in its TfTarget): resident, the blocks in the VBA; or whole, both
+// tiers of a swapping context -- the scan then takes the entries that resolve in either tier (ViewScanT<true>, the
+// rule is tf_tier.h's), and tf_render.hip's kernels over both tiers are launched for the target (the
+// whole reading).  On a context without a GlobalCache the whole reading runs the resident kernels.
+//
 // No view call writes anything of the context's: not a TF_BUF_* buffer, not its device state, not its host
 // parameters (the call's intrinsics go into the view's TfTarget, not through an IntrScope), not the raycast pair's
 // tile costs.  Every call flushes a pending per-call frame first and runs on the context stream, after the caller's
@@ -29,6 +34,7 @@
 #include "tf_compact.h"
 #include "tf_env.h"
 #include "tf_pose.h"
+#include "tf_tier.h"
 #include "tf_vis.h"
 
 #include <limits.h>
@@ -43,12 +49,17 @@ struct tf_view {
     int4* grp;                       // the compaction's scratch: [2 * groups + 2] (tf_compact.h)
     unsigned long long* masks;       // per 64 entries the visible lanes (count pass -> emit pass): [4 * groups]
     float4* maps[2];                 // renderICP's points / normals, three levels each; from the first tf_view_icp_maps
+    // the reading (tf_set_view_reading) lives in t.whole: every stage takes it from the call's TfTarget
 };
 
 // ---- the scan ------------------------------------------------------------------------------------------
-struct ViewScanPass {
+// WHOLE: live = the entry resolves in either tier (tf_tier.h) -- one flag byte per entry more, fetched only where
+// ptr == -1; the ballots, the prefix and the emit pass are the same
+template <bool WHOLE>
+struct ViewScanT {
     struct Item {};
     const TfHashEntry* hash;
+    const unsigned char* flags;      // hasStoredData per entry (WHOLE)
     const TfDevState* st;            // the view's: M_alloc is the world -> camera matrix
     VisArgs v;
     unsigned long long* masks;
@@ -62,7 +73,7 @@ struct ViewScanPass {
             e.x = (short)(w.x & 0xffffu); e.y = (short)(w.x >> 16); e.z = (short)(w.y & 0xffffu); e.pad = 0;
             e.offset = (int)w.z; e.ptr = (int)w.w;
         }
-        const bool live = e.ptr >= 0;
+        const bool live = WHOLE ? tier_ptr_resolves(flags, i, e.ptr) : e.ptr >= 0;     // (past n: ptr -2)
         bool vis = false;
         if (__ballot(live) != 0ull) {          // (wave-uniform: an empty wave does no projection)
             if (live) vis = vis_block(e, st->M_alloc, v);
@@ -73,6 +84,8 @@ struct ViewScanPass {
     }
     __device__ __forceinline__ void emit(int, const Item&, unsigned, int, int, int) const {}
 };
+struct ViewScanPass : ViewScanT<false> {};
+struct ViewScanWholePass : ViewScanT<true> {};
 
 struct ViewEmitPass {
     struct Item {};
@@ -212,11 +225,12 @@ static tf_status view_begin(tf_view* v, const float* intr, const float* rt, int 
 
 // FindVisibleBlocks over the view's matrices: count, the capacity check on the host, emit.  TF_CAPACITY leaves
 // the list and the view's count as they were.
-static tf_status view_scan(tf_view* v, const TfTarget& t, int* n_visible)
+template <class Scan>
+static tf_status view_scan_as(tf_view* v, const TfTarget& t, int* n_visible)
 {
     tf_ctx* c = v->c;
-    ViewScanPass scan;
-    scan.hash = c->hash; scan.st = t.st; scan.masks = v->masks;
+    Scan scan;
+    scan.hash = c->hash; scan.flags = c->swapFlags; scan.st = t.st; scan.masks = v->masks;
     scan.v.fx = t.fx; scan.v.fy = t.fy; scan.v.cx = t.cx; scan.v.cy = t.cy;
     scan.v.factor = (float)TF_BLK * c->p.voxelSize;
     scan.v.W = t.W; scan.v.H = t.H;
@@ -234,6 +248,12 @@ static tf_status view_scan(tf_view* v, const TfTarget& t, int* n_visible)
     hipLaunchKernelGGL(k_view_set_n, dim3(1), dim3(1), 0, c->stream, t.st, totals);
     TF_CHECK(hipGetLastError());
     return TF_OK;
+}
+
+// the whole reading on a context without a GlobalCache is the resident one
+static tf_status view_scan(tf_view* v, const TfTarget& t, int* n_visible)
+{
+    return (t.whole && v->c->p.use_swapping) ? view_scan_as<ViewScanWholePass>(v, t, n_visible) : view_scan_as<ViewScanPass>(v, t, n_visible);
 }
 
 static bool type_ok(int type) { return type >= TF_RENDER_SHADED_GREYSCALE && type <= TF_RENDER_COLOUR_FROM_CONFIDENCE; }
@@ -363,6 +383,20 @@ extern "C" tf_status tf_view_stats(tf_view* v, int* n_visible, int* n_render_blo
     if (s != TF_OK) return s;
     if (n_visible) *n_visible = two[0];
     if (n_render_blocks) *n_render_blocks = two[1];
+    return TF_OK;
+}
+
+extern "C" tf_status tf_set_view_reading(tf_view* v, int reading)
+{
+    if (!v || (reading != TF_VIEW_RESIDENT && reading != TF_VIEW_WHOLE)) return TF_INVALID_ARG;
+    v->t.whole = reading == TF_VIEW_WHOLE;
+    return TF_OK;
+}
+
+extern "C" tf_status tf_get_view_reading(tf_view* v, int* reading)
+{
+    if (!v || !reading) return TF_INVALID_ARG;
+    *reading = v->t.whole ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT;
     return TF_OK;
 }
 

@@ -42,9 +42,11 @@ class View:
     """A free view of a TopFu's map (tf_view, include/tfusion_hip.h): its own size, visible list, range image,
     raycast result and image.  Rendering through it leaves the tracker's state and output untouched.  Poses are
     3x4 / 4x4 [R|t]: `c2w` camera -> world, `w2c` world -> camera; `intr` (fx, fy, cx, cy), None: the context's.
+    `whole` is the view's reading (tf_set_view_reading): False, the blocks in the VBA; True, on a swapping TopFu,
+    the blocks of the GlobalCache as well.
     Created by TopFu.view(); close() (or the with statement) releases it early, the TopFu's close() at the latest."""
 
-    def __init__(self, owner, cols, rows, vis_capacity=0, max_render_blocks=0):
+    def __init__(self, owner, cols, rows, vis_capacity=0, max_render_blocks=0, whole=False):
         self._owner = owner
         self._h = None
         vp = L.TfViewParams(int(cols), int(rows), int(vis_capacity), int(max_render_blocks))
@@ -56,6 +58,18 @@ class View:
         self.vis_capacity, self.max_render_blocks = vp.vis_capacity, vp.max_render_blocks
         self.needed = 0               # entries the last find_visible found (also when it raised TF_CAPACITY)
         owner._views.append(self)
+        if whole:
+            self.whole = True
+
+    @property
+    def whole(self):
+        r = ctypes.c_int(0)
+        L.check(L.load().tf_get_view_reading(self._handle(), ctypes.byref(r)), "tf_get_view_reading")
+        return r.value == L.TF_VIEW_WHOLE
+
+    @whole.setter
+    def whole(self, on):
+        L.check(L.load().tf_set_view_reading(self._handle(), L.TF_VIEW_WHOLE if on else L.TF_VIEW_RESIDENT), "tf_set_view_reading")
 
     def close(self):
         if self._h and self._owner._h:          # (a closed TopFu has released its views already)
@@ -185,10 +199,12 @@ class TopFu:
                 v._h = None
             self._views = []
 
-    def view(self, cols=None, rows=None, vis_capacity=0, max_render_blocks=0):
+    def view(self, cols=None, rows=None, vis_capacity=0, max_render_blocks=0, whole=False):
         """A free view of the map (View): cols x rows (None: the context's), a visible list of vis_capacity entries
-        (0: n_buckets + n_excess) and a tile cap of max_render_blocks (0: the context's)."""
-        return View(self, self.W if cols is None else cols, self.H if rows is None else rows, vis_capacity, max_render_blocks)
+        (0: n_buckets + n_excess) and a tile cap of max_render_blocks (0: the context's).  whole: the view reads the
+        GlobalCache of a swapping TopFu as well as its VBA (View.whole)."""
+        return View(self, self.W if cols is None else cols, self.H if rows is None else rows, vis_capacity, max_render_blocks,
+                    whole)
 
     def __del__(self):
         try:
