@@ -172,7 +172,8 @@ def test_sequence(oracle_mod, cols, rows, nframes, icp_schedule):
 
 def test_sequence_ed_atomic(oracle_mod, monkeypatch):
     """k_ed_fill's device-scope-atomic path (taken past ED_LDS_MAX_N visible entries, forced
-    here with a threshold of 0): the whole range image after every frame, spill area included."""
+    here with a threshold of 0): the whole range image after every frame, spill area included.
+    (Thresholds inside a list's length, and crossed between two calls: tests/test_gpu_ed_edges.py.)"""
     monkeypatch.setenv("TFUSION_ED_LDS_MAX_N", "0")
     g, o = make_pair(oracle_mod, 320, 240)
     _run_sequence(g, o, 320, 240, 16)
@@ -181,7 +182,8 @@ def test_sequence_ed_atomic(oracle_mod, monkeypatch):
 @pytest.mark.parametrize("lds_max_n", ["16384", "0"])
 def test_sequence_render_block_cap(oracle_mod, monkeypatch, lds_max_n):
     """MAX_RENDERING_BLOCKS engaged (a cap of 48 tiles): blocks whose tiles do not fit are
-    dropped in visible-list order (VisualisationHelper.cu:70-74), on both k_ed_fill paths."""
+    dropped in visible-list order (VisualisationHelper.cu:70-74), on both k_ed_fill paths.
+    (Caps that land exactly on a block, a chunk boundary and the last entry: tests/test_gpu_ed_edges.py.)"""
     monkeypatch.setenv("TFUSION_ED_LDS_MAX_N", lds_max_n)
     g, o = make_pair(oracle_mod, 320, 240, max_render_blocks=48)
     capped = _run_sequence(g, o, 320, 240, 8, need_spill=False)
