@@ -610,6 +610,8 @@ extern "C" tf_status tf_upload(tf_ctx* c, int which, int level, const void* host
     if (which == TF_BUF_HASH) TF_CHECK(tfk_grid_rebuild(c));       // keep the block grid exact
     if (which == TF_BUF_RANGE) TF_CHECK(ed_spill_all(c));          // next CreateExpectedDepths: whole buffer
     static const int one = 1;
+    if (which == TF_BUF_VISIBLE_TYPE || which == TF_BUF_VISIBLE_IDS)   // types 3 off the list (tf_vis.h)
+        TF_CHECK(hipMemcpyAsync((char*)c->st + offsetof(TfDevState, vis_stale), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (which == TF_BUF_HASH || which == TF_BUF_VBA || which == TF_BUF_VBA_RGB || which == TF_BUF_ALLOC_LIST ||
         which == TF_BUF_EXCESS_LIST)                               // next reset (in-frame ones too): full clear
         TF_CHECK(hipMemcpyAsync((char*)c->st + offsetof(TfDevState, scene_external), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -633,6 +635,7 @@ extern "C" tf_status tf_set_counters(tf_ctx* c, int lastFreeBlockId, int lastFre
     c->st_host->lastFreeBlockId = lastFreeBlockId;
     c->st_host->lastFreeExcessListId = lastFreeExcessListId;
     c->st_host->noVisibleEntries = noVisibleEntries;
+    c->st_host->vis_stale = 1;                                      // the list no longer vouches for every type 3
     c->st_host->scene_external = 1;                                 // next reset: full clear
     TF_CHECK(hipMemcpyAsync(c->st, c->st_host, sizeof(TfDevState), hipMemcpyHostToDevice, c->stream));
     return sync_checked(c);

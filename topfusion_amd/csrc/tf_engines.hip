@@ -279,9 +279,12 @@ extern "C" tf_status tf_scene_alloc(tf_ctx* c, const float intr[4], const float 
     return pose_stage(c, pose_rt, TF_POSE_ALLOC_NOINV, [&] {
         hipError_t e = hipSuccess;
         if (reset_visible_list) {      // renderState_vh->noVisibleEntries = 0 (SceneReconstructionEngine_host.cu:88)
-            static const int zero = 0;
+            static const int zero = 0, one = 1;
             e = hipMemcpyAsync((char*)c->st + offsetof(TfDevState, noVisibleEntries), &zero, sizeof(int), hipMemcpyHostToDevice,
                                c->stream);
+            // the entries of the dropped list keep their types: those still of type 3 are tested all the same (tf_vis.h)
+            if (e == hipSuccess)
+                e = hipMemcpyAsync((char*)c->st + offsetof(TfDevState, vis_stale), &one, sizeof(int), hipMemcpyHostToDevice, c->stream);
         }
         return e == hipSuccess ? tfk_alloc(c, 0, TfAhead{}, 0, only_update_visible_list ? 1 : 0) : e;
     });

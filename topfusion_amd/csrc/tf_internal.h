@@ -78,7 +78,10 @@ struct TfDevState {
     // (render_snapshot / icp_fold_t3)
     float M_render[16];      // M_ray of the frame being rendered
     int render_go;           // the frame took the tracking path (mode 1, ICP ok)
-    int pad3_[3];
+    int vis_stale;           // entries of type 3 may exist that the visible list does not hold (the list was capped
+                             // when it was built, or reset, or set from the host since): the next visible-list build
+                             // tests every entry still of type 3, as buildVisibleList does (vis_count_chunk)
+    int pad3_[2];
     // swapping (tf_swap.hip): the last frame's counts, and the free-list top handed from the
     // swap-in launch to the swap-out launch
     int swap_in, swap_out, swap_realloc, swap_free0;

@@ -555,7 +555,7 @@ k_alloc_discard(TfDevState* __restrict__ st, const int* __restrict__ counts, uns
 // ---------------------------------------------------------------------------------------
 // one chunk of the count pass: allocation counters reset, type 4 -> 0, swap states marked; the
 // thread's 16 types after the clean-up in lo / hi, its count of listed entries returned
-__device__ __forceinline__ int vis_count_chunk(const VisArgs& v, TfDevState* __restrict__ st,
+__device__ __forceinline__ int vis_count_chunk(const VisArgs& v, TfDevState* __restrict__ st, const TfHashEntry* __restrict__ hash,
                                                unsigned char* __restrict__ visType, int* __restrict__ allocCounts,
                                                unsigned char* __restrict__ swapState, unsigned long long& lo_out,
                                                unsigned long long& hi_out)
@@ -575,6 +575,14 @@ __device__ __forceinline__ int vis_count_chunk(const VisArgs& v, TfDevState* __r
         }
     }
     const int base = blockIdx.x * CHUNK + threadIdx.x * 16;
+    // types 3 off the list (TfDevState::vis_stale): k_set_type3 has not seen them, so they get buildVisibleList's
+    // test here (:449-476), on the hash as the allocation left it, and become 4; a listed entry that is still 3 has
+    // passed the same test.  A rare pass of its own ahead of the count, kept out of the unrolled loop below.
+    if (__builtin_expect(st->vis_stale != 0, 0) && base < v.n_total) {
+#pragma unroll 1
+        for (int i = 0; i < 16; ++i)
+            if (visType[base + i] == 3 && !vis_block(hash[base + i], st->M_alloc, v)) visType[base + i] = 4;
+    }
     int cnt = 0;
     lo_out = 0; hi_out = 0;
     if (base < v.n_total) {
@@ -618,7 +626,7 @@ k_vis_count(VisArgs v, TfDevState* __restrict__ st, const TfHashEntry* __restric
 {
     if (st->abort) return;
     unsigned long long lo, hi;
-    const int cnt = vis_count_chunk(v, st, visType, allocCounts, swapState, lo, hi);
+    const int cnt = vis_count_chunk(v, st, hash, visType, allocCounts, swapState, lo, hi);
     int tot = block_sum(cnt);
     if (threadIdx.x == 0) counts[blockIdx.x] = tot;
 }
@@ -639,7 +647,10 @@ k_vis_apply(VisArgs v, TfDevState* __restrict__ st, int n_chunks, const int* __r
         if (h < (int)blockIdx.x) pre += c;
     }
     pre = block_sum(pre); all = block_sum(all);
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->noVisibleEntries = all < v.cap ? all : v.cap;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->noVisibleEntries = all < v.cap ? all : v.cap;
+        st->vis_stale = all > v.cap;                     // entries past the cap keep their type off the list
+    }
     int cnt = 0;
     if (base < v.n_total)
         for (int i = 0; i < 16; ++i) cnt += byte16(lo, hi, i) > 0;
@@ -661,13 +672,13 @@ k_vis_apply(VisArgs v, TfDevState* __restrict__ st, int n_chunks, const int* __r
 // so the wait always ends; a bounded spin still turns a lost count into the frame's sticky error.
 // The last workgroup, which has waited on all the others, writes noVisibleEntries.
 __global__ void __launch_bounds__(256)
-k_vis_build(VisArgs v, TfDevState* __restrict__ st, unsigned char* __restrict__ visType,
+k_vis_build(VisArgs v, TfDevState* __restrict__ st, const TfHashEntry* __restrict__ hash, unsigned char* __restrict__ visType,
             int* __restrict__ allocCounts, unsigned char* __restrict__ swapState, unsigned long long* __restrict__ agg,
             unsigned gen, int* __restrict__ visibleIds, int fault)
 {
     if (st->abort) return;
     unsigned long long lo, hi;
-    const int cnt = vis_count_chunk(v, st, visType, allocCounts, swapState, lo, hi);
+    const int cnt = vis_count_chunk(v, st, hash, visType, allocCounts, swapState, lo, hi);
     int own;
     int r = block_excl_scan(cnt, &own);
     if (threadIdx.x == 0)
@@ -695,6 +706,7 @@ k_vis_build(VisArgs v, TfDevState* __restrict__ st, unsigned char* __restrict__ 
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
         const int all = pre + own;
         st->noVisibleEntries = all < v.cap ? all : v.cap;
+        st->vis_stale = all > v.cap;
     }
     if (!cnt) return;
     r += pre;
@@ -755,7 +767,7 @@ hipError_t tfk_alloc(tf_ctx* c, int snapshot, TfAhead bil, size_t pitch, int onl
                            c->allocCounts, c->allocType, c->winnerKey, c->hash, c->visType, c->allocList, c->excessList,
                            c->n_total);
     if (c->vis_fused) {
-        hipLaunchKernelGGL(k_vis_build, dim3(c->vis_chunks), dim3(256), 0, c->stream, v, c->st, c->visType,
+        hipLaunchKernelGGL(k_vis_build, dim3(c->vis_chunks), dim3(256), 0, c->stream, v, c->st, c->hash, c->visType,
                            c->allocCounts, swapping ? c->swapState : nullptr, c->visAgg, ++c->vis_gen, c->visibleIds,
                            (int)(++c->vis_launches == c->vis_fault_launch));
     } else {

@@ -618,6 +618,7 @@ static tf_status ckpt_load_finish(tf_ctx* c, const unsigned char* data, const st
     st->lastFreeBlockId = lastFreeBlockId;
     st->lastFreeExcessListId = lastFreeExcessListId;
     st->noVisibleEntries = noVisibleEntries;
+    st->vis_stale = 1;                                     // (the stored list may have been a capped one)
     st->frame_counter = info.frame_counter;
     // the free lists and the blocks in use need not be what frames alone leave (a scene that came
     // through tf_upload): every later reset clears everything (tf_reset.h)

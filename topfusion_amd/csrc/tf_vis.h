@@ -48,7 +48,11 @@ __device__ __forceinline__ bool vis_block(const TfHashEntry& e, const float* M, 
 }
 
 // setToType3 (SceneReconstructionEngine_host.cu:343-348) with the visibility test of the
-// entries still of type 3 (:449-476) already applied: 3 = visible, 4 = not (k_set_type3)
+// entries still of type 3 (:449-476) already applied: 3 = visible, 4 = not (k_set_type3).
+// buildVisibleList tests every entry of type 3, on the list or not; an entry keeps a type 3 off the
+// list when the list that held it was capped, reset (resetVisibleList) or replaced from the host.
+// Those are tested where the visible list is built (vis_count_chunk, tf_scene.hip), when
+// TfDevState::vis_stale says that such entries may exist.
 __device__ __forceinline__ void set_type3_pass(const VisArgs& v, int n, const float* M, const TfHashEntry* __restrict__ hash,
                                                const int* __restrict__ visibleIds, unsigned char* __restrict__ visType,
                                                int tid, int stride)
