@@ -14,6 +14,9 @@
 //   ... --save-scene F : write the checkpoint F after the last frame (TopFu::saveScene)
 //   ... --load-scene F --capacity BUCKETS,EXCESS,BLOCKS : resume in tables of these sizes, whatever F was saved
 //                        with (TopFu::loadMapResized: the map is re-hashed on the way in)
+//   ... --merge-scene F [--merge-offset bx,by,bz] : fuse the checkpoint F into the map before the first frame, after
+//                        --load-scene, its blocks moved by that many whole blocks (TopFu::mergeMap); may be given
+//                        more than once, each --merge-offset goes with the --merge-scene before it
 //   ... --view-out F.ppm --view-pose tx,ty,tz,rx,ry,rz [--view-size CxR] : the final map from that camera -> world
 //                        pose (translation in metres, rotation as a Rodrigues vector) at that size (default: the
 //                        frames'), through a free view (TopFu::renderView), as a binary PPM.  With 0 frames and
@@ -40,6 +43,7 @@ int main(int argc, char** argv)
 {
     std::string pgm, ppm, mesh, load_scene, save_scene, capacity, view_out, view_pose, view_size;
     bool mesh_normals = false, mesh_indexed = false, view_whole = false;
+    std::vector<std::string> merge_scenes, merge_offsets;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--pgm") && i + 1 < argc) pgm = argv[++i];
@@ -48,6 +52,8 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--load-scene") && i + 1 < argc) load_scene = argv[++i];
         else if (!std::strcmp(argv[i], "--save-scene") && i + 1 < argc) save_scene = argv[++i];
         else if (!std::strcmp(argv[i], "--capacity") && i + 1 < argc) capacity = argv[++i];
+        else if (!std::strcmp(argv[i], "--merge-scene") && i + 1 < argc) { merge_scenes.push_back(argv[++i]); merge_offsets.push_back(""); }
+        else if (!std::strcmp(argv[i], "--merge-offset") && i + 1 < argc && !merge_scenes.empty()) merge_offsets.back() = argv[++i];
         else if (!std::strcmp(argv[i], "--view-out") && i + 1 < argc) view_out = argv[++i];
         else if (!std::strcmp(argv[i], "--view-pose") && i + 1 < argc) view_pose = argv[++i];
         else if (!std::strcmp(argv[i], "--view-size") && i + 1 < argc) view_size = argv[++i];
@@ -100,6 +106,19 @@ int main(int argc, char** argv)
     } else if (!load_scene.empty()) {
         topfu->loadScene(load_scene);
         scene_line("loaded from", load_scene);
+    }
+    for (size_t k = 0; k < merge_scenes.size(); ++k) {
+        std::array<int, 3> off = { 0, 0, 0 };
+        if (!merge_offsets[k].empty() && std::sscanf(merge_offsets[k].c_str(), "%d,%d,%d", &off[0], &off[1], &off[2]) != 3) {
+            std::fprintf(stderr, "--merge-offset bx,by,bz\n");
+            return 1;
+        }
+        struct tf_merge_report rep;
+        topfu->mergeMap(merge_scenes[k], off, &rep);
+        scene_line("merged from", merge_scenes[k]);
+        std::printf("merged at block offset (%d %d %d): %lld records combined, %lld inserted, %lld revived, %lld skipped, %lld blocks, "
+                    "%lld excess slots\n", off[0], off[1], off[2], rep.records_combined, rep.records_inserted, rep.records_revived,
+                    rep.records_skipped, rep.blocks_used, rep.excess_used);
     }
 
     cuda::Depth depth_device;

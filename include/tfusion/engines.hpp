@@ -238,6 +238,15 @@ namespace tfusion
         {
             tf_engine_check(tf_map_load_resized(ctx_, path.c_str(), report), "tf_map_load_resized");
         }
+        // Map merge (addition: tf_map_merge): a version-1 checkpoint fused into this scene, which must be one
+        // without swapping; its block positions are moved by `offset` whole blocks.  A position the scene holds
+        // with a block is combined voxel by voxel (CombineVoxelInformation), a new one is inserted by the
+        // allocation rule.  Throws with TF_CAPACITY when the free lists are too short (report, when given, says
+        // what is needed); the scene is then as it was.
+        void mergeMap(const std::string& path, const std::array<int, 3>& offset = { 0, 0, 0 }, struct tf_merge_report* report = nullptr)
+        {
+            tf_engine_check(tf_map_merge(ctx_, path.c_str(), offset.data(), report), "tf_map_merge");
+        }
 
     private:
         tf_ctx* ctx_ = nullptr;

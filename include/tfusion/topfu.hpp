@@ -14,6 +14,7 @@
 #include "types.hpp"
 #include "cuda/projective_icp.hpp"
 
+#include <array>
 #include <memory>
 
 namespace tfusion
@@ -386,6 +387,15 @@ namespace tfusion
         {
             check(tf_map_load_resized(ctx_, path.c_str(), report), "tf_map_load_resized");
             after_load();
+        }
+        // Map merge (addition: tf_map_merge): a version-1 checkpoint fused into the map this TopFu holds, its block
+        // positions moved by `offset` whole blocks -- combined voxel by voxel where the map already has the block,
+        // inserted where it does not.  The pose, the poses so far and the tracker's maps stay.  Throws with
+        // TF_CAPACITY when the free lists are too short (report, when given, says what is needed); the map is then
+        // as it was.
+        void mergeMap(const std::string& path, const std::array<int, 3>& offset = { 0, 0, 0 }, struct tf_merge_report* report = nullptr)
+        {
+            check(tf_map_merge(ctx_, path.c_str(), offset.data(), report), "tf_map_merge");
         }
         static struct tf_map_file_info mapFileInfo(const std::string& path)
         {

@@ -698,6 +698,38 @@ struct tf_resize_report {
  * reproduces the saving context's frames when n_buckets is the file's. */
 tf_status tf_map_load_resized(tf_ctx* ctx, const char* path, struct tf_resize_report* report);
 
+/* ---- map merge (addition; DESIGN.md §5 Map merge) ---------------------------------------------------------
+ * A version-1 checkpoint fused into the live scene, block by block.  The file's records with a block (ptr >= 0,
+ * the carried records), in file order and with block_offset added to their block position, are applied one at a
+ * time: the reference's allocation walk looks the position up in the live table.  Found with a block: every voxel
+ * of it becomes CombineVoxelInformation(file voxel, context voxel, maxW) -- a file voxel of weight 0 leaves the
+ * context's as it is.  Found with ptr == -1: the entry takes allocList[lastFreeBlockId--] and the file's block is
+ * copied.  Not found: inserted by the reference's allocation rule -- the free bucket entry, or
+ * excessList[lastFreeExcessListId--] linked to the end of the bucket's chain -- with a block from the alloc list,
+ * the file's block copied, visType 0.  The visible list, the pose, the frame counter, the tracker's maps, the
+ * range image, the raycast result and every view stay as they are; the block grid gets the new blocks; the
+ * context counts as after a hash upload.  Two merges of one file into byte-identical contexts give byte-identical
+ * contexts. */
+struct tf_merge_report {
+    long long records_combined;  /* position already held a block: combined voxel by voxel */
+    long long records_inserted;  /* position new to the table: entry and block added */
+    long long records_revived;   /* position found with ptr == -1: given a block, the file's copied */
+    long long records_skipped;   /* file records with ptr < 0: no voxels to give */
+    long long blocks_used;       /* VBA blocks taken from the free list (inserted + revived) */
+    long long excess_used;       /* excess-list slots taken */
+};
+/* addition (no reference counterpart).  block_offset: NULL or three ints added to every record's block position
+ * (whole blocks).  The context must have use_swapping == 0 and voxel_rgb == 0 and so must the file, a version-1
+ * one; both agree in the bits of voxelSize and mu and in maxW; cols, rows, the capacities and the intrinsics
+ * need not agree.  The file's pose, frame counter, previous maps, visible list, free lists and visType bytes are
+ * ignored.  TF_INVALID_ARG otherwise, for a file tf_map_load would refuse as invalid, for an offset that takes a
+ * carried position outside the int16 range, and for two carried records of one position.  TF_CAPACITY: more
+ * blocks needed than lastFreeBlockId + 1, or more excess slots than lastFreeExcessListId + 1.  Every refusal is
+ * decided before the first write and leaves the context exactly as it was.  report may be NULL; it is filled on
+ * TF_OK and on TF_CAPACITY (what would have been needed), zeroed otherwise.  Synchronous.  tf_scene_ckpt_times
+ * reports the call as a load: the placement kernels in ms[0], the block kernel in ms[1], its bytes in ms[5]. */
+tf_status tf_map_merge(tf_ctx* ctx, const char* path, const int block_offset[3], struct tf_merge_report* report);
+
 /* ---- free views (addition; DESIGN.md §5 Free views) -------------------------------------------------------
  * A tf_view is a second render state bound to a context: its own image size, visible list, range image, raycast
  * result, output image, expected-depth scratch and device state block.  It owns no scene data: it reads the

@@ -79,6 +79,15 @@ class TfResizeReport(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
 
 
+class TfMergeReport(ctypes.Structure):
+    """struct tf_merge_report: what a map merge did (or, on TF_CAPACITY, would have needed)."""
+    _fields_ = [(n, ctypes.c_longlong) for n in ("records_combined", "records_inserted", "records_revived", "records_skipped",
+                                                 "blocks_used", "excess_used")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class TfViewParams(ctypes.Structure):
     """tf_view_params: a free view's size and capacities (0: n_buckets + n_excess / the context's)."""
     _fields_ = [(n, ctypes.c_int) for n in ("cols", "rows", "vis_capacity", "max_render_blocks")]
@@ -232,6 +241,7 @@ def load():
         "tf_map_load": ([P, ctypes.c_char_p], I),
         "tf_map_file_info": ([ctypes.c_char_p, ctypes.POINTER(TfMapFileInfo)], I),
         "tf_map_load_resized": ([P, ctypes.c_char_p, ctypes.POINTER(TfResizeReport)], I),
+        "tf_map_merge": ([P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(TfMergeReport)], I),
         "tf_view_create": ([P, ctypes.POINTER(TfViewParams), ctypes.POINTER(P)], I),
         "tf_view_destroy": ([P], None),
         "tf_view_get_params": ([P, ctypes.POINTER(TfViewParams)], I),

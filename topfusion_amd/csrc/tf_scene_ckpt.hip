@@ -10,8 +10,8 @@
 //   k_ck_pass<true, P>  : every item with its place in each list -- the group's base, the waves before, the lanes below
 //
 // and the passes are: CkSavePass (an entry gets a record / holds a block / has a stored block in the GlobalCache:
-// the record table and the two lists the gathers walk), CkRzPass (the resized load's placement) and CkVisPass (its
-// visible list).  The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of
+// the record table and the two lists the gathers walk), CkRzPass (the resized load's placement), CkVisPass (its
+// visible list) and CkMergePass (the map merge's placement against a live table, tf_map_merge, further down).  The counts fit 32 bits (records <= n_total, blocks <= n_blocks), so the scan is a small kernel of
 // its own over int4 group counts (16 B per 256 items, the fourth lane zero; a pass with fewer lists leaves the
 // others zero) rather than k_mesh_prefix over 64-bit per-entry counts, and shares no scratch with a mesh extraction.
 // No atomics in these passes, and no workgroup waits on another inside a grid.  Beside them:
@@ -29,6 +29,7 @@
 #include "tf_host.h"
 #include "tf_compact.h"
 #include "tf_scene_file.h"
+#include "tf_swap_combine.h"
 
 #include <chrono>
 #include <vector>
@@ -281,6 +282,167 @@ struct CkVisPass {
         if ((bits & 1u) && at < capacity) visibleIds[at] = idx;
     }
 };
+
+// ---- the map merge (tf_map_merge, DESIGN.md §5 Map merge): a version-1 file's carried records (ptr >= 0, file order),
+// moved by a whole-block offset, into the live table.  A position the table holds with a block is combined voxel by
+// voxel, one it holds with ptr == -1 gets a block, a new one is inserted by the reference's allocation rule.
+//
+//   k_mg_find   : the reference's walk per record, read only: the entry that holds pos' (mode combine / revive), or
+//                 (mode insert) the bucket h, the end of its chain e(h) (-1: the bucket entry itself is free) and the
+//                 first round's atomicMin of j per bucket -- k_rz_hash's part for the records not found
+//   k_rz_round  : the ranks m(j) among the records not found, as the resized load's
+//   CkMergePass : counted -- per 256 records those that need an excess slot (not found, and m > 0 or no free bucket
+//                 entry), a block (inserted or revived), and the carried ones; emitted -- t(j), ptr'(j) from the LIVE
+//                 lists (excessList[lastFreeExcessListId - o(j)], allocList[lastFreeBlockId - b(j)]) and, per block of
+//                 the file's payload, the word k_mg_blocks reads: the target ptr, bit 31 set to combine
+//   k_mg_apply  : the new entries, the revived entries' ptr, the link from e(h), the block grid cells
+//   k_mg_blocks : a staged chunk into the VBA, k_ck_copy's shape: copied, or sw_combine(file, context) per voxel
+//
+// Everything up to CkMergePass's emit writes scratch only; a table or list the walk cannot trust (a chain that leaves
+// the excess area or does not end, a ptr or a list value outside its table: uploaded tables) sets `bad`.
+enum { MG_SKIP = 0, MG_COMBINE = 1, MG_REVIVE = 2, MG_INSERT = 3 };
+enum { MG_N_INSERT = 0, MG_N_COMBINE = 1, MG_LEFT = 2, MG_N_REVIVE = 3, MG_BAD = 4, MG_TALLY = 8 };
+
+struct MgOffset { int x, y, z; };
+
+__global__ __launch_bounds__(CK_WG) void k_mg_find(const ck_u2* __restrict__ records, int n, MgOffset off, const TfHashEntry* __restrict__ hash,
+                                                   unsigned mask, int n_buckets, int n_excess, int n_blocks, int* __restrict__ mgH,
+                                                   int* __restrict__ mgRank, int* __restrict__ mgSucc, int* __restrict__ mgFound,
+                                                   int* __restrict__ mgEnd, int* __restrict__ mgMode, int* __restrict__ bid,
+                                                   int* __restrict__ tally)
+{
+    const int ng = (n + CK_WG - 1) / CK_WG;
+    for (int g = blockIdx.x; g < ng; g += gridDim.x) {
+        const int j = g * CK_WG + threadIdx.x;
+        int mode = MG_SKIP;
+        if (j < n) {
+            const ck_u2 a = records[3 * (size_t)j], b = records[3 * (size_t)j + 1], c = records[3 * (size_t)j + 2];
+            int h = -1, found = -1, end = -1;
+            if ((int)c.x >= 0) {
+                const int x = (short)(a.y & 0xffffu) + off.x, y = (short)(a.y >> 16) + off.y, z = (short)(b.x & 0xffffu) + off.z;
+                const unsigned k0 = ((unsigned)x & 0xffffu) | (unsigned)y << 16, k1 = (unsigned)z & 0xffffu;
+                h = tf_hash_index(x, y, z, mask);
+                mode = MG_INSERT;
+                int i = h, steps = 0;
+                ck_u4 e = *reinterpret_cast<const ck_u4*>(hash + i);
+                if ((int)e.w >= -1) {                      // (a free bucket entry: its chain is not followed)
+                    for (;;) {
+                        if (e.x == k0 && (e.y & 0xffffu) == k1 && (int)e.w >= -1) {
+                            found = i;
+                            mode = (int)e.w >= 0 ? MG_COMBINE : MG_REVIVE;
+                            if ((int)e.w >= n_blocks) tally[MG_BAD] = 1;
+                            break;
+                        }
+                        const int o = (int)e.z;
+                        if (o < 1) { end = i; break; }
+                        if (o > n_excess || ++steps > n_excess) { tally[MG_BAD] = 1; mode = MG_SKIP; break; }
+                        i = n_buckets + o - 1;
+                        e = *reinterpret_cast<const ck_u4*>(hash + i);
+                    }
+                }
+                if (mode == MG_INSERT) atomicMin(bid + h, j);
+                else h = -1;
+            }
+            mgH[j] = h;
+            mgRank[j] = -1;
+            mgSucc[j] = -1;
+            mgFound[j] = found;
+            mgEnd[j] = end;
+            mgMode[j] = mode;
+        }
+        const int ni = __popcll(__ballot(mode == MG_INSERT)), nc = __popcll(__ballot(mode == MG_COMBINE)),
+                  nr = __popcll(__ballot(mode == MG_REVIVE));
+        if ((threadIdx.x & 63) == 0) {                     // (sums: the order they land in does not show)
+            if (ni) atomicAdd(tally + MG_N_INSERT, ni);
+            if (nc) atomicAdd(tally + MG_N_COMBINE, nc);
+            if (nr) atomicAdd(tally + MG_N_REVIVE, nr);
+        }
+    }
+}
+
+struct CkMergePass {
+    struct Item {};
+    const int *mgMode, *mgRank, *mgEnd, *mgFound, *mgH;
+    const TfHashEntry* hash;
+    const int *allocList, *excessList;
+    int lastBlock, lastExcess, n_buckets, n_excess, n_blocks;
+    int *mgT, *mgPtr;
+    unsigned* blockWord;
+    int* bad;
+
+    __device__ __forceinline__ unsigned classify(int j, bool in, Item&) const
+    {
+        if (!in) return 0u;
+        const int m = mgMode[j];
+        const bool exc = m == MG_INSERT && (mgRank[j] > 0 || mgEnd[j] >= 0), blk = m == MG_INSERT || m == MG_REVIVE;
+        return (unsigned)exc | (unsigned)blk << 1 | (unsigned)(m != MG_SKIP) << 2;
+    }
+    __device__ __forceinline__ void emit(int j, const Item&, unsigned bits, int at_exc, int at_blk, int at_car) const
+    {
+        const int m = mgMode[j];
+        int t = m == MG_INSERT ? mgH[j] : mgFound[j], ptr = -1;
+        if (bits & 1u) {
+            int x = excessList[lastExcess - at_exc];
+            if ((unsigned)x >= (unsigned)n_excess) { *bad = 1; x = 0; }
+            t = n_buckets + x;
+        }
+        if (bits & 2u) ptr = allocList[lastBlock - at_blk];
+        else if (m == MG_COMBINE) ptr = hash[t].ptr;
+        if ((bits & 4u) && (unsigned)ptr >= (unsigned)n_blocks) { *bad = 1; ptr = 0; }
+        mgT[j] = t;
+        mgPtr[j] = ptr;
+        if (bits & 4u) blockWord[at_car] = (unsigned)ptr | (m == MG_COMBINE ? 0x80000000u : 0u);
+    }
+};
+
+__global__ __launch_bounds__(CK_WG) void k_mg_apply(const ck_u2* __restrict__ records, int n, MgOffset off, int n_buckets,
+                                                    const int* __restrict__ mgMode, const int* __restrict__ mgRank,
+                                                    const int* __restrict__ mgSucc, const int* __restrict__ mgEnd,
+                                                    const int* __restrict__ mgT, const int* __restrict__ mgPtr, TfHashEntry* __restrict__ hash,
+                                                    unsigned char* __restrict__ visType, int2* __restrict__ grid)
+{
+    for (int j = blockIdx.x * CK_WG + threadIdx.x; j < n; j += gridDim.x * CK_WG) {
+        const int m = mgMode[j];
+        if (m != MG_INSERT && m != MG_REVIVE) continue;
+        const int at = mgT[j];
+        TfHashEntry e;
+        if (m == MG_REVIVE) {                              // the ptr word alone: another record may link from this entry
+            e = hash[at];
+            e.ptr = mgPtr[j];
+            hash[at].ptr = e.ptr;
+        } else {
+            const ck_u2 a = records[3 * (size_t)j], b = records[3 * (size_t)j + 1];
+            const int succ = mgSucc[j];
+            e.x = (short)((short)(a.y & 0xffffu) + off.x);
+            e.y = (short)((short)(a.y >> 16) + off.y);
+            e.z = (short)((short)(b.x & 0xffffu) + off.z);
+            e.pad = 0;
+            e.offset = succ >= 0 ? mgT[succ] - n_buckets + 1 : 0;
+            e.ptr = mgPtr[j];
+            hash[at] = e;
+            visType[at] = 0;
+            if (mgRank[j] == 0 && mgEnd[j] >= 0) hash[mgEnd[j]].offset = at - n_buckets + 1;     // (the offset word alone)
+        }
+        grid_set(grid, e, at);
+    }
+}
+
+// 16-byte unit u of the chunk: block u / 128, unit u % 128 of it; word[b]: the block's ptr, bit 31 -- combine
+__global__ __launch_bounds__(CK_WG) void k_mg_blocks(ck_u4* __restrict__ vba, const unsigned* __restrict__ word, int nb, int maxW,
+                                                     const ck_u4* __restrict__ stage)
+{
+    const size_t n = (size_t)nb << 7;
+    for (size_t u = (size_t)blockIdx.x * CK_WG + threadIdx.x; u < n; u += (size_t)gridDim.x * CK_WG) {
+        const unsigned w = word[u >> 7];
+        ck_u4* p = vba + (size_t)(w & 0x7fffffffu) * 128u + ((unsigned)u & 127u);
+        ck_u4 v = __builtin_nontemporal_load(stage + u);
+        if (w >> 31) {
+            const ck_u4 d = *p;
+            v = ck_u4{ sw_combine(v.x, d.x, maxW), sw_combine(v.y, d.y, maxW), sw_combine(v.z, d.z, maxW), sw_combine(v.w, d.w, maxW) };
+        }
+        *p = v;
+    }
+}
 
 // ---- the launchers (ck_groups, ck_grid, tfk_ck_count, tfk_ck_emit: tf_compact.h) ---------------------
 // what the staging buffer and its pinned twin hold: ckpt_chunk_blocks blocks (with their colour)
@@ -680,6 +842,30 @@ static tf_status scene_load(tf_ctx* c, const unsigned char* data, const struct t
     return ckpt_load_finish(c, data, info, lay, info.lastFreeBlockId, info.lastFreeExcessListId, info.noVisibleEntries);
 }
 
+// the rank rounds over n records, `left` of which bid (rzH >= 0, rzRank < 0, the first bids in bid[0, nbk)): a round
+// ranks one record of every bucket that has any left; *rounds of them were needed.  `counter` is a device word.
+static tf_status ck_rank_rounds(tf_ctx* c, int n, int left, const int* rzH, int* rzRank, int* rzSucc, int* bid, int* counter, int* rounds)
+{
+    const int nbk = c->p.n_buckets;
+    const dim3 grid(ck_grid((size_t)n)), wg(CK_WG);
+    for (*rounds = 0; left > 0; ++*rounds) {
+        const int r = *rounds;
+        int* cur = bid + (size_t)(r % 3) * nbk;
+        int* prev = bid + (size_t)((r + 2) % 3) * nbk;
+        int* next = bid + (size_t)((r + 1) % 3) * nbk;
+        const tf_status s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+            const hipError_t e = hipMemsetAsync(counter, 0, sizeof(int), c->stream);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k_rz_round, grid, wg, 0, c->stream, n, r, rzH, rzRank, rzSucc, cur, prev, next, counter);
+            return hipGetLastError();
+        });
+        if (s != TF_OK) return s;
+        TF_CHECK(hipMemcpyAsync(&left, counter, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        TF_CHECK(hipStreamSynchronize(c->stream));
+    }
+    return TF_OK;
+}
+
 // the validated file into a context of other capacities: the placement into scratch, the fit check, then the commit
 // in scene_load's order.  TF_CAPACITY leaves the context as it was.
 static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
@@ -719,20 +905,8 @@ static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const 
     TF_CHECK(hipMemcpyAsync(host_tally, tally, sizeof(host_tally), hipMemcpyDeviceToHost, c->stream));
     TF_CHECK(hipStreamSynchronize(c->stream));
     int rounds = 0;
-    for (int left = host_tally[0]; left > 0; ++rounds) {   // a round ranks one record of every bucket that has any left
-        int* cur = bid + (size_t)(rounds % 3) * nbk;
-        int* prev = bid + (size_t)((rounds + 2) % 3) * nbk;
-        int* next = bid + (size_t)((rounds + 1) % 3) * nbk;
-        s = ck_timed_kernels(c, CK_T_INDEX, [&] {
-            const hipError_t e = hipMemsetAsync(tally + 2, 0, sizeof(int), c->stream);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_rz_round, grid, wg, 0, c->stream, n, rounds, rzH, rzRank, rzSucc, cur, prev, next, tally + 2);
-            return hipGetLastError();
-        });
-        if (s != TF_OK) return s;
-        TF_CHECK(hipMemcpyAsync(&left, tally + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        TF_CHECK(hipStreamSynchronize(c->stream));
-    }
+    s = ck_rank_rounds(c, n, host_tally[0], rzH, rzRank, rzSucc, bid, tally + 2, &rounds);
+    if (s != TF_OK) return s;
     const CkRzPass place = { rec, rzRank, sw, nbk, c->p.n_excess, c->p.n_blocks, rzH, rzT, ptr_dev, sto_dev };
     s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ck_count(c, place, n, grp); });
     if (s != TF_OK) return s;
@@ -773,6 +947,28 @@ static tf_status scene_load_resized(tf_ctx* c, const unsigned char* data, const 
                             nvis.x < c->p.vis_capacity ? nvis.x : c->p.vis_capacity);
 }
 
+// a checkpoint file read whole and validated (the file and check times of tf_scene_ckpt_times start here).  *data is
+// the caller's to free whenever it is not null, also when the validation refused the file
+static tf_status ckpt_read_file(tf_ctx* c, const char* path, double t_call, unsigned char** data, struct tf_map_file_info* minfo,
+                                TfSceneLayout* lay)
+{
+    FILE* f = fopen(path, "rb");
+    if (!f) return TF_INVALID_ARG;
+    long long size = -1;
+    if (fseeko(f, 0, SEEK_END) == 0) size = (long long)ftello(f);
+    if (size < TF_SCENE_HEADER_BYTES || fseeko(f, 0, SEEK_SET) != 0) { fclose(f); return TF_INVALID_ARG; }    // (shorter than either header)
+    memset(c->ckpt_ms, 0, sizeof(c->ckpt_ms));
+    *data = (unsigned char*)malloc((size_t)size);
+    if (!*data) { fclose(f); return TF_OOM; }
+    const size_t got = fread(*data, 1, (size_t)size, f);
+    fclose(f);
+    c->ckpt_ms[CK_T_FILE] = ck_now_ms() - t_call;
+    const double t_check = ck_now_ms();
+    const tf_status s = got == (size_t)size ? tf_map_file_validate(*data, got, minfo, lay) : TF_INVALID_ARG;
+    c->ckpt_ms[CK_T_CHECK] = ck_now_ms() - t_check;
+    return s;
+}
+
 // tf_map_load, or with `resized` tf_map_load_resized: the capacities need not agree, the records are re-hashed
 static tf_status map_load(tf_ctx* c, const char* path, bool resized, struct tf_resize_report* report)
 {
@@ -782,22 +978,11 @@ static tf_status map_load(tf_ctx* c, const char* path, bool resized, struct tf_r
         if (s0 != TF_OK) return s0;
     }
     const double t_call = ck_now_ms();
-    FILE* f = fopen(path, "rb");
-    if (!f) return TF_INVALID_ARG;
-    long long size = -1;
-    if (fseeko(f, 0, SEEK_END) == 0) size = (long long)ftello(f);
-    if (size < TF_SCENE_HEADER_BYTES || fseeko(f, 0, SEEK_SET) != 0) { fclose(f); return TF_INVALID_ARG; }    // (shorter than either header)
-    memset(c->ckpt_ms, 0, sizeof(c->ckpt_ms));
-    unsigned char* data = (unsigned char*)malloc((size_t)size);
-    if (!data) { fclose(f); return TF_OOM; }
-    const size_t got = fread(data, 1, (size_t)size, f);
-    fclose(f);
-    c->ckpt_ms[CK_T_FILE] = ck_now_ms() - t_call;
+    unsigned char* data = nullptr;
     struct tf_map_file_info minfo;
     TfSceneLayout lay;
-    const double t_check = ck_now_ms();
-    tf_status s = got == (size_t)size ? tf_map_file_validate(data, got, &minfo, &lay) : TF_INVALID_ARG;
-    c->ckpt_ms[CK_T_CHECK] = ck_now_ms() - t_check;
+    tf_status s = ckpt_read_file(c, path, t_call, &data, &minfo, &lay);
+    if (s != TF_OK && !data) return s;
     if (s == TF_OK) {
         const tf_params& a = minfo.scene.params;
         const tf_params& b = c->p;
@@ -826,6 +1011,135 @@ extern "C" tf_status tf_map_load_resized(tf_ctx* c, const char* path, struct tf_
     TF_FLUSH(c);
     if (report) memset(report, 0, sizeof(*report));
     return map_load(c, path, true, report);
+}
+
+// the validated version-1 file into the live scene (DESIGN.md §5 Map merge): find, rank, count into scratch; the
+// refusals; then the commit -- entries, links and grid cells, the blocks, the two counters.  Nothing before the
+// commit writes the context.
+static tf_status scene_merge(tf_ctx* c, const unsigned char* data, const struct tf_map_file_info& minfo, const TfSceneLayout& lay,
+                             const int block_offset[3], struct tf_merge_report* report)
+{
+    TfCtxMem tmp(c->mem.fns());
+    unsigned char* rec_dev = nullptr;
+    int *mg = nullptr, *bid = nullptr, *tally = nullptr;
+    unsigned* word = nullptr;
+    int4* grp = nullptr;
+    const struct tf_scene_file_info& info = minfo.scene;
+    if (info.n_records > 0x7fffffffll / 8) return TF_INVALID_ARG;      // (a valid file has at most n_total of them)
+    const int n = (int)info.n_records, ng = ck_groups(n), nbk = c->p.n_buckets;
+    const size_t rec_bytes = (size_t)n * TF_SCENE_RECORD_BYTES;
+    long long carried = 0;
+    const double t_check = ck_now_ms();
+    tf_status s = tf_merge_records_check(data + lay.records_off, n, block_offset, &carried);
+    c->ckpt_ms[CK_T_CHECK] += ck_now_ms() - t_check;
+    if (s != TF_OK) return s;
+    if (carried != info.n_blocks_stored) return TF_INVALID_ARG;        // (the validation's count)
+    s = sync_state(c);                                     // the live counters; TF_HIP_ERROR on a context in error
+    if (s != TF_OK) return s;
+    const int lastBlock = c->st_host->lastFreeBlockId, lastExcess = c->st_host->lastFreeExcessListId;
+    if (lastBlock < -1 || lastBlock >= c->p.n_blocks || lastExcess < -1 || lastExcess >= c->p.n_excess) return TF_INVALID_ARG;     // (tf_set_counters)
+    TF_CHECK(tfk_ckpt_scratch(c));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&rec_dev, rec_bytes)));
+    TF_CHECK(tf_mem_hip(tmp.alloc(&mg, sizeof(int) * 8 * (size_t)n)));             // h, rank, successor, t, found, chain end, ptr', mode
+    TF_CHECK(tf_mem_hip(tmp.alloc(&word, sizeof(unsigned) * (size_t)carried)));    // per block of the payload
+    TF_CHECK(tf_mem_hip(tmp.alloc(&bid, sizeof(int) * 3 * (size_t)nbk)));          // the rounds' three bucket arrays
+    TF_CHECK(tf_mem_hip(tmp.alloc(&grp, sizeof(int4) * (2 * (size_t)ng + 1))));    // the placement pass's scratch
+    TF_CHECK(tf_mem_hip(tmp.alloc(&tally, sizeof(int) * MG_TALLY)));
+    int *mgH = mg, *mgRank = mg + n, *mgSucc = mg + 2 * (size_t)n, *mgT = mg + 3 * (size_t)n, *mgFound = mg + 4 * (size_t)n,
+        *mgEnd = mg + 5 * (size_t)n, *mgPtr = mg + 6 * (size_t)n, *mgMode = mg + 7 * (size_t)n;
+    s = ckpt_h2d(c, rec_dev, data + lay.records_off, rec_bytes);
+    if (s != TF_OK) return s;
+    const ck_u2* rec = (const ck_u2*)rec_dev;
+    const dim3 grid(ck_grid((size_t)n)), wg(CK_WG);
+    const MgOffset off = { block_offset ? block_offset[0] : 0, block_offset ? block_offset[1] : 0, block_offset ? block_offset[2] : 0 };
+    int host_tally[MG_TALLY];
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+        hipError_t e = hipMemsetAsync(bid, 0x7f, sizeof(int) * 3 * (size_t)nbk, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(tally, 0, sizeof(int) * MG_TALLY, c->stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_mg_find, grid, wg, 0, c->stream, rec, n, off, (const TfHashEntry*)c->hash, (unsigned)(nbk - 1), nbk, c->p.n_excess,
+                           c->p.n_blocks, mgH, mgRank, mgSucc, mgFound, mgEnd, mgMode, bid, tally);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    TF_CHECK(hipMemcpyAsync(host_tally, tally, sizeof(host_tally), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    if (host_tally[MG_BAD]) return TF_INVALID_ARG;         // a chain or a ptr of the live table leaves its table
+    int rounds = 0;
+    s = ck_rank_rounds(c, n, host_tally[MG_N_INSERT], mgH, mgRank, mgSucc, bid, tally + MG_LEFT, &rounds);
+    if (s != TF_OK) return s;
+    const CkMergePass place = { mgMode, mgRank, mgEnd, mgFound, mgH, c->hash, c->allocList, c->excessList, lastBlock, lastExcess, nbk,
+                                c->p.n_excess, c->p.n_blocks, mgT, mgPtr, word, tally + MG_BAD };
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ck_count(c, place, n, grp); });
+    if (s != TF_OK) return s;
+    int4 totals;                                           // excess slots, blocks, carried records
+    TF_CHECK(hipMemcpyAsync(&totals, grp + 2 * (size_t)ng, sizeof(totals), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    if (totals.z != carried) return TF_INVALID_ARG;
+    struct tf_merge_report rep;
+    rep.records_combined = host_tally[MG_N_COMBINE];
+    rep.records_inserted = host_tally[MG_N_INSERT];
+    rep.records_revived = host_tally[MG_N_REVIVE];
+    rep.records_skipped = (long long)n - carried;
+    rep.blocks_used = totals.y;
+    rep.excess_used = totals.x;
+    if (totals.y > lastBlock + 1 || totals.x > lastExcess + 1) {
+        if (report) *report = rep;
+        return TF_CAPACITY;
+    }
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] { return tfk_ck_emit(c, place, n, grp); });     // (scratch still)
+    if (s != TF_OK) return s;
+    TF_CHECK(hipMemcpyAsync(host_tally, tally, sizeof(host_tally), hipMemcpyDeviceToHost, c->stream));
+    TF_CHECK(hipStreamSynchronize(c->stream));
+    if (host_tally[MG_BAD]) return TF_INVALID_ARG;         // a free-list value outside its table
+    // ---- the commit ----
+    s = ck_timed_kernels(c, CK_T_INDEX, [&] {
+        hipLaunchKernelGGL(k_mg_apply, grid, wg, 0, c->stream, rec, n, off, nbk, (const int*)mgMode, (const int*)mgRank, (const int*)mgSucc,
+                           (const int*)mgEnd, (const int*)mgT, (const int*)mgPtr, c->hash, c->visType, c->bgrid);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    s = ckpt_payload(c, carried, TF_SCENE_BLOCK_BYTES, nullptr, data + lay.blocks_off, [&](long long b0, int nb) {
+        hipLaunchKernelGGL(k_mg_blocks, dim3(ck_grid((size_t)nb * 128)), dim3(CK_WG), 0, c->stream, (ck_u4*)c->vba, (const unsigned*)(word + b0), nb,
+                           c->p.maxW, (const ck_u4*)c->ckptStage);
+        return hipGetLastError();
+    });
+    if (s != TF_OK) return s;
+    TfDevState* st = c->st_host;                           // (no frame ran since the sync above)
+    st->lastFreeBlockId = lastBlock - totals.y;
+    st->lastFreeExcessListId = lastExcess - totals.x;
+    st->scene_external = 1;                                // as after a hash upload: every later reset clears everything
+    TF_CHECK(hipMemcpyAsync(c->st, c->st_host, sizeof(TfDevState), hipMemcpyHostToDevice, c->stream));
+    s = sync_checked(c);
+    if (s == TF_OK && report) *report = rep;
+    return s;
+}
+
+extern "C" tf_status tf_map_merge(tf_ctx* c, const char* path, const int block_offset[3], struct tf_merge_report* report)
+{
+    TF_FLUSH(c);
+    if (report) memset(report, 0, sizeof(*report));
+    if (!c || !path) return TF_INVALID_ARG;
+    if (c->p.use_swapping || c->p.voxel_rgb) return TF_INVALID_ARG;
+    {
+        const tf_status s0 = sync_checked(c);
+        if (s0 != TF_OK) return s0;
+    }
+    const double t_call = ck_now_ms();
+    unsigned char* data = nullptr;
+    struct tf_map_file_info minfo;
+    TfSceneLayout lay;
+    tf_status s = ckpt_read_file(c, path, t_call, &data, &minfo, &lay);
+    if (s == TF_OK) {
+        const tf_params& a = minfo.scene.params;
+        if (minfo.version != (int)TF_SCENE_VERSION || a.use_swapping || a.voxel_rgb || !bits_equal(a.voxelSize, c->p.voxelSize) ||
+            !bits_equal(a.mu, c->p.mu) || a.maxW != c->p.maxW)
+            s = TF_INVALID_ARG;
+    }
+    if (s == TF_OK) s = scene_merge(c, data, minfo, lay, block_offset, report);
+    free(data);
+    c->ckpt_ms[CK_T_CALL] = ck_now_ms() - t_call;
+    return s;
 }
 
 extern "C" tf_status tf_scene_load(tf_ctx* c, const char* path)

@@ -236,6 +236,45 @@ tf_status tf_map_records_check(const unsigned char* r, long long n_records, cons
     return records_check(r, n_records, pp, n_blocks_stored, true, n_cache_blocks);
 }
 
+// the map merge's own rule over a validated record table (tf_map_merge, DESIGN.md §5 Map merge): the carried
+// records (ptr >= 0) moved by block_offset stay inside the int16 range, and no two of them share a position.
+// The positions as 48-bit keys, sorted: equal neighbours are a duplicate.
+static int key_cmp(const void* a, const void* b)
+{
+    const uint64_t x = *(const uint64_t*)a, y = *(const uint64_t*)b;
+    return x < y ? -1 : x > y ? 1 : 0;
+}
+
+tf_status tf_merge_records_check(const unsigned char* r, long long n_records, const int block_offset[3], long long* n_carried)
+{
+    if (n_records < 0 || (!r && n_records > 0) || !n_carried) return TF_INVALID_ARG;
+    *n_carried = 0;
+    uint64_t* keys = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)(n_records > 0 ? n_records : 1));
+    if (!keys) return TF_OOM;
+    size_t n = 0;
+    tf_status s = TF_OK;
+    for (long long k = 0; k < n_records && s == TF_OK; ++k, r += TF_SCENE_RECORD_BYTES) {
+        if ((int32_t)get32(r + 16) < 0) continue;
+        int16_t xyz[3];
+        memcpy(xyz, r + 4, 6);
+        uint64_t key = 0;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t v = (int64_t)xyz[a] + (block_offset ? (int64_t)block_offset[a] : 0);
+            if (v < INT16_MIN || v > INT16_MAX) s = TF_INVALID_ARG;
+            key = key << 16 | (uint64_t)(uint16_t)(int16_t)(s == TF_OK ? v : 0);
+        }
+        keys[n++] = key;
+    }
+    if (s == TF_OK) {
+        qsort(keys, n, sizeof(uint64_t), key_cmp);
+        for (size_t i = 1; i < n && s == TF_OK; ++i)
+            if (keys[i] == keys[i - 1]) s = TF_INVALID_ARG;
+    }
+    free(keys);
+    *n_carried = (long long)n;
+    return s;
+}
+
 // what follows a decoded header of either version
 static tf_status body_validate(const unsigned char* data, size_t len, const struct tf_scene_file_info* info, bool v2, long long n_cache,
                                const TfSceneLayout* lay)

@@ -81,6 +81,11 @@ bool tf_scene_list_within(const unsigned char* values, size_t n, int32_t bound);
 // them), the list values within their tables.  TF_OK or TF_INVALID_ARG (TF_OOM: no scratch).
 tf_status tf_scene_file_validate(const unsigned char* data, size_t len, struct tf_scene_file_info* info, TfSceneLayout* lay);
 
+// the map merge's rule over a validated record table (tf_map_merge): every carried record (ptr >= 0) moved by
+// block_offset (NULL: none) keeps its position inside the int16 range, and no two carried records share a position.
+// *n_carried: the records with ptr >= 0.  TF_OK or TF_INVALID_ARG (TF_OOM: no scratch)
+tf_status tf_merge_records_check(const unsigned char* records, long long n_records, const int block_offset[3], long long* n_carried);
+
 // ---- both versions (tf_map_save / tf_map_load / tf_map_file_info) ----
 // as tf_scene_layout, by info->version: 1 is tf_scene_layout itself (n_cache_blocks must be 0); 2 requires
 // use_swapping == 1, voxel_rgb == 0 and 0 <= n_cache_blocks <= n_records

@@ -519,6 +519,22 @@ class TopFu:
         self._framed = True
         return rep.as_dict()
 
+    def merge_map(self, path, block_offset=(0, 0, 0)):
+        """Fuses a version-1 checkpoint into the live scene (tf_map_merge): the file's records with a block, moved by
+        block_offset whole blocks, are combined voxel by voxel where the scene already holds the position and
+        inserted where it does not; pose, visible list and tracker maps stay.  Returns the report as a dict
+        (records_combined, records_inserted, records_revived, records_skipped, blocks_used, excess_used).  A file
+        that does not fit the free lists is TfError with TF_CAPACITY; its .report holds what would have been
+        needed.  Every refusal leaves the context as it was."""
+        rep = L.TfMergeReport()
+        off = (ctypes.c_int * 3)(*(int(v) for v in block_offset))
+        status = L.load().tf_map_merge(self._h, str(path).encode(), off, ctypes.byref(rep))
+        if status != L.TF_OK:
+            err = L.TfError(status, "tf_map_merge")
+            err.report = rep.as_dict() if status == L.TF_CAPACITY else None
+            raise err
+        return rep.as_dict()
+
     @classmethod
     def from_map(cls, path, device=None, resize=False, **overrides):
         """from_scene for a map checkpoint of either version: the context is built from the file's
