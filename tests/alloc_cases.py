@@ -21,12 +21,12 @@ import functools
 import numpy as np
 
 from topfusion_amd import synth
+from vbh_ref import (FOUND_BUCKET, FOUND_BUCKET_OUT, FOUND_CHAIN, FOUND_CHAIN_OUT, FOUND_NONE, HASH_DTYPE,  # noqa: F401
+                     chain, empty_hash, hash_index, probe as lookup)      # (lookup: one step's probe, :264-296)
 
 F = np.float32
-HASH_DTYPE = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("pad", "<i2"), ("offset", "<i4"), ("ptr", "<i4")])
 WALK_DTYPE = np.dtype([("pixel", "<i4"), ("step", "<i4"), ("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("entry", "<i4"),
                        ("rtype", "u1"), ("found", "u1")])
-FOUND_NONE, FOUND_BUCKET, FOUND_CHAIN, FOUND_BUCKET_OUT, FOUND_CHAIN_OUT = range(5)   # (_OUT: swapped out, ptr == -1)
 VOXEL, BLOCK = 0.005, 0.04
 TILE, AR_SLOTS, BATCH, CHUNK = 16, 256, 8, 4096               # tf_scene.hip: the request tile, its table, steps per batch
 GRID_HALF = 128                                                # tf_grid_in: block coordinates in [-128, 128)
@@ -72,18 +72,6 @@ def mu_largest(voxel=VOXEL):
         else:
             hi = mid
     return float(lo), float(hi)
-
-
-def hash_index(x, y, z, n_buckets):
-    """hashIndex (RepresentationAccess.hpp:5-7)."""
-    m = 0xffffffff
-    return int((((int(x) * 73856093) & m) ^ ((int(y) * 19349669) & m) ^ ((int(z) * 83492791) & m)) & (n_buckets - 1))
-
-
-def empty_hash(n_total):
-    h = np.zeros(n_total, HASH_DTYPE)
-    h["ptr"] = -2
-    return h
 
 
 # ---- the per-pixel walk ------------------------------------------------------------------------------------------
@@ -133,24 +121,6 @@ def step_blocks(kw, pose, dists):
     pix, step, blk = np.concatenate(pix), np.concatenate(step), np.concatenate(blk)
     order = np.lexsort((step, pix))
     return pix[order], step[order], blk[order]
-
-
-def lookup(hash, n_buckets, b):
-    """One step's probe (:264-296) of the read-only table: (entry, request type, found class)."""
-    bx, by, bz = (int(v) for v in b)
-    idx = hash_index(bx, by, bz, n_buckets)
-    e = hash[idx]
-    match = lambda e: e["x"] == bx and e["y"] == by and e["z"] == bz and e["ptr"] >= -1
-    if match(e):
-        return idx, 0, FOUND_BUCKET_OUT if e["ptr"] == -1 else FOUND_BUCKET
-    if e["ptr"] < -1:
-        return idx, 1, FOUND_NONE
-    while e["offset"] >= 1:
-        idx = n_buckets + int(e["offset"]) - 1
-        e = hash[idx]
-        if match(e):
-            return idx, 0, FOUND_CHAIN_OUT if e["ptr"] == -1 else FOUND_CHAIN
-    return idx, 2, FOUND_NONE
 
 
 def walk(kw, pose, dists, hash):
@@ -414,11 +384,8 @@ def _filler_pool(nb):
     """Block positions far from every case's (y <= -20000, z = 25000), by bucket."""
     x, y = np.meshgrid(np.arange(0, 30000, 7), np.arange(-20000, -20256, -1))
     x, y = x.reshape(-1), y.reshape(-1)
-    with np.errstate(over="ignore"):
-        hsh = ((x.astype(np.int64).astype(np.uint32) * np.uint32(73856093)) ^ (y.astype(np.int64).astype(np.uint32) * np.uint32(19349669))
-               ^ np.uint32((25000 * 83492791) & 0xffffffff)) & np.uint32(nb - 1)
     pool = {}
-    for b, xx, yy in zip(hsh.tolist(), x.tolist(), y.tolist()):
+    for b, xx, yy in zip(hash_index(x, y, 25000, nb).tolist(), x.tolist(), y.tolist()):
         pool.setdefault(b, []).append((xx, yy, 25000))
     return pool
 
@@ -451,13 +418,6 @@ def chain_table(kw, blocks_by_class):
         used_ex.append(want)
         return want
 
-    def chain_end(idx):
-        n = 1
-        while h["offset"][idx] >= 1:
-            idx = nb + int(h["offset"][idx]) - 1
-            n += 1
-        return idx, n
-
     pool = _filler_pool(nb)
 
     taken = {}
@@ -470,7 +430,8 @@ def chain_table(kw, blocks_by_class):
         bucket = hash_index(*b, nb)
         if h["ptr"][bucket] < -1:
             put(bucket, find_filler(bucket), new_ptr())
-        end, n = chain_end(bucket)
+        links = list(chain(h, nb, b))
+        end, n = links[-1], len(links)
         while n < depth:
             off = free_excess()
             put(nb + off, find_filler(bucket), new_ptr())

@@ -39,8 +39,8 @@ import functools
 import numpy as np
 
 from topfusion_amd import synth
+from vbh_ref import HASH_DTYPE, empty_hash, hash_index  # noqa: F401
 
-HASH_DTYPE = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("pad", "<i2"), ("offset", "<i4"), ("ptr", "<i4")])
 VOXEL, BLOCK = 0.005, 0.04
 SUB, RB = 8, 16                               # minmaximg_subsample, renderingBlockSize
 FAR_AWAY, VERY_CLOSE = np.float32(999999.9), np.float32(0.05)
@@ -90,14 +90,6 @@ def params_kw(W, H, intr=None, **over):
     kw = dict(cols=W, rows=H, fx=fx, fy=fy, cx=cx, cy=cy, **TABLES)
     kw.update(over)
     return kw
-
-
-def hash_index(blocks, n_buckets=TABLES["n_buckets"]):
-    """hashIndex (RepresentationAccess.hpp:5-7) of block positions (n, 3)."""
-    b = np.asarray(blocks).astype(np.int64).astype(np.uint32)
-    with np.errstate(over="ignore"):
-        h = (b[:, 0] * np.uint32(73856093)) ^ (b[:, 1] * np.uint32(19349669)) ^ (b[:, 2] * np.uint32(83492791))
-    return (h & np.uint32(n_buckets - 1)).astype(np.int32)
 
 
 def project64(blocks, pose, W, H, intr=None):
@@ -252,15 +244,14 @@ class Scene:
                 if key[1] == "wide" and len(placed) >= WIDE_BOXES + 8:
                     break
                 if b not in entry:
-                    h = int(hash_index(np.array([b]))[0])
+                    h = hash_index(*b, TABLES["n_buckets"])
                     if h in taken:
                         continue
                     taken[h] = b
                     entry[b] = h
                 placed.append(b)
             fams[key] = placed
-        self.hash = np.zeros(N_TOTAL, HASH_DTYPE)
-        self.hash["ptr"] = -2
+        self.hash = empty_hash(N_TOTAL)
         noblock = [b for b in noblock if b in entry]
         ptr = 0
         for h in sorted(taken):
@@ -414,7 +405,7 @@ def inject(state, blocks, n_buckets):
     last, last_excess, n = state["counters"]
     entries = []
     for b in blocks:
-        i = int(hash_index(np.array([b]), n_buckets)[0])
+        i = hash_index(*b, n_buckets)
         if h[i]["ptr"] != -2 or h[i]["offset"] != 0:
             continue
         h[i]["x"], h[i]["y"], h[i]["z"] = b

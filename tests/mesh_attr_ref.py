@@ -37,7 +37,7 @@ def _tiles27(h, vba, rgb, n_buckets, live):
             else:
                 key = (b[0] + ox, b[1] + oy, b[2] + oz)
                 if key not in cache:
-                    cache[key] = M.find_block(h, n_buckets, key)
+                    cache[key] = M.find_live(h, n_buckets, key)[1]
                 p = cache[key]
             if p >= 0:
                 sl = (i, slice(8 * oz + 8, 8 * oz + 16), slice(8 * oy + 8, 8 * oy + 16), slice(8 * ox + 8, 8 * ox + 16))

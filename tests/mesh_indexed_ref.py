@@ -3,7 +3,7 @@ from the specification and not from the kernels.
 
 Triangles, their order, their values and the case tables are mesh_ref's / mesh_attr_ref's.  This module
 derives on its own, per triangle vertex, the Kuhn edge (p, d) it lies on, the hash entry that owns the
-edge (the live entry of block floor(p / 8), by its own walk of the hash), the vertex order (owner entry,
+edge (the live entry of block floor(p / 8), by findVoxel's walk: vbh_ref.find_live), the vertex order (owner entry,
 p's voxel index in the owner block, direction code) and from that the vertex table and the index buffer.
 
     indexed(hash, vba, voxel_size, n_buckets, rgb=None) -> (vertices (nv, 3) f32, indices (nt, 3) u32,
@@ -15,23 +15,7 @@ import numpy as np
 
 import mesh_attr_ref as A
 import mesh_ref as M
-
-
-def find_entry(h, n_buckets, pos):
-    """The hash entry index of the live (ptr >= 0) entry of block `pos`: the bucket entry, then the excess
-    chain; -1 when there is none or a coordinate leaves the short range."""
-    x, y, z = (int(v) for v in pos)
-    if not all(-32768 <= v <= 32767 for v in (x, y, z)):
-        return -1
-    hx = ((x * 73856093) & 0xffffffff) ^ ((y * 19349669) & 0xffffffff) ^ ((z * 83492791) & 0xffffffff)
-    hi = hx & (n_buckets - 1)
-    while True:
-        e = h[hi]
-        if e["x"] == x and e["y"] == y and e["z"] == z and e["ptr"] >= 0:
-            return hi
-        if e["offset"] < 1:
-            return -1
-        hi = n_buckets + int(e["offset"]) - 1
+from vbh_ref import find_live
 
 
 def triangle_edges(h, vba, n_buckets, chunk=64):
@@ -83,7 +67,7 @@ def indexed(h, vba, voxel_size, n_buckets, rgb=None, soup=None, stats=None):
     assert ((D == 0) | (D == 1)).all() and (D.sum(-1) > 0).all()
     blk = P // 8                                                            # floor: negative coordinates too
     ub, binv = np.unique(blk.reshape(-1, 3), axis=0, return_inverse=True)
-    owner_of = np.array([find_entry(h, n_buckets, b) for b in ub], np.int64)
+    owner_of = np.array([find_live(h, n_buckets, b)[0] for b in ub], np.int64)
     assert (owner_of >= 0).all(), "an edge whose owner block is not live"
     owner = owner_of[binv.reshape(-1)].reshape(nt, 3) if nt else np.zeros((0, 3), np.int64)
     lp = (P % 8) @ np.array([1, 8, 64])

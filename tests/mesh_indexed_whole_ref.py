@@ -28,7 +28,7 @@ def ownership(h, vba, state, flags, store, n_buckets, maxW=WR.MAXW):
     h2, v2 = WR.resolve(h, vba, state, flags, store, maxW)
     ent, P, _ = X.triangle_edges(h2, v2, n_buckets)
     ub, binv = np.unique((P // 8).reshape(-1, 3), axis=0, return_inverse=True)
-    owner_of = np.array([X.find_entry(h2, n_buckets, b) for b in ub], np.int64)
+    owner_of = np.array([X.find_live(h2, n_buckets, b)[0] for b in ub], np.int64)
     return ent, owner_of[binv.reshape(-1)].reshape(-1, 3)
 
 

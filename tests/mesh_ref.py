@@ -12,6 +12,8 @@ import itertools
 
 import numpy as np
 
+from vbh_ref import find_live
+
 PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))   # xyz xzy yxz yzx zxy zyx
 
 
@@ -57,26 +59,10 @@ def case_triangles(k, m):
     return out
 
 
-def find_block(h, n_buckets, pos):
-    """findVoxel's walk: the bucket entry, then the excess chain; the VBA block of the first entry at
-    `pos` with ptr >= 0, or -1.  Positions outside the short range are missing."""
-    x, y, z = pos
-    if not all(-32768 <= v <= 32767 for v in pos):
-        return -1
-    hx = ((x * 73856093) & 0xffffffff) ^ ((y * 19349669) & 0xffffffff) ^ ((z * 83492791) & 0xffffffff)
-    hi = hx & (n_buckets - 1)
-    while True:
-        e = h[hi]
-        if e["x"] == x and e["y"] == y and e["z"] == z and e["ptr"] >= 0:
-            return int(e["ptr"])
-        if e["offset"] < 1:
-            return -1
-        hi = n_buckets + int(e["offset"]) - 1
-
-
 def _tiles(h, vba, n_buckets, live):
     """(n, 9, 9, 9) sdf and w arrays, indexed [z, y, x], of each live entry's cube corners: its own
-    block and the seven neighbours (a missing block reads as Voxel_s(): sdf 32767, w 0)."""
+    block and the seven neighbours, each found as findVoxel does (vbh_ref.find_live; a missing block reads as
+    Voxel_s(): sdf 32767, w 0)."""
     v = vba.reshape(-1, 8, 8, 8)
     sdf = np.full((len(live), 16, 16, 16), 32767, np.int32)
     w = np.zeros((len(live), 16, 16, 16), np.int32)
@@ -89,7 +75,7 @@ def _tiles(h, vba, n_buckets, live):
             else:
                 key = (bx + dx, by + dy, bz + dz)
                 if key not in cache:
-                    cache[key] = find_block(h, n_buckets, key)
+                    cache[key] = find_live(h, n_buckets, key)[1]
                 p = cache[key]
             if p >= 0:
                 sl = (n, slice(8 * dz, 8 * dz + 8), slice(8 * dy, 8 * dy + 8), slice(8 * dx, 8 * dx + 8))

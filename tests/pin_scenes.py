@@ -21,15 +21,13 @@ import zlib
 import numpy as np
 
 from topfusion_amd import synth
+from vbh_ref import HASH_DTYPE, VOXEL_DTYPE, chain
 
 N_BUCKETS, N_EXCESS, N_BLOCKS = 0x100000, 0x20000, 0x1000
 N_TOTAL = N_BUCKETS + N_EXCESS
 W, H = 96, 72
 SCENES = ("sphere", "random", "plane")
 CASES = ("sdf_read", "raycast", "integrate", "alloc_pp", "visibility", "expected_depths", "pixels")
-
-HASH_DTYPE = np.dtype([("x", "<i2"), ("y", "<i2"), ("z", "<i2"), ("pad", "<i2"), ("offset", "<i4"), ("ptr", "<i4")])
-VOXEL_DTYPE = np.dtype([("sdf", "<i2"), ("w", "u1"), ("pad", "u1")])
 
 FAR_AWAY, VERY_CLOSE = np.float32(999999.9), np.float32(0.05)     # VisualisationEngine_Shared.hpp:17-23
 MU, MAXW, VOXEL_SIZE, VF_MIN, VF_MAX = np.float32(0.02), 100, np.float32(0.005), np.float32(0.2), np.float32(3.0)
@@ -284,10 +282,8 @@ def _random():
     chains = [entry[nb + 4 * g: nb + 4 * g + 4] for g in range(len(groups))]
     for g, ch in enumerate(chains):
         assert ch[0] < N_BUCKETS and np.all(ch[1:] >= N_BUCKETS)         # bucket entry, then three excess entries
-        walk = [int(ch[0])]
-        while h["offset"][walk[-1]] >= 1:
-            walk.append(N_BUCKETS + int(h["offset"][walk[-1]]) - 1)
-        assert len(walk) == 4
+        walk = list(chain(h, N_BUCKETS, groups[g][0]))
+        assert len(walk) == 4 and walk[0] == ch[0]
         if g % 3 == 0:
             h["ptr"][walk[1]] = -1                                       # swapped out, mid-chain
         if g % 3 == 1:

@@ -2,21 +2,19 @@
 topfusion_amd/csrc/tf_scene_ckpt.hip), over scene_ckpt_ref state dicts.
 
 merge(target, file, offset) is the state the target reaches when the file's carried records (entry.ptr >= 0, in file
-order), moved by `offset` whole blocks, are applied one at a time: the reference's allocation walk (alloc_cases.lookup)
+order), moved by `offset` whole blocks, are applied one at a time: the reference's allocation walk (vbh_ref.probe)
 looks the position up in the live table; found with a block -- every voxel becomes CombineVoxelInformation(file,
 context) (mesh_whole_ref.combine, held to the oracle); found with ptr == -1 -- the entry takes
-allocList[lastFreeBlockId--] and the file's block; not found -- inserted by allocateVoxelBlocksList's rule (the free
-bucket entry, or excessList[lastFreeExcessListId--] linked to the end of the chain), as alloc_cases.Ref.alloc applies
-it.  closed_form() is what a parallel implementation computes instead of the loop.  made_pair() is a target and a file
-in small tables that hit every case."""
+allocList[lastFreeBlockId--] and the file's block; not found -- inserted by allocateVoxelBlocksList's rule
+(vbh_ref.place: the free bucket entry, or excessList[lastFreeExcessListId--] linked to the end of the chain).
+closed_form() is what a parallel implementation computes instead of the loop.  made_pair() is a target and a file in
+small tables that hit every case."""
 import numpy as np
 
-import alloc_cases as A
 import mesh_whole_ref as MW
 import scene_ckpt_ref as R
-from scene_ckpt_ref import HASH_DTYPE, VOXEL_RESET
-from scene_resize_ref import hash_index
-from topfusion_amd.topfu import VOXEL_DTYPE
+import vbh_ref as V
+from vbh_ref import HASH_DTYPE, VOXEL_DTYPE, VOXEL_RESET, hash_index
 
 REPORT_KEYS = ("records_combined", "records_inserted", "records_revived", "records_skipped", "blocks_used", "excess_used")
 COMBINE, REVIVE, INSERT = 1, 2, 3
@@ -49,23 +47,6 @@ def carried(file, offset=(0, 0, 0)):
     return k, pos, e["ptr"][k].astype(np.int64), len(rec)
 
 
-def find_all(hash_, n_buckets, pos):
-    """Every entry the reference's walk (alloc_cases.lookup's: the chain is followed only from a bucket entry with
-    ptr >= -1) passes that holds pos with ptr >= -1."""
-    pos = tuple(int(v) for v in pos)
-    i = hash_index(*pos, n_buckets)
-    found = []
-    if int(hash_["ptr"][i]) < -1:
-        return found
-    while True:
-        e = hash_[i]
-        if (int(e["x"]), int(e["y"]), int(e["z"])) == pos and int(e["ptr"]) >= -1:
-            found.append(int(i))
-        if int(e["offset"]) < 1:
-            return found
-        i = n_buckets + int(e["offset"]) - 1
-
-
 def check(target, file, offset=(0, 0, 0)):
     """Raises Invalid for what tf_map_merge refuses with TF_INVALID_ARG (the file itself is taken as valid)."""
     p, q = target["params"], file["params"]
@@ -95,7 +76,7 @@ def _loop(target, file, offset, unlimited):
     v, e = target["counters"]["lastFreeBlockId"], target["counters"]["lastFreeExcessListId"]
     if unlimited:                                       # virtual slots behind the real ones, taken when those run out
         m = len(pos)
-        hash_ = np.concatenate([hash_, np.full(m, R.reset_entry(), HASH_DTYPE)])
+        hash_ = np.concatenate([hash_, V.empty_hash(m)])
         vis = np.concatenate([vis, np.zeros(m, np.uint8)])
         alloc = np.concatenate([nblk + np.arange(m)[::-1], alloc[:v + 1]])
         excess = np.concatenate([ne + np.arange(m)[::-1], excess[:e + 1]])
@@ -113,8 +94,8 @@ def _loop(target, file, offset, unlimited):
         return ptr
 
     for p, f in zip(pos, fptr):
-        idx, rtype, found = A.lookup(hash_, nb, p)
-        if rtype == 0 and found in (A.FOUND_BUCKET, A.FOUND_CHAIN):
+        idx, rtype, found = V.probe(hash_, nb, p)
+        if rtype == 0 and found in (V.FOUND_BUCKET, V.FOUND_CHAIN):
             ptr = int(hash_["ptr"][idx])
             vba[ptr] = MW.combine(src[f].view(VOXEL_DTYPE), vba[ptr].view(VOXEL_DTYPE), maxW).view(np.uint32)
             n["records_combined"] += 1
@@ -122,13 +103,7 @@ def _loop(target, file, offset, unlimited):
             hash_["ptr"][idx] = take_block(f)
             n["records_revived"] += 1
         else:
-            t = idx
-            if rtype == 2:
-                x = int(excess[e])
-                e -= 1
-                hash_["offset"][idx] = x + 1
-                t = nb + x
-            hash_[t] = (p[0], p[1], p[2], 0, 0, take_block(f))
+            t, e = V.place(hash_, nb, p, take_block(f), excess, e)
             vis[t] = 0
             n["records_inserted"] += 1
     n["blocks_used"], n["excess_used"] = v0 - v, e0 - e
@@ -173,9 +148,9 @@ def closed_form(target, file, offset=(0, 0, 0)):
     seen, last, rows = {}, {}, []
     o = b = 0
     for rk, p in zip(k, pos):
-        idx, rtype, found = A.lookup(hash_, nb, p)
+        idx, rtype, found = V.probe(hash_, nb, p)
         if rtype == 0:
-            if found in (A.FOUND_BUCKET, A.FOUND_CHAIN):
+            if found in (V.FOUND_BUCKET, V.FOUND_CHAIN):
                 rows.append([int(rk), COMBINE, -1, -1, idx, int(hash_["ptr"][idx]), -1])
             else:
                 rows.append([int(rk), REVIVE, -1, -1, idx, int(alloc[v - b]), -1])
@@ -320,12 +295,7 @@ def made_pair(seed=23):
     chained = [int(i) for i in np.flatnonzero((h["offset"][:nb] >= 1) & (h["ptr"][:nb] >= 0))][:3]
     orphaned = set()
     for b in chained:
-        i = b
-        while True:
-            orphaned.add(i)
-            if h["offset"][i] < 1:
-                break
-            i = nb + int(h["offset"][i]) - 1
+        orphaned.update(V.chain(h, nb, (h["x"][b], h["y"][b], h["z"][b])))
         h["ptr"][b] = -2
         target["visType"][b] = 0
     target["visibleIds"] = np.flatnonzero(target["visType"] == 1).astype(np.int32)

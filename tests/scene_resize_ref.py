@@ -3,14 +3,14 @@ topfusion_amd/csrc/tf_scene_ckpt.hip), over scene_ckpt_ref / scene_map_ref state
 
 resize(state, n_buckets, n_excess, n_blocks, vis_capacity) is the state a freshly reset context of those capacities
 reaches when the carried records of `state`'s file (entry.ptr >= -1, in file order) are inserted one at a time by the
-reference's allocation rule (allocateVoxelBlocksList): the bucket entry when the bucket is empty, else the end of the
-bucket's chain linked to excessList[lastFreeExcessListId--]; a block from allocList[lastFreeBlockId--] where the
-record has one.  Records with ptr < -1 have no position and are dropped.  closed_form() is what a parallel
+reference's allocation rule (vbh_ref.place: the bucket entry when the bucket is empty, else the end of the bucket's
+chain linked to excessList[lastFreeExcessListId--]); a block from allocList[lastFreeBlockId--] where the record has
+one.  find_entry is vbh_ref.find_held: the whole chain, every entry that holds the position.  Records with ptr < -1 have no position and are dropped.  closed_form() is what a parallel
 implementation computes instead of the loop."""
 import numpy as np
 
 import scene_map_ref as MR
-from scene_ckpt_ref import HASH_DTYPE, VOXEL_RESET, reset_entry
+from vbh_ref import HASH_DTYPE, VOXEL_RESET, empty_hash, find_held as find_entry, hash_index, place  # noqa: F401
 
 REPORT_KEYS = ("records_carried", "records_dropped", "blocks", "cache_blocks", "excess_used", "longest_chain")
 
@@ -21,12 +21,6 @@ class Capacity(Exception):
     def __init__(self, report):
         super().__init__(str(report))
         self.report = report
-
-
-def hash_index(x, y, z, n_buckets):
-    """hashIndex (RepresentationAccess.hpp) in uint32 arithmetic, one position."""
-    m = 0xffffffff
-    return (((x * 73856093) & m) ^ ((y * 19349669) & m) ^ ((z * 83492791) & m)) & (n_buckets - 1)
 
 
 def _record_fields(state):
@@ -63,7 +57,7 @@ def resize(state, n_buckets, n_excess, n_blocks, vis_capacity):
         raise Capacity(report)
     rgb_src = state["rgb"]
     n_total = n_buckets + n_excess
-    hash_ = np.full(n_total, reset_entry(), HASH_DTYPE)
+    hash_ = empty_hash(n_total)
     vis, st, fl = (np.zeros(n_total, np.uint8) for _ in range(3))
     alloc, excess = np.arange(n_blocks, dtype=np.int32), np.arange(n_excess, dtype=np.int32)
     last_block, last_excess = n_blocks - 1, n_excess - 1
@@ -76,17 +70,6 @@ def resize(state, n_buckets, n_excess, n_blocks, vis_capacity):
         ptr = int(e["ptr"])
         if ptr < -1:
             continue
-        h = hash_index(int(e["x"]), int(e["y"]), int(e["z"]), n_buckets)
-        if int(hash_[h]["ptr"]) < -1:
-            t = h
-        else:
-            end = h
-            while int(hash_[end]["offset"]) >= 1:
-                end = n_buckets + int(hash_[end]["offset"]) - 1
-            x = int(excess[last_excess])
-            last_excess -= 1
-            hash_[end]["offset"] = x + 1
-            t = n_buckets + x
         new_ptr = -1
         if ptr >= 0:
             new_ptr = int(alloc[last_block])
@@ -94,7 +77,7 @@ def resize(state, n_buckets, n_excess, n_blocks, vis_capacity):
             vba[new_ptr] = vba_src[ptr]
             if rgb is not None:
                 rgb[new_ptr] = np.asarray(rgb_src).view(np.uint32).reshape(-1, 512)[ptr]
-        hash_[t] = (e["x"], e["y"], e["z"], 0, 0, new_ptr)
+        t, last_excess = place(hash_, n_buckets, (e["x"], e["y"], e["z"]), new_ptr, excess, last_excess)
         vis[t] = r["visType"]
         if sw:
             st[t], fl[t] = r["swapState"], f
@@ -138,20 +121,6 @@ def closed_form(state, n_buckets, n_excess, n_blocks):
         last[h] = len(rows)
         rows.append([k, h, m, t, new_ptr, -1])
     return rows
-
-
-def find_entry(hash_, n_buckets, pos):
-    """The reference's chain walk: every index on pos's chain that holds pos with ptr >= -1, and the entries walked."""
-    i = hash_index(int(pos[0]), int(pos[1]), int(pos[2]), n_buckets)
-    found, walked = [], 0
-    while True:
-        e = hash_[i]
-        walked += 1
-        if (int(e["x"]), int(e["y"]), int(e["z"])) == tuple(int(v) for v in pos) and int(e["ptr"]) >= -1:
-            found.append(i)
-        if int(e["offset"]) < 1:
-            return found, walked
-        i = n_buckets + int(e["offset"]) - 1
 
 
 # ---- a made map for the tests: random positions in a small table, every kind of record -------------------------------

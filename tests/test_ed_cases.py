@@ -58,7 +58,7 @@ def test_table(pair, oracle_mod):
     assert (live < E.TABLES["n_buckets"]).all() and not s.hash["offset"].any()
     pos = s.blocks_of(live)
     assert [oracle_mod.hash_index(*p, E.TABLES["n_buckets"]) for p in pos[:200]] == live[:200].tolist()
-    assert np.array_equal(E.hash_index(pos), live)
+    assert np.array_equal(E.hash_index(*pos.T, E.TABLES["n_buckets"]), live)
     ptr = s.hash["ptr"][live]
     assert np.array_equal(ptr[ptr >= 0], np.arange(s.n_alloc)) and s.n_alloc <= E.TABLES["n_blocks"]
     assert set(ptr[ptr < 0]) == {-1}                         # (the ptr -2 ones look like every empty entry)

@@ -52,7 +52,7 @@ def test_dense_scene_coverage():
     flat = f.reshape(-1)
     first[flat[::-1]] = np.arange(len(flat))[::-1]
     p, d = P.reshape(-1, 3)[first], D.reshape(-1, 3)[first]
-    owner = np.array([X.find_entry(c["hash"], c["cfg"]["n_buckets"], b) for b in p // 8])
+    owner = np.array([X.find_live(c["hash"], c["cfg"]["n_buckets"], b)[0] for b in p // 8])
     key = np.stack([owner, (p % 8) @ np.array([1, 8, 64]), d @ np.array([1, 2, 4])], -1)
     assert all(tuple(key[i]) < tuple(key[i + 1]) for i in range(len(key) - 1))
 

@@ -158,11 +158,9 @@ def test_scene_properties():
     hi = P.synth.hash_index(pos[..., 0], pos[..., 1], pos[..., 2], P.N_BUCKETS)
     assert np.all(hi == hi[:, :1])
     mid_swapped = mid_free = 0
-    for b in hi[:, 0]:
-        walk = [int(b)]
-        while h["offset"][walk[-1]] >= 1:
-            walk.append(P.N_BUCKETS + int(h["offset"][walk[-1]]) - 1)
-        assert len(walk) == 4
+    for b, first in zip(hi[:, 0], pos[:, 0]):
+        walk = list(P.chain(h, P.N_BUCKETS, first))
+        assert len(walk) == 4 and walk[0] == b
         mid_swapped += any(h["ptr"][w] == -1 for w in walk[1:3])
         mid_free += any(h["ptr"][w] < -1 for w in walk[1:3])
     assert mid_swapped >= 3 and mid_free == 1

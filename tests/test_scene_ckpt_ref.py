@@ -58,7 +58,7 @@ def test_records_ascend_and_visible_only_entry():
     assert np.all(np.diff(rec["index"].astype(np.int64)) > 0)
     # entry 7 has only visType set: a record with ResetScene's entry, and no payload for it
     assert rec[1]["visType"] == 2 and rec[1]["entry"].tobytes() == R.reset_entry().tobytes()
-    assert not rec["pad"].any()
+    assert not (rec["swapState"].any() or rec["hasStoredData"].any() or rec["pad"].any())    # version 1: three pad bytes
     # payloads in record order: entry 3 holds block 1, entry 18 block 0
     o = R.HEADER_BYTES + 24 * 4
     vba = s["vba"].reshape(-1, 512)

@@ -15,6 +15,7 @@ import alloc_cases as A
 import scene_ckpt_ref as R
 import scene_merge_ref as G
 import scene_resize_ref as Z
+import vbh_ref as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OFFSETS = ((0, 0, 0), G.MADE_OFFSET)
@@ -115,7 +116,7 @@ def test_every_carried_position_is_found_once(off):
     _, pos, fptr, _ = G.carried(file, off)
     at = set()
     for p in pos:
-        found = G.find_all(out["hash"], nb, p)
+        found = V.find_held(out["hash"], nb, p, from_free_bucket=False)[0]
         assert len(found) == 1 and int(out["hash"]["ptr"][found[0]]) >= 0, p
         assert A.lookup(out["hash"], nb, p)[:2] == (found[0], 0)
         at.add(found[0])
@@ -123,8 +124,8 @@ def test_every_carried_position_is_found_once(off):
     # what the target could find it still finds, with the same block
     for i in np.flatnonzero(target["hash"]["ptr"] >= 0):
         e = target["hash"][i]
-        if G.find_all(target["hash"], nb, (e["x"], e["y"], e["z"])) == [i]:
-            assert G.find_all(out["hash"], nb, (e["x"], e["y"], e["z"])) == [i] and int(out["hash"]["ptr"][i]) == int(e["ptr"])
+        if V.find_held(target["hash"], nb, (e["x"], e["y"], e["z"]), from_free_bucket=False)[0] == [i]:
+            assert V.find_held(out["hash"], nb, (e["x"], e["y"], e["z"]), from_free_bucket=False)[0] == [i] and int(out["hash"]["ptr"][i]) == int(e["ptr"])
     # blocks distinct; the lists, the visible list, the pose and the maps as they were
     used = out["hash"]["ptr"][out["hash"]["ptr"] >= 0]
     assert len(np.unique(used)) == len(used)
