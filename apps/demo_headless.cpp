@@ -22,6 +22,11 @@
 //                        frames'), through a free view (TopFu::renderView), as a binary PPM.  With 0 frames and
 //                        --load-scene: a saved map's picture and nothing else.
 //   ... --view-whole   : that view reads the GlobalCache of a swapping map as well as the resident blocks
+//   ... --slice-out F.pgm --slice-plane ox,oy,oz,ux,uy,uz,vx,vy,vz [--slice-size CxR] : a cross-section of the final
+//                        map's TSDF (TopFu::slice): pixel (x, y) is the point o + x * u + y * v, in metres, at that
+//                        size (default: the frames').  Grey = (unsigned char)((sdf + 1) * 127.5f), 0 where the
+//                        confidence is 0 (nothing observed); a binary PGM.
+//   ... --slice-whole  : the slice reads the GlobalCache of a swapping map as well
 #include <tfusion/io.hpp>
 #include <tfusion/topfu.hpp>
 
@@ -41,8 +46,8 @@ using namespace tfusion;
 
 int main(int argc, char** argv)
 {
-    std::string pgm, ppm, mesh, load_scene, save_scene, capacity, view_out, view_pose, view_size;
-    bool mesh_normals = false, mesh_indexed = false, view_whole = false;
+    std::string pgm, ppm, mesh, load_scene, save_scene, capacity, view_out, view_pose, view_size, slice_out, slice_plane, slice_size;
+    bool mesh_normals = false, mesh_indexed = false, view_whole = false, slice_whole = false;
     std::vector<std::string> merge_scenes, merge_offsets;
     std::vector<const char*> pos;
     for (int i = 1; i < argc; ++i) {
@@ -60,6 +65,10 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--mesh-normals")) mesh_normals = true;
         else if (!std::strcmp(argv[i], "--mesh-indexed")) mesh_indexed = true;
         else if (!std::strcmp(argv[i], "--view-whole")) view_whole = true;
+        else if (!std::strcmp(argv[i], "--slice-out") && i + 1 < argc) slice_out = argv[++i];
+        else if (!std::strcmp(argv[i], "--slice-plane") && i + 1 < argc) slice_plane = argv[++i];
+        else if (!std::strcmp(argv[i], "--slice-size") && i + 1 < argc) slice_size = argv[++i];
+        else if (!std::strcmp(argv[i], "--slice-whole")) slice_whole = true;
         else pos.push_back(argv[i]);
     }
     int frames = pos.size() > 0 ? std::atoi(pos[0]) : (pgm.empty() ? 100 : 1 << 30);
@@ -191,6 +200,33 @@ int main(int argc, char** argv)
         long view_lit = 0;
         for (size_t k = 0; k < px.size(); k += 4) view_lit += px[k] > 0;
         std::printf("free view %dx%d written to %s: %ld pixels lit\n", vc, vr, view_out.c_str(), view_lit);
+        if (frames == 0 && slice_out.empty()) return 0;
+    }
+    if (!slice_out.empty()) {
+        float q[9];
+        int sc = cols, sr = rows;
+        if (std::sscanf(slice_plane.c_str(), "%f,%f,%f,%f,%f,%f,%f,%f,%f", &q[0], &q[1], &q[2], &q[3], &q[4], &q[5], &q[6], &q[7], &q[8]) != 9 ||
+            (!slice_size.empty() && std::sscanf(slice_size.c_str(), "%dx%d", &sc, &sr) != 2) || sc <= 0 || sr <= 0) {
+            std::fprintf(stderr, "--slice-plane ox,oy,oz,ux,uy,uz,vx,vy,vz  --slice-size CxR\n");
+            return 1;
+        }
+        const size_t n = (size_t)sc * sr;
+        cuda::DeviceArray<float> sdf(n), conf(n);
+        tf_query_out out = {};
+        out.sdf = sdf.ptr();
+        out.confidence = conf.ptr();
+        topfu->slice(q, q + 3, q + 6, sc, sr, TF_QUERY_METRES, slice_whole, out);
+        std::vector<float> hs, hc;
+        sdf.download(hs);
+        conf.download(hc);
+        std::vector<unsigned char> grey(n);
+        long seen = 0;
+        for (size_t k = 0; k < n; ++k) {               // the mapping is the host's: the library returns the TSDF itself
+            grey[k] = hc[k] == 0.0f ? (unsigned char)0 : (unsigned char)((hs[k] + 1.0f) * 127.5f);
+            seen += hc[k] != 0.0f;
+        }
+        io::writePGM8(slice_out, grey.data(), sc, sr);
+        std::printf("slice %dx%d written to %s: %ld pixels observed\n", sc, sr, slice_out.c_str(), seen);
         if (frames == 0) return 0;
     }
     long lit = 0;

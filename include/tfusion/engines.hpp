@@ -222,6 +222,22 @@ namespace tfusion
             tf_engine_check(tf_mesh_save_ply_indexed_whole(ctx_, path.c_str(), attrs), "tf_mesh_save_ply_indexed_whole");
         }
 
+        // Scene queries (additions: tf_scene_query / tf_scene_slice): the TSDF at n device points (3 floats each,
+        // in voxel units or metres) or on the cols x rows pixels of the plane origin + x * u + y * v -- per point
+        // the nearest and the interpolated SDF, the confidence, the entry of the nearest voxel's block, the SDF
+        // gradient and (Voxel_s_rgb scenes, never with whole) the colour, each into the device array of `out` that
+        // is not null.  whole: both tiers of a swapping scene.  Nothing of the scene is written.
+        void query(const float* points, long long n, tf_query_units units, bool whole, const tf_query_out& out)
+        {
+            tf_engine_check(tf_scene_query(ctx_, points, n, (int)units, whole ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT, &out), "tf_scene_query");
+        }
+        void slice(const float origin[3], const float u[3], const float v[3], int cols, int rows, tf_query_units units, bool whole,
+                   const tf_query_out& out)
+        {
+            tf_engine_check(tf_scene_slice(ctx_, origin, u, v, cols, rows, (int)units, whole ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT, &out),
+                            "tf_scene_slice");
+        }
+
         // Map checkpoints (additions: tf_map_save / tf_map_load).  saveMap writes the state the scene resumes
         // from, sized by what is live: of a swapping scene both tiers -- the hash, the active blocks, the
         // GlobalCache's swap states, stored flags and stored blocks, the lists and counters (version 2 of the

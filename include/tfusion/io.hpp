@@ -117,6 +117,18 @@ inline void writePPM(const std::string& path, const uint8_t* rgba, int cols, int
     if (!ok) throw std::runtime_error("short write " + path);
 }
 
+// an 8-bit grey image as a binary PGM (the demo's TSDF slices)
+inline void writePGM8(const std::string& path, const uint8_t* px, int cols, int rows)
+{
+    if (!px || cols <= 0 || rows <= 0) throw std::runtime_error("writePGM8: bad image for " + path);
+    std::FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + path);
+    std::fprintf(f, "P5\n%d %d\n255\n", cols, rows);
+    bool ok = std::fwrite(px, 1, (size_t)cols * rows, f) == (size_t)cols * rows;
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) throw std::runtime_error("short write " + path);
+}
+
 inline void writePGM16(const std::string& path, const uint16_t* px, int cols, int rows)
 {
     std::FILE* f = std::fopen(path.c_str(), "wb");

@@ -276,6 +276,20 @@ namespace tfusion
             check(tf_get_stats(ctx_, &s), "tf_get_stats");
             return s;
         }
+        // Scene queries (additions: tf_scene_query / tf_scene_slice, as Scene::query / Scene::slice): the TSDF at n
+        // device points (3 floats each, voxel units or metres) or on the pixels of the plane origin + x * u + y * v,
+        // into the device arrays of `out` that are not null.  The tracker does not notice.  (TopFu itself runs
+        // without swapping, where whole is the resident reading byte for byte.)
+        void query(const float* points, long long n, tf_query_units units, bool whole, const tf_query_out& out)
+        {
+            check(tf_scene_query(ctx_, points, n, (int)units, whole ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT, &out), "tf_scene_query");
+        }
+        void slice(const float origin[3], const float u[3], const float v[3], int cols, int rows, tf_query_units units, bool whole,
+                   const tf_query_out& out)
+        {
+            check(tf_scene_slice(ctx_, origin, u, v, cols, rows, (int)units, whole ? TF_VIEW_WHOLE : TF_VIEW_RESIDENT, &out),
+                  "tf_scene_slice");
+        }
         // Mesh extraction (additions: the reference has no mesher; tf_mesh_extract / tf_mesh_save_ply).
         // extractMesh: the scene's triangles as 9 floats each (three xyz vertices, right-hand normal
         // towards free space) in `triangles`, resized to fit; returns their number.

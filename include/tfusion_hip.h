@@ -808,6 +808,50 @@ tf_status tf_view_download(tf_view* view, int which, void* host, size_t bytes);
 /* the last find_visible's count and the last expected_depths' tile total (noTotalBlocks) */
 tf_status tf_view_stats(tf_view* view, int* n_visible, int* n_render_blocks);
 
+/* ---- scene queries (addition; DESIGN.md §5 Scene queries) --------------------------------------------------
+ * The TSDF at any point and on any plane, without a camera: per point the reference's three SDF reads
+ * (RepresentationAccess.hpp: readFromSDF_float_uninterpolated, readFromSDF_float_interpolated,
+ * readWithConfidenceFromSDF_float_interpolated), computeSingleNormalFromSDF and drawPixelColour, each with a fresh
+ * IndexCache -- a query has no cache to carry, so a point has one value whatever stands before it in the batch.
+ *
+ * Coordinates.  A point is three floats in voxel units (TF_QUERY_VOXELS), as the reference's functions take them.
+ * With TF_QUERY_METRES each component is first multiplied by the float32 1.0f / voxelSize (one rounding: the
+ * raycast's oneOverVoxelSize).
+ * Range guard.  Decided per point before any memory read, on the voxel-unit coordinates: a point is in range iff
+ * all three satisfy -262136.0f <= c && c <= 262136.0f (+-32767 * 8: every voxel from -1 to +2 around it then has
+ * an int16 block coordinate).  NaN fails the comparison.  An out-of-range point reads as nothing: sdf_nearest 1,
+ * entry -1, sdf 1, confidence 0, normal (0, 0, 0), colour 0 0 0 0.  An in-range point gets what the reference's
+ * functions compute, whatever that is in empty space.
+ * Slices.  Pixel (x, y) of tf_scene_slice is the point (o_k + (float)x * u_k) + (float)y * v_k per component,
+ * every operation rounded to float32 and none contracted; units and guard then apply as above.  A slice is
+ * tf_scene_query on those points, byte for byte, without the points ever existing in memory.
+ * Reading.  TF_VIEW_RESIDENT or TF_VIEW_WHOLE with the meaning they have for a view.  Under the whole reading
+ * every voxel read goes through the resolution of its block over the VBA and the GlobalCache, and entry is the
+ * first entry of the chain that resolves; colour is refused (a swapping scene has no colour plane).  On a context
+ * without stored data the whole reading is byte-identical to the resident one; without use_swapping it runs the
+ * resident kernels.
+ * Status.  n == 0 is TF_OK with nothing written; outputs past n are never touched.  TF_INVALID_ARG: a NULL ctx,
+ * NULL points with n > 0, n < 0, cols or rows <= 0, an unknown units or reading, out NULL or every output NULL,
+ * colour without voxel_rgb or with TF_VIEW_WHOLE.  A context in error returns TF_HIP_ERROR.
+ * Ordering.  The call flushes a pending per-call frame, runs on the context stream after the caller's work on the
+ * default stream, and returns when done.  Nothing of the context is written -- no TF_BUF_* buffer, counter,
+ * visType, device state field or tile order -- so a context with queries between its frames produces the frames
+ * of one without, bit for bit. */
+typedef enum tf_query_units { TF_QUERY_VOXELS = 0, TF_QUERY_METRES = 1 } tf_query_units;
+typedef struct tf_query_out {        /* device pointers; each skipped when NULL; at least one non-NULL */
+    float*   sdf_nearest;  /* [n]    readFromSDF_float_uninterpolated */
+    int*     entry;        /* [n]    hash entry whose block holds the nearest voxel, -1: none (the fresh-cache vmIndex - 1) */
+    float*   sdf;          /* [n]    readFromSDF_float_interpolated (== readWithConfidence...'s value) */
+    float*   confidence;   /* [n]    readWithConfidenceFromSDF_float_interpolated's confidence */
+    float*   normal;       /* [n][3] computeSingleNormalFromSDF, as the reference leaves it (not normalised) */
+    uint8_t* colour;       /* [n][4] drawPixelColour; voxel_rgb contexts only; 4-byte aligned (stored as one word) */
+} tf_query_out;
+tf_status tf_scene_query(tf_ctx* ctx, const float* dev_points /* [n][3] */, long long n, int units, int reading,
+                         const tf_query_out* out);
+/* n = cols * rows, row-major */
+tf_status tf_scene_slice(tf_ctx* ctx, const float origin[3], const float u[3], const float v[3], int cols, int rows,
+                         int units, int reading, const tf_query_out* out);
+
 #ifdef __cplusplus
 }
 #endif

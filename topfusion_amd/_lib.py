@@ -19,6 +19,7 @@ TF_CAPACITY = 7                                # tf_map_load_resized: the map do
                                                # tf_view_find_visible / tf_view_render: the view's list is too short
 TF_VIEW_VISIBLE_IDS, TF_VIEW_RANGE, TF_VIEW_RAYCAST, TF_VIEW_IMAGE = range(4)   # tf_view_download
 TF_VIEW_RESIDENT, TF_VIEW_WHOLE = 0, 1      # tf_set_view_reading
+TF_QUERY_VOXELS, TF_QUERY_METRES = 0, 1     # tf_scene_query / tf_scene_slice: the points' units
 TF_MESH_NORMALS, TF_MESH_COLOURS = 1, 2       # tf_mesh_save_ply_attr's attrs
 TF_MESH_INDEXED = 4
 TF_MESH_WHOLE = 8                              # the reading over both tiers of a swapping scene (tf_mesh_extract_whole)
@@ -91,6 +92,11 @@ class TfMergeReport(ctypes.Structure):
 class TfViewParams(ctypes.Structure):
     """tf_view_params: a free view's size and capacities (0: n_buckets + n_excess / the context's)."""
     _fields_ = [(n, ctypes.c_int) for n in ("cols", "rows", "vis_capacity", "max_render_blocks")]
+
+
+class TfQueryOut(ctypes.Structure):
+    """tf_query_out: the device output pointers of a scene query, each skipped when NULL."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("sdf_nearest", "entry", "sdf", "confidence", "normal", "colour")]
 
 
 class TfTotals(ctypes.Structure):
@@ -255,6 +261,8 @@ def load():
         "tf_view_render": ([P, P, P, I, P, S], I),
         "tf_view_download": ([P, I, P, S], I),
         "tf_view_stats": ([P, ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "tf_scene_query": ([P, P, ctypes.c_longlong, I, I, ctypes.POINTER(TfQueryOut)], I),
+        "tf_scene_slice": ([P, P, P, P, I, I, I, I, ctypes.POINTER(TfQueryOut)], I),
     }
     override = bool(os.environ.get("TFUSION_HIP_LIB"))    # an A/B build (tools/gpu_ab_c3i.sh) may be older
     for name, (args, res) in sig.items():

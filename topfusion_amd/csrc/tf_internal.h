@@ -582,6 +582,15 @@ hipError_t tfk_render_type(tf_ctx* c, const TfTarget& t, int type);
 hipError_t tfk_icp_maps(tf_ctx* c, const TfTarget& t, float4* const pts[TF_LEVELS], float4* const nrm[TF_LEVELS]);
 hipError_t tfk_expected_depths(tf_ctx* c, const TfTarget& t, int project_done, int keep_bins);
 hipError_t ed_spill_all(tf_ctx* c, const TfTarget& t);
+// scene queries (tf_query.hip): the reads of n points -- pts, or with slice non-null the pixels of its plane --
+// scaled to voxel units (scale: 1 or 1 / voxelSize), one launch per output group asked for (the four SDF reads,
+// the gradient, the colour).  Reads the scene alone; writes the caller's outputs alone.
+struct TfQuerySlice {
+    float o[3], u[3], v[3];
+    int cols;
+};
+hipError_t tfk_scene_query(tf_ctx* c, const float* pts, const TfQuerySlice* slice, long long n, float scale, int whole,
+                           const tf_query_out& out);
 // CreateICPMaps raycast + renderImage, one launch (frame path); next: + that frame's dists/pyramid/normals
 // + dists/pyramid/normals of pyr, bilateral of bil; fuse_ed: CreateExpectedDepths' fill in the same
 // grid (frame path, when tfk_ed_fused: then no separate tfk_expected_depths launch)

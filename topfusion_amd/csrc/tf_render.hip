@@ -1877,3 +1877,145 @@ hipError_t tfk_raycast_pair(tf_ctx* c, TfAhead pyr, TfAhead bil, size_t pitch, i
               order ? c->tile_cost : nullptr);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------
+// Scene queries (tf_scene_query / tf_scene_slice): the reads above at caller points instead of a
+// ray's -- readFromSDF_float_uninterpolated, readFromSDF_float_interpolated, readWithConfidenceFromSDF_float_
+// interpolated (RepresentationAccess.hpp:129-199), computeSingleNormalFromSDF (:340-453) and drawPixelColour
+// (VisualisationEngine_Shared.hpp:312-322), each with a fresh IndexCache.  One point per lane.  A batch's points are
+// incoherent where a ray's samples are not: any wave may mix blocks inside the grid, blocks outside it (the hash
+// walk) and missing blocks, and the lookups above decide their slow path per wave (wave_any), so all 64 lanes
+// reach them together: a lane past n takes the last point and a lane outside the range guard the origin, and
+// only their stores differ.
+// Three kernels per reading and point source, one per output group, chosen from the compiler's resource report
+// (profiles/scene_query_resources.txt): the SDF reads hold the eight corner words, the gradient its 4x4x4
+// neighbourhood and an LDS slot per thread, the colour the colour plane -- a caller asking for sdf alone pays
+// neither the gradient's registers nor its LDS.
+// ---------------------------------------------------------------------------------------
+#define TF_QUERY_LIMIT 262136.0f        // +-32767 * 8: every voxel from -1 to +2 around the point has an int16 block coordinate
+enum { TF_Q_SDF = 0, TF_Q_NORMAL = 1, TF_Q_COLOUR = 2 };
+
+// where the points come from: an array, or the pixels of a plane (tf_scene_slice: the same kernels, no array)
+struct QueryPoints { const float* pts; };
+__device__ __forceinline__ void query_point(const QueryPoints& g, long long i, float* p)
+{
+    const float* s = g.pts + 3 * i;
+    p[0] = s[0]; p[1] = s[1]; p[2] = s[2];
+}
+__device__ __forceinline__ void query_point(const TfQuerySlice& g, long long i, float* p)
+{
+    // (an index below 2^32 -- every slice a test or a screen asks for -- divides in 32 bits)
+    const bool small = (unsigned long long)i <= 0xffffffffull;
+    const int yi = small ? (int)((unsigned)i / (unsigned)g.cols) : (int)(i / g.cols);
+    const float x = (float)(int)(i - (long long)yi * g.cols), y = (float)yi;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = __fadd_rn(__fadd_rn(g.o[k], __fmul_rn(x, g.u[k])), __fmul_rn(y, g.v[k]));
+}
+
+// the eight interpolation corners of pt with their voxel words kept: the nearest voxel (ROUND(pt)) is corner
+// Corners::cu of them, so one fetch answers the three SDF reads.  Resident: q.hU is the nearest voxel's entry.
+__device__ __forceinline__ void query_corners(const SceneView& s, const float* pt, Corners& q)
+{
+    corners_lookup(s, pt, q);
+    corners_vox(s, q);
+}
+// ... over both tiers (interp_at(SceneViewWhole)'s lookups and loads)
+__device__ __forceinline__ void query_corners(const SceneViewWhole& s, const float* pt, Corners& q)
+{
+    unsigned o[8];
+    const bool in = corners_prep(pt, q, o);
+    const int X[2] = { q.bx, q.bx + q.sx }, Y[2] = { q.by, q.by + q.sy }, Z[2] = { q.bz, q.bz + q.sz };
+    int sto[8];
+    wblk_find8(s, X, Y, Z, o, in, q.voff, sto);
+    const int lx[2] = { lin_x(q.fx), lin_x(q.fx + 1) }, ly[2] = { lin_y(q.fy), lin_y(q.fy + 1) };
+    const int lz[2] = { lin_zg(q.fz), lin_zg(q.fz + 1) };
+    int lin[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) lin[c] = lx[c & 1] + ly[(c >> 1) & 1] + lz[c >> 2];
+    wvox8(s, q.voff, sto, lin, q.raw);
+}
+// the entry whose block holds the nearest voxel: the first of the chain that resolves (asked for only where the
+// caller wants it: the corner lookups keep offsets, not entries)
+__device__ __forceinline__ int query_entry(const SceneView&, const float*, const Corners& q) { return q.hU; }
+__device__ __forceinline__ int query_entry(const SceneViewWhole& s, const float* pt, const Corners&)
+{
+    return blk_ent(blk_one(s, vblk(tf_round(pt[0])), vblk(tf_round(pt[1])), vblk(tf_round(pt[2]))));
+}
+
+template <int WHAT, class S, class G>
+__global__ void __launch_bounds__(256)
+k_scene_query(S s, G gen, long long n, float scale, tf_query_out out, const unsigned* __restrict__ rgb_guard)
+{
+    constexpr bool WHOLE = std::is_same<S, SceneViewWhole>::value;
+    static_assert(!WHOLE || WHAT != TF_Q_COLOUR, "a swapping scene has no colour plane");
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n;                 // the last wave's tail: the last point again, and no store
+    float p[3];
+    query_point(gen, live ? i : n - 1, p);
+    bool ok = true;                          // the range guard, before any read of the scene (NaN fails it)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p[k] = __fmul_rn(p[k], scale);       // voxel units: scale = 1, which changes no value
+        ok = ok && -TF_QUERY_LIMIT <= p[k] && p[k] <= TF_QUERY_LIMIT;
+    }
+    if (!ok) p[0] = p[1] = p[2] = 0.0f;      // a stand-in inside the range; its results are overwritten below
+    if constexpr (WHAT == TF_Q_SDF) {
+        Corners q;
+        query_corners(s, p, q);
+        float conf;
+        const float sdf = interp_sdf_conf(q, &conf);
+        const unsigned near = sel_tree(q.raw, (q.cu & 1) != 0, (q.cu & 2) != 0, (q.cu & 4) != 0);
+        // a missing block reads Voxel_s(): 32767 / 32767 = 1
+        if (out.sdf_nearest && live) out.sdf_nearest[i] = ok ? tf_short_to_float((short)(near & 0xffffu)) : 1.0f;
+        if (out.sdf && live) out.sdf[i] = ok ? sdf : 1.0f;
+        if (out.confidence && live) out.confidence[i] = ok ? conf : 0.0f;
+        if (out.entry) {                     // (uniform: the whole reading's lookup is the wave's)
+            const int e = query_entry(s, p, q);
+            if (live) out.entry[i] = ok ? e : -1;
+        }
+    } else if constexpr (WHAT == TF_Q_NORMAL) {
+        constexpr int VSTRIDE = WHOLE ? VTAB_STRIDE_WHOLE : VTAB_STRIDE;
+        __shared__ int vtab[256 * VSTRIDE];
+        float nn[3];
+        sdf_normal(s, p, nn, &vtab[threadIdx.x * VSTRIDE]);
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) out.normal[3 * i + k] = ok ? nn[k] : 0.0f;
+        }
+    } else if constexpr (!WHOLE) {
+        const uchar4 v = colour_at(s, rgb_guard, p);
+        if (live) reinterpret_cast<uchar4*>(out.colour)[i] = ok ? v : make_uchar4(0, 0, 0, 0);
+    }
+}
+
+template <class S, class G>
+static void query_launch(tf_ctx* c, const S& s, const G& gen, long long n, float scale, const tf_query_out& o)
+{
+    const dim3 g((unsigned)((n + 255) / 256)), b(256);
+    const unsigned* cg = c->vba_rgb_guard;
+    if (o.sdf_nearest || o.entry || o.sdf || o.confidence)
+        hipLaunchKernelGGL((k_scene_query<TF_Q_SDF, S, G>), g, b, 0, c->stream, s, gen, n, scale, o, cg);
+    if (o.normal) hipLaunchKernelGGL((k_scene_query<TF_Q_NORMAL, S, G>), g, b, 0, c->stream, s, gen, n, scale, o, cg);
+    if constexpr (!std::is_same<S, SceneViewWhole>::value) {
+        if (o.colour) hipLaunchKernelGGL((k_scene_query<TF_Q_COLOUR, S, G>), g, b, 0, c->stream, s, gen, n, scale, o, cg);
+    }
+}
+
+hipError_t tfk_scene_query(tf_ctx* c, const float* pts, const TfQuerySlice* slice, long long n, float scale, int whole,
+                           const tf_query_out& out)
+{
+    if (n <= 0) return hipSuccess;
+    if (n > 0x7fffffffLL * 256) return hipErrorInvalidValue;           // one workgroup per 256 points
+    const QueryPoints qp = { pts };
+    if (whole && c->p.use_swapping) {          // without a GlobalCache the whole reading is the resident one
+        if (out.colour) return hipErrorInvalidValue;
+        const SceneViewWhole w = scene_view_whole(c);
+        if (slice) query_launch(c, w, *slice, n, scale, out);
+        else query_launch(c, w, qp, n, scale, out);
+    } else {
+        const SceneView s = scene_view(c);
+        if (slice) query_launch(c, s, *slice, n, scale, out);
+        else query_launch(c, s, qp, n, scale, out);
+    }
+    return hipGetLastError();
+}

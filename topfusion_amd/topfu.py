@@ -745,6 +745,74 @@ class TopFu:
             return
         L.check(L.load().tf_mesh_save_ply_attr(self._h, str(path).encode(), attrs), "tf_mesh_save_ply_attr")
 
+    # -- scene queries (additions: tf_scene_query / tf_scene_slice; DESIGN.md §5 Scene queries) --------------
+    _QUERY_OUTS = (("sdf_nearest", np.float32, ()), ("entry", np.int32, ()), ("sdf", np.float32, ()),
+                   ("confidence", np.float32, ()), ("normal", np.float32, (3,)), ("colour", np.uint8, (4,)))
+
+    def _query(self, n, normals, colours, call, where):
+        want = [k for k, _, _ in self._QUERY_OUTS if (k != "normal" or normals) and (k != "colour" or colours)]
+        outs = {k: np.empty((n,) + tail, dt) for k, dt, tail in self._QUERY_OUTS if k in want}
+        hip = L.hip_runtime()
+        qo = L.TfQueryOut()
+        devs = []
+        try:
+            for k, o in outs.items():
+                d = ctypes.c_void_p()
+                if hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(max(o.nbytes, 16))) != 0:
+                    raise L.TfError(L.TF_OOM, "hipMalloc (query)")
+                devs.append(d)
+                setattr(qo, k, d.value)
+            L.check(call(hip, qo, devs), where)
+            for o, d in zip(outs.values(), devs):
+                if n and hip.hipMemcpy(_ptr(o), d, ctypes.c_size_t(o.nbytes), 2) != 0:      # hipMemcpyDeviceToHost
+                    raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (query)")
+        finally:
+            for d in devs:
+                if d:
+                    hip.hipFree(d)
+        return outs
+
+    @staticmethod
+    def _query_units(units):
+        if units not in ("m", "voxels"):
+            raise L.TfError(L.TF_INVALID_ARG, f"query units {units!r} (\"m\" or \"voxels\")")
+        return L.TF_QUERY_METRES if units == "m" else L.TF_QUERY_VOXELS
+
+    def query(self, points, units="m", whole=False, normals=False, colours=False):
+        """The TSDF at host points (n, 3) float32, in metres or ("voxels") voxel units (tf_scene_query): a dict of
+        numpy arrays -- sdf_nearest, entry, sdf, confidence, and with normals / colours normal (n, 3) (the SDF
+        gradient as the reference leaves it) / colour (n, 4) RGBA (voxel_rgb contexts, never with whole=True).
+        A point outside +-262136 voxels reads as nothing (1, -1, 1, 0, zeros).  whole: both tiers of a swapping
+        scene.  Through temporary device buffers."""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise L.TfError(L.TF_INVALID_ARG, "query points: (n, 3) float32")
+        n, u, r = len(pts), self._query_units(units), L.TF_VIEW_WHOLE if whole else L.TF_VIEW_RESIDENT
+
+        def call(hip, qo, devs):
+            d = ctypes.c_void_p()
+            if hip.hipMalloc(ctypes.byref(d), ctypes.c_size_t(max(pts.nbytes, 16))) != 0:
+                raise L.TfError(L.TF_OOM, "hipMalloc (query)")
+            devs.append(d)
+            if n and hip.hipMemcpy(d, _ptr(pts), ctypes.c_size_t(pts.nbytes), 1) != 0:      # hipMemcpyHostToDevice
+                raise L.TfError(L.TF_HIP_ERROR, "hipMemcpy (query)")
+            return L.load().tf_scene_query(self._h, d, n, u, r, ctypes.byref(qo))
+        return self._query(n, normals, colours, call, "tf_scene_query")
+
+    def slice(self, origin, u, v, cols, rows, units="m", whole=False, normals=False, colours=False):
+        """query() on the plane origin + x * u + y * v, x < cols, y < rows (tf_scene_slice; the points are made on
+        the device, in float32): the same dict with arrays of shape (rows, cols[, k])."""
+        o3, u3, v3 = (np.ascontiguousarray(a, np.float32).reshape(3) for a in (origin, u, v))
+        cols, rows = int(cols), int(rows)
+        if cols <= 0 or rows <= 0:
+            raise L.TfError(L.TF_INVALID_ARG, "slice size")
+        un, r = self._query_units(units), L.TF_VIEW_WHOLE if whole else L.TF_VIEW_RESIDENT
+
+        def call(hip, qo, devs):
+            return L.load().tf_scene_slice(self._h, _ptr(o3), _ptr(u3), _ptr(v3), cols, rows, un, r, ctypes.byref(qo))
+        outs = self._query(cols * rows, normals, colours, call, "tf_scene_slice")
+        return {k: a.reshape((rows, cols) + a.shape[1:]) for k, a in outs.items()}
+
     # typed views
     def hash(self):
         return self.download(L.TF_BUF_HASH).view(HASH_DTYPE)
